@@ -5,6 +5,7 @@ line and (N=1) the CPU port of the reference algorithm beside it.
 
     python bench.py --gpus 1 --steps K --warmup W
     python bench.py --workload poisson|galerkin|rmat [--scale S] [--grid G]     (one other config as the headline)
+    python bench.py ... --dump-outputs DIR      (the last timed step's result as DIR/<name>.npy, for comparing builds)
     python -m torch.distributed.run --nnodes=1 --nproc-per-node N --master-addr 127.0.0.1 \
         --master-port P bench.py --gpus N --steps K --warmup W
 
@@ -70,7 +71,67 @@ def parse():
                          "(exercises the multi-rank logic where only one GPU is available; not a measurement)")
     ap.add_argument("--dist-path", action="store_true",
                     help="with --gpus 1: run the row-block + all-to-allv path on a 1-rank group (rehearsal of the N>1 code)")
-    return ap.parse_args()
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write what the last timed step returned to its caller as DIR/<name>.npy "
+                         "(float64): the digest, or for the COO sink nnz(C) and a fixed seeded sample of C's tuples")
+    args = ap.parse_args()
+    if args.steps < 1:
+        ap.error("--steps must be at least 1")
+    if args.warmup < 0:
+        ap.error("--warmup must not be negative")
+    return args
+
+
+# ------------------------------------------------------------------------------------------ --dump-outputs
+
+DUMP_MAX_BYTES = 64 << 20      # all files of one dump together
+DUMP_BLOCK = 1024              # COO sink: C is sampled in runs of this many consecutive (row-major) tuples ...
+DUMP_BLOCKS = 1024             # ... this many runs at most (1M tuples, 32 MB as four float64 arrays)
+DUMP_SEED = 12345              # which runs: fixed, so that two builds are sampled at the same positions
+
+
+def digest_arrays(nnz, vsum, vhash):
+    """The digest sink's answer (count, value sum, index hash); the 64-bit hash as two exact 32-bit halves."""
+    import numpy as np
+    vhash = int(vhash)
+    return {"nnz_c": np.array([int(nnz)], np.float64), "digest_sum": np.array([float(vsum)], np.float64),
+            "digest_hash": np.array([vhash >> 32, vhash & 0xffffffff], np.float64)}
+
+
+def coo_arrays(ctx, res):
+    """A COO-sink result: nnz(C), its shape, and C's tuples -- all of them up to DUMP_BLOCK * DUMP_BLOCKS, beyond that
+    DUMP_BLOCKS runs of DUMP_BLOCK consecutive tuples at seeded positions -- with the position of every sampled tuple."""
+    import numpy as np
+    n = int(res.nnz)
+    nblk = -(-n // DUMP_BLOCK)
+    if nblk <= DUMP_BLOCKS:
+        blocks = np.arange(nblk, dtype=np.int64)
+    else:
+        blocks = np.sort(np.random.default_rng(DUMP_SEED).choice(nblk, DUMP_BLOCKS, replace=False))
+    pos, rows, cols, vals = [], [], [], []
+    for b in blocks.tolist():
+        lo = b * DUMP_BLOCK
+        cnt = min(DUMP_BLOCK, n - lo)
+        pos.append(np.arange(lo, lo + cnt, dtype=np.int64))
+        rows.append(ctx.to_host(res.idx0 + 4 * lo, cnt, np.int32))
+        cols.append(ctx.to_host(res.idx1 + 4 * lo, cnt, np.int32))
+        vals.append(ctx.to_host(res.val + 8 * lo, cnt, np.float64))
+
+    def cat(parts):
+        return np.concatenate(parts).astype(np.float64) if parts else np.zeros(0, np.float64)
+    return {"nnz_c": np.array([n], np.float64), "c_shape": np.array([int(res.shape0), int(res.shape1)], np.float64),
+            "c_pos": cat(pos), "c_row": cat(rows), "c_col": cat(cols), "c_val": cat(vals)}
+
+
+def write_dump(dirname, arrays):
+    import numpy as np
+    total = sum(a.nbytes for a in arrays.values())
+    if total > DUMP_MAX_BYTES:
+        raise RuntimeError("--dump-outputs: %d bytes exceed the %d byte limit" % (total, DUMP_MAX_BYTES))
+    os.makedirs(dirname, exist_ok=True)
+    for name, a in arrays.items():
+        assert a.dtype in (np.float32, np.float64), name
+        np.save(os.path.join(dirname, name + ".npy"), a)
 
 
 def cpu_baseline(scale, seed):
@@ -295,6 +356,8 @@ def spawn_ranks(args):
 
 def main():
     args = parse()
+    if args.dump_outputs and args.workload == "galerkin" and (args.gpus > 1 or args.dist_path):
+        raise SystemExit("--dump-outputs: the sharded Galerkin step leaves C's tuples spread over the ranks; dump it with --gpus 1")
     if args.gpus > 1 and "WORLD_SIZE" not in os.environ:
         spawn_ranks(args)
     # dmabuf IPC for RCCL: must be in the environment before the HIP runtime starts
@@ -337,7 +400,6 @@ def main():
         line = single_gpu(args, torch, capi, ctx, dev, stream)
         print(json.dumps(line), flush=True)
         ctx.close()
-        finish()
         return
 
     if args.rehearse_gloo:
@@ -359,7 +421,6 @@ def main():
         dd.close()
         ctx.close()
         dist.destroy_process_group()
-        finish()
         return
     if args.workload == "poisson":
         g = args.grid or 4096
@@ -465,6 +526,8 @@ def main():
     nnz_c, vsum, vhash = sd.reduce_digest(int(res.nnz), float(res.sum), int(res.hash), coll_dev)
 
     if rank == 0:
+        if args.dump_outputs:
+            write_dump(args.dump_outputs, digest_arrays(nnz_c, vsum, vhash))
         ms_step = elapsed / args.steps * 1e3
         line = headline(args, world, wname, n, ne, nnz_a, products, nnz_c, vsum, vhash, ms_step, elapsed,
                         [r[0] for r in results], remote_total, calib,
@@ -473,7 +536,6 @@ def main():
     dd.close()
     ctx.close()
     dist.destroy_process_group()
-    finish()
 
 
 def galerkin_sharded(args, torch, dist, capi, sd, ctx, dd, dev, coll_dev, rank, world, barrier):
@@ -651,6 +713,10 @@ def single_gpu(args, torch, capi, ctx, dev, stream):
     w = Workload(torch, capi, ctx, dev, args.workload, args.scale, args.grid, args.seed, args.sink, prepared=args.prepared)
     summary, results = run_workload(torch, w, args.steps, args.warmup)
     last = results[-1]
+    if args.dump_outputs:
+        # before anything else runs on ctx: a later COO multiply may reuse the buffers of the last step's result
+        c = last[-1]
+        write_dump(args.dump_outputs, digest_arrays(c.nnz, c.sum, c.hash) if w.sink == capi.SINK_DIGEST else coo_arrays(ctx, c))
     flat = [r for step in results for r in step] if w.kind == "galerkin" else [step[0] for step in results]
     nnz_a, products, nnz_c = sum(summary["nnz_a"]), sum(summary["products"]), summary["nnz_c"][-1]
     elapsed = summary["ms_per_step"] * 1e-3 * args.steps
@@ -717,18 +783,6 @@ def single_gpu(args, torch, capi, ctx, dev, stream):
     if not args.no_cpu_baseline and default_line:
         line["cpu_baseline"] = cpu_baseline(args.cpu_scale, args.seed)
     return line
-
-
-def finish():
-    """Leave nothing behind: flush, then end the process without the interpreter's slow teardown (hundreds of
-    idle OpenMP workers of the CPU baseline, the HIP runtime's unmapping of ~200 GB) so that no child or
-    lingering process outlives the bench line."""
-    sys.stdout.flush()
-    sys.stderr.flush()
-    tools = os.environ.get("LD_PRELOAD", "") + os.environ.get("ROCP_TOOL_LIBRARIES", "")
-    if "rocprof" in tools:
-        return                                    # a profiler writes its output from exit handlers: leave normally
-    os._exit(0)
 
 
 if __name__ == "__main__":
