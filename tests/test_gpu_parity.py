@@ -8,9 +8,12 @@ arrival order.
 """
 import os
 
+import functools
+
 import numpy as np
 import pytest
 
+import projection as pj
 from oracle import binding as orc
 from spsparse_amd import workloads as wl
 
@@ -1272,12 +1275,6 @@ def _device_operand(ctx, gen, n_tuples, shape, sort0=-1):
     return capi.device_coo(t[0].data_ptr(), t[1].data_ptr(), t[2].data_ptr(), n_tuples, shape, sort0), t
 
 
-def _row_sums_by_linearity(a, b, n_rows, n_inner):
-    """(A B) 1 = A (B 1): per-row sums of C from O(nnz) host arithmetic."""
-    b1 = np.bincount(b[0], weights=b[2], minlength=n_inner)
-    return np.bincount(a[0], weights=a[2] * b1[a[1]], minlength=n_rows)
-
-
 def test_cfg2_rmat20_full_size_properties(ctx):
     """BASELINE cfg2: R-MAT scale-20 A*A (P = 2.09e10, nnz(C) = 9.7e9) -- every row sum and the
     grand sum follow from linearity; nnz(C) is bounded by the products and reproducible."""
@@ -1287,7 +1284,7 @@ def test_cfg2_rmat20_full_size_properties(ctx):
     A, keep = _device_operand(ctx, lambda *p: ctx.gen_rmat(scale, seed, 0, ne, *p), ne, (n, n))
     d = ctx.multiply(A, A, sink=capi.SINK_DIGEST, flags=capi.SINK_ROWSTATS)
     a = wl.rmat(scale, seed)
-    want = _row_sums_by_linearity(a, a, n, n)
+    want = pj.row_sums_by_linearity(a, a, n, n)
     got = ctx.to_host(d.row_sum, n, np.float64)
     nz = want != 0
     assert np.array_equal(got != 0, nz)                  # values are positive: a row is empty iff its sum is 0
@@ -1320,7 +1317,7 @@ def test_rmat18_whole_product_against_the_oracle_digest(ctx, flags):
     A, keep = _device_operand(ctx, lambda *p: ctx.gen_rmat(scale, seed, 0, ne, *p), ne, (n, n))
     d = ctx.multiply(A, A, sink=capi.SINK_DIGEST, flags=capi.SINK_ROWSTATS | flags)
     a = wl.rmat(scale, seed)
-    w = orc.multiply_digest(orc.Mat(*a), orc.Mat(*a), nthreads=orc.host_threads(), rowstats=True)
+    w = _rmat18_oracle_digest(False)
     assert (d.nnz, d.hash, d.products, d.nnz_a) == (w.nnz, w.hash, w.products, w.nnz_a)
     assert np.array_equal(ctx.to_host(d.row_nnz, n, np.int64), w.row_nnz)
     assert np.array_equal(ctx.to_host(d.row_hash, n, np.uint64), w.row_hash)
@@ -1334,6 +1331,74 @@ def test_rmat18_whole_product_against_the_oracle_digest(ctx, flags):
         cj = ctx.to_host(r.idx1, int(r.nnz), np.int32)
         with np.errstate(over="ignore"):
             assert int(np.sum(orc.mix64(ci, cj), dtype=np.uint64)) == w.hash
+        del ci, cj
+        # ... and whole, on the device: strict (i, j) order, row projections with 1 and x and the column projection with
+        # y inside their linearity bounds (tests/projection.py)
+        x, y = pj.weights(n, 1), pj.weights(n, 2)
+        s = pj.reduce_coo(pj.device_source(ctx, r, 1 << 27), int(r.nnz), (n, n), w=x, u=y, device="cuda:0")
+        assert pj.failures(s, pj.Reference(a, a), x, y, want=(w.nnz, w.row_nnz, w.hash)) == []
+    del keep
+
+
+@functools.lru_cache(maxsize=None)
+def _rmat18_oracle_digest(signed):
+    """The oracle's streaming digest (row statistics included) of R-MAT scale-18 A*A, seed 1; signed: A's values signed
+    by a hash of (i, j) (projection.sign_of), duplicates alike."""
+    a = _rmat18_host(signed)
+    return orc.multiply_digest(orc.Mat(*a), orc.Mat(*a), nthreads=orc.host_threads(), rowstats=True)
+
+
+def _rmat18_host(signed):
+    i, j, v, shape = wl.rmat(18, 1)
+    return i, j, v * pj.sign_of(i, j) if signed else v, shape
+
+
+@pytest.mark.parametrize("signed", [False, True], ids=["positive", "signed"])
+@pytest.mark.parametrize("knobs", [{}, {"direct_min": 1024}, {"no_tiles": 1}],
+                         ids=lambda k: ",".join("%s=%d" % kv for kv in k.items()) or "default")
+def test_rmat18_coo_whole_in_each_scheme(ctx, knobs, signed):
+    """R-MAT scale-18 A*A (1.28e9 tuples) through the COO sink, whole, under the default cell schemes and two forced
+    ones: the direct tiles (k_direct_tiles, never checked above scale 15 before) and no tiles at all.  Strict order; the
+    row projections with 1 and x and the column projection with y inside their linearity bounds; positive values: the
+    index set equals the oracle's digest.  Signed values (a hash of (i, j)): in SINK_EXACT_PATTERN the index set equals
+    the signed oracle's digest, and in the default order (where cancellation may leave a rounding residue instead of a
+    dropped zero) the projections stay inside the signed bound.  The weights are applied after the multiply: these
+    are the plain emit branch's values."""
+    import torch
+    from spsparse_amd import capi
+    scale, seed = 18, 1
+    n, ne = 1 << scale, 16 << scale
+    A, keep = _device_operand(ctx, lambda *p: ctx.gen_rmat(scale, seed, 0, ne, *p), ne, (n, n))
+    if signed:
+        i64, j64 = keep[0].long(), keep[1].long()
+        keep[2].mul_(1.0 - 2.0 * ((pj.mix64_t(i64, j64) >> 40) & 1).double())
+        del i64, j64
+        torch.cuda.synchronize()
+    a = _rmat18_host(signed)
+    assert np.array_equal(keep[2].cpu().numpy(), a[2])
+    o = _rmat18_oracle_digest(signed)
+    ref = pj.Reference(a, a)
+    x, y = pj.weights(n, 1), pj.weights(n, 2)
+    for k, v in knobs.items():
+        ctx.set_tuning(k, v)
+    try:
+        r = ctx.multiply(A, A, sink=capi.SINK_COO)
+        if "direct_min" in knobs:
+            assert r.products_direct > 0
+        if knobs.get("no_tiles"):
+            assert r.products_tiles == 0
+        s = pj.reduce_coo(pj.device_source(ctx, r, 1 << 27), int(r.nnz), (n, n), w=x, u=y, device="cuda:0")
+        assert pj.failures(s, ref, x, y, want=None if signed else (o.nnz, o.row_nnz, o.hash)) == []
+        assert signed or s.vmin > 0
+        for name, got, proj in (("rows x", s.row_w, ref.rows(x)), ("cols y", s.col_u, ref.cols(y))):
+            print("%s: largest error/bound %.3g" % (name, pj.within(got, *proj)[1]))
+        if signed:
+            r = ctx.multiply(A, A, sink=capi.SINK_COO, flags=capi.SINK_EXACT_PATTERN)
+            s = pj.reduce_coo(pj.device_source(ctx, r, 1 << 27), int(r.nnz), (n, n), w=x, u=y, device="cuda:0")
+            assert pj.failures(s, ref, x, y, want=(o.nnz, o.row_nnz, o.hash)) == []
+    finally:
+        for k in knobs:
+            ctx.set_tuning(k, 0)
     del keep
 
 
