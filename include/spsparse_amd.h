@@ -32,6 +32,11 @@
  *     row and window: 1.4 GB for a 2^20-square matrix, 43 GB at 2^23).  Where they would not fit the device the
  *     product also goes by column blocks, narrow enough for them to fit; SPSAMD_ENOMEM only if one window's
  *     share does not.
+ *
+ * Applying a matrix to dense vectors
+ *   spsamd_multiply_dense is the reference's multiply(M, x, y, handle_nan, transpose) (multiply_dense.hpp:11-35, compiled
+ *   out there) into a DenseAccum (accum.hpp:110-140), for nrhs right-hand sides at once.  Every entry of Y is
+ *   bit-identical to the reference's loop over M's tuples in storage order (duplicates and explicit zeros included).
  */
 #ifndef SPSPARSE_AMD_H
 #define SPSPARSE_AMD_H
@@ -187,6 +192,9 @@ const char *spsamd_version(void);
  *   trace           1                 the symbolic phase prints its choices (tile scheme, cell counts) to stderr
  *   index_budget_mb > 0               cap of the heavy rows' window indices (default: 80 % of the free device memory);
  *                                     beyond it the product goes by column blocks of op(B)
+ *   spmm_path       1 | 2 | 3         multiply_dense: every row through the serial (thread per row and rhs) | lanes (wave per
+ *                                     row, lanes across rhs) | fold (wave per row, ordered fold) kernel (default: by row length)
+ *   spmm_long_min   > 0               multiply_dense: rows of more tuples than this go to a wave kernel (64)
  * The environment variables of the same purpose (SPSAMD_W ...) are read once, inside spsamd_ctx_create; nothing reads
  * the environment later.  Unknown names: SPSAMD_EINVAL. */
 int spsamd_ctx_set_tuning(spsamd_ctx *ctx, const char *name, long value);
@@ -251,6 +259,32 @@ int spsamd_result_fetch(spsamd_ctx *ctx, const spsamd_result *result,
  */
 int spsamd_result_scatter_dense(spsamd_ctx *ctx, const spsamd_result *result, double *dense_device, size_t ld,
 	int duplicate_policy);
+
+/*
+ * Y (op)= op(M) * X  -- multiply_dense.hpp:11-35 (compiled out in the reference), y a DenseAccum (accum.hpp:110-140),
+ * nrhs right-hand sides at once.  For each right-hand side r, over M's tuples (i, j, v) IN STORAGE ORDER ((j, i) with 'T'):
+ *     p = v * X[j*ldx + r];   if (handle_nan && (isnan(p) || isinf(p))) skip;
+ *     Y[i*ldy + r]:  ADD  Y += p   |   REPLACE  Y = p   |   LEAVE_ALONE  if (!isnan(Y)) Y = p   (accum.hpp:124-135)
+ * Every entry of Y is bit-identical to that loop: the adds into one entry run in storage order, products and sums are
+ * rounded separately (no FMA), and a NaN result has the bits x86-64 gives it (the left operand's NaN, quieted, else the
+ * right one's, else 0xFFF8000000000000).  Y is never zeroed: an entry that receives no product keeps its value.  M is NOT
+ * consolidated -- duplicates and explicit zeros each contribute (0 * Inf = NaN) -- except a prepared operand
+ * (SPSAMD_MEM_PREPARED), which is taken as its consolidated tuples the way Consolidate<> takes a sorted array: preparing
+ * merges duplicates and drops zeros, and so can change Y.
+ *   X      cols(op(M)) rows of nrhs values, row-major: X[j*ldx + r]
+ *   Y      rows(op(M)) rows, Y[i*ldy + r], read and written (the ldy - nrhs values after each row's are not touched)
+ *   mem    SPSAMD_MEM_HOST or SPSAMD_MEM_DEVICE, for X and Y together (M has its own `mem`)
+ * SPSAMD_EINVAL: M NULL, X or Y NULL while nrhs > 0 and M has a non-empty dimension, ldx or ldy < nrhs, a policy outside
+ * 0..2, a bad mem, an index of M out of bounds, X and Y overlapping.  nrhs == 0 or an empty M: 0, Y untouched.
+ * Returns when Y holds the result.  The workspace comes from the context's arena; neither output buffer is written, so a
+ * SINK_COO result stays valid and fetchable across the call and can itself be M.
+ */
+int spsamd_multiply_dense(spsamd_ctx *ctx,
+	const spsamd_coo *M, char transpose,
+	const double *X, size_t ldx,
+	double *Y, size_t ldy,
+	size_t nrhs, int mem,
+	int duplicate_policy, int handle_nan);
 
 /* Copy `bytes` between host and/or device memory of this context's device
  * (e.g. result->row_nnz to the host, result->idx0 into a caller's device

@@ -461,6 +461,22 @@ int add_chunk_v(void *user, const int32_t *i, const int32_t *, const double *v, 
 	return 0;
 }
 
+// ---- multiply(M, x, y, handle_nan, transpose) (multiply_dense.hpp:11-35, compiled out in the reference) -------
+// y (op)= op(M) * x for host vectors x (cols(op(M)) entries) and y (rows(op(M)) entries, read and written) through
+// spsamd_multiply_dense: every y[i] bit-identical to the reference's loop over M's tuples in storage order, y a
+// DenseAccum with duplicate_policy (accum.hpp:124-135).  transpose = true is the reference's 'T'.
+template <class MatT>
+void multiply_dense(MatT const &M, const double *x, double *y, bool handle_nan = false, bool transpose = false,
+	DuplicatePolicy duplicate_policy = DuplicatePolicy::ADD)
+{
+	spsamd_coo m = detail::as_coo(M);
+	spsamd_ctx *ctx = default_context().get();
+	if (!ctx) return;
+	int rc = spsamd_multiply_dense(ctx, &m, transpose ? 'T' : '.', x, 1, y, 1, 1, SPSAMD_MEM_HOST, (int)duplicate_policy,
+		handle_nan ? 1 : 0);
+	if (rc != 0) (*spsparse_error)(-1, "%s", spsamd_last_error(ctx));
+}
+
 // ---- VectorCooArray::consolidate on the device ---------------------------
 template <class IndexT, class ValT, int RANK>
 void VectorCooArray<IndexT, ValT, RANK>::consolidate(std::array<int, RANK> const &_sort_order,

@@ -76,7 +76,8 @@ SYMBOLS = ["spsamd_ctx_create", "spsamd_ctx_destroy", "spsamd_last_error", "spsa
            "spsamd_dim_beginnings", "spsamd_gen_rmat",
            "spsamd_gen_random_rows", "spsamd_gen_poisson2d", "spsamd_gen_laplace3d", "spsamd_gen_aggregation3d",
            "spsamd_dist_unique_id", "spsamd_dist_create", "spsamd_dist_destroy", "spsamd_dist_multiply",
-           "spsamd_operand_prepare", "spsamd_operand_as_coo", "spsamd_operand_bytes", "spsamd_operand_destroy"]
+           "spsamd_operand_prepare", "spsamd_operand_as_coo", "spsamd_operand_bytes", "spsamd_operand_destroy",
+           "spsamd_multiply_dense"]
 
 _lib = None
 
@@ -114,6 +115,8 @@ def load():
                                      C.c_int, C.c_int, C.c_int, C.c_int, P(Result)]
     L.spsamd_result_fetch.argtypes = [C.c_void_p, P(Result), CHUNK_FN, C.c_void_p]
     L.spsamd_result_scatter_dense.argtypes = [C.c_void_p, P(Result), C.c_void_p, C.c_size_t, C.c_int]
+    L.spsamd_multiply_dense.argtypes = [C.c_void_p, P(Coo), C.c_char, C.c_void_p, C.c_size_t, C.c_void_p, C.c_size_t,
+                                        C.c_size_t, C.c_int, C.c_int, C.c_int]
     L.spsamd_memcpy.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_size_t]
     L.spsamd_consolidate.argtypes = [C.c_void_p, P(Coo), C.c_int, C.c_int, C.c_int, P(Result)]
     L.spsamd_sorted_permutation.argtypes = [C.c_void_p, P(Coo), C.c_int, C.c_void_p]
@@ -259,6 +262,23 @@ class Context:
         """DenseAccum on the device: dense[i*ld + j] (+)= v for the tuples of a SINK_COO result."""
         self._check(self.L.spsamd_result_scatter_dense(self.h, C.byref(res), dense_ptr, ld, duplicate_policy))
 
+    def multiply_dense(self, M, X, Y, transpose='.', duplicate_policy=ADD, handle_nan=False):
+        """spsamd_multiply_dense: Y (op)= op(M) @ X, bit-identical to the reference's loop over M's tuples in storage
+        order (multiply_dense.hpp:11-35, Y a DenseAccum).  M: a Coo struct.  X, Y: 2-D float64 numpy arrays (host) or
+        float64 torch tensors on this context's device, rows contiguous (stride 1 along the right-hand sides); a 1-D
+        X / Y is one right-hand side.  Y is updated in place."""
+        (px, ldx, nx, mx), (py, ldy, ny, my) = _dense_arg(X, "X", writable=False), _dense_arg(Y, "Y", writable=True)
+        if mx != my:
+            raise ValueError("X and Y must both be host (numpy) or both device (torch) arrays")
+        if nx != ny:
+            raise ValueError("X has %d right-hand sides, Y %d" % (nx, ny))
+        nrow, ncol = (M.shape1, M.shape0) if transpose == 'T' else (M.shape0, M.shape1)
+        if _rows(X) != ncol or _rows(Y) != nrow:
+            raise ValueError("X needs %d rows and Y %d rows for op(M) of shape (%d, %d)" % (ncol, nrow, nrow, ncol))
+        self._check(self.L.spsamd_multiply_dense(self.h, C.byref(M), transpose.encode(), px, ldx, py, ldy, nx, mx,
+                                                 duplicate_policy, int(handle_nan)))
+        return Y
+
     def to_host(self, dev_ptr, count, dtype):
         """numpy copy of `count` elements of device memory (spsamd_memcpy)."""
         out = np.empty(count, dtype=dtype)
@@ -283,6 +303,47 @@ class Context:
 
     def gen_aggregation3d(self, N, p0, p1, pv):
         self._check(self.L.spsamd_gen_aggregation3d(self.h, N, p0, p1, pv))
+
+
+def _rows(A):
+    return int(A.shape[0])
+
+
+def _dense_arg(A, name, writable):
+    """(pointer, leading dimension, right-hand sides, mem) of a dense X / Y argument."""
+    if isinstance(A, np.ndarray):
+        if A.dtype != np.float64:
+            raise TypeError("%s must be float64" % name)
+        if writable and not A.flags.writeable:
+            raise ValueError("%s is read-only" % name)
+        mem, item, strides = MEM_HOST, A.itemsize, A.strides
+    else:
+        import torch
+        if not isinstance(A, torch.Tensor):
+            raise TypeError("%s must be a numpy array or a torch tensor" % name)
+        if A.dtype != torch.float64:
+            raise TypeError("%s must be float64" % name)
+        if A.device.type != "cuda":
+            raise ValueError("%s must be a device tensor (or a numpy array for host memory)" % name)
+        mem, item, strides = MEM_DEVICE, 8, tuple(s * 8 for s in A.stride())
+    if A.ndim == 1:
+        nrhs, ld = 1, strides[0] // item
+        if strides[0] % item or (A.shape[0] > 1 and ld < 1):
+            raise ValueError("%s: unsupported stride" % name)
+        ld = max(ld, 1)
+    elif A.ndim == 2:
+        nrhs = int(A.shape[1])
+        if nrhs > 1 and strides[1] != item:
+            raise ValueError("%s must have contiguous rows (stride 1 along the right-hand sides)" % name)
+        if strides[0] % item:
+            raise ValueError("%s: unsupported row stride" % name)
+        ld = strides[0] // item if A.shape[0] > 1 else nrhs
+        if ld < nrhs:
+            raise ValueError("%s: rows overlap" % name)
+    else:
+        raise ValueError("%s must be 1-D or 2-D" % name)
+    ptr = A.ctypes.data if mem == MEM_HOST else A.data_ptr()
+    return ptr, ld, nrhs, mem
 
 
 class Operand:

@@ -48,8 +48,8 @@ extern "C" int spsamd_ctx_create(spsamd_ctx **out, int device, void *hip_stream)
 	if (hipStreamCreateWithFlags(&c->side2, hipStreamNonBlocking) != hipSuccess) { spsamd_ctx_destroy(c); return SPSAMD_EHIP; }
 	for (auto &e : c->ev_side2) if (hipEventCreateWithFlags(&e, hipEventDisableTiming) != hipSuccess) { spsamd_ctx_destroy(c); return SPSAMD_EHIP; }
 	// developer knobs: the environment is consulted here and nowhere else
-	static const char *const knobs[] = {"window", "cell_cap", "dense_min", "no_tiles", "xcd", "emit_path", "light_path", "no_wmajor", "direct_min", "tiles_v1", "long_cap", "long_dense_min", "index_budget_mb", "trace", "light_two_pass"};
-	static const char *const envs[] = {"SPSAMD_W", "SPSAMD_CELL_CAP", "SPSAMD_DENSE_MIN", "SPSAMD_NO_TILES", "SPSAMD_XCD", "SPSAMD_EMIT_PATH", "SPSAMD_LIGHT_PATH", "SPSAMD_NO_WMAJOR", "SPSAMD_DIRECT_MIN", "SPSAMD_TILES_V1", "SPSAMD_LONG_CAP", "SPSAMD_LONG_DENSE_MIN", "SPSAMD_INDEX_BUDGET_MB", "SPSAMD_TRACE", "SPSAMD_LIGHT_TWO_PASS"};
+	static const char *const knobs[] = {"window", "cell_cap", "dense_min", "no_tiles", "xcd", "emit_path", "light_path", "no_wmajor", "direct_min", "tiles_v1", "long_cap", "long_dense_min", "index_budget_mb", "trace", "light_two_pass", "spmm_path", "spmm_long_min"};
+	static const char *const envs[] = {"SPSAMD_W", "SPSAMD_CELL_CAP", "SPSAMD_DENSE_MIN", "SPSAMD_NO_TILES", "SPSAMD_XCD", "SPSAMD_EMIT_PATH", "SPSAMD_LIGHT_PATH", "SPSAMD_NO_WMAJOR", "SPSAMD_DIRECT_MIN", "SPSAMD_TILES_V1", "SPSAMD_LONG_CAP", "SPSAMD_LONG_DENSE_MIN", "SPSAMD_INDEX_BUDGET_MB", "SPSAMD_TRACE", "SPSAMD_LIGHT_TWO_PASS", "SPSAMD_SPMM_PATH", "SPSAMD_SPMM_LONG_MIN"};
 	static_assert(sizeof knobs / sizeof knobs[0] == sizeof envs / sizeof envs[0], "one environment variable per knob");
 	for (size_t k = 0; k < sizeof knobs / sizeof knobs[0]; ++k)
 		if (const char *e = getenv(envs[k])) (void)spsamd_ctx_set_tuning(c, knobs[k], atol(e));
@@ -67,6 +67,7 @@ extern "C" int spsamd_ctx_set_tuning(spsamd_ctx *c, const char *name, long value
 		{"window", &c->tune.window}, {"cell_cap", &c->tune.cell_cap}, {"dense_min", &c->tune.dense_min},
 		{"no_tiles", &c->tune.no_tiles}, {"xcd", &c->tune.xcd}, {"emit_path", &c->tune.emit_path},
 		{"light_path", &c->tune.light_path}, {"no_wmajor", &c->tune.no_wmajor}, {"direct_min", &c->tune.direct_min}, {"tiles_v1", &c->tune.tiles_v1}, {"long_cap", &c->tune.long_cap}, {"long_dense_min", &c->tune.long_dense_min}, {"index_budget_mb", &c->tune.index_budget_mb}, {"trace", &c->tune.trace}, {"light_two_pass", &c->tune.light_two_pass},
+		{"spmm_path", &c->tune.spmm_path}, {"spmm_long_min", &c->tune.spmm_long_min},
 	};
 	for (auto &t : tab) if (!std::strcmp(t.n, name)) { *t.p = (int)value; return SPSAMD_OK; }
 	c->last_error = std::string("unknown tuning knob: ") + name;
@@ -413,6 +414,51 @@ extern "C" int spsamd_result_scatter_dense(spsamd_ctx *c, const spsamd_result *r
 		unsigned grid = (unsigned)std::min<uint64_t>((res->nnz + 255) / 256, 8192);
 		k_scatter_dense<<<dim3(grid), dim3(256), 0, c->stream>>>(res->idx0, res->idx1, res->val, res->nnz, dense, ld, policy);
 		SPS_LAUNCH_CHECK();
+		SPS_HIP(hipStreamSynchronize(c->stream));
+		return SPSAMD_OK;
+	)
+}
+
+// Y (op)= op(M) * X (multiply_dense.hpp:11-35; y a DenseAccum, accum.hpp:110-140).  Workspace only: neither output set of
+// the context is written, so a SINK_COO result stays fetchable and may itself be M.
+extern "C" int spsamd_multiply_dense(spsamd_ctx *c, const spsamd_coo *M, char transpose, const double *X, size_t ldx,
+	double *Y, size_t ldy, size_t nrhs, int mem, int policy, int handle_nan)
+{
+	if (!c) return SPSAMD_EINVAL;
+	API_GUARD(c,
+		if (!M) throw Error{SPSAMD_EINVAL, "null matrix"};
+		const int lead = transpose == 'T' ? 1 : 0;
+		const uint64_t shape[2] = {M->shape0, M->shape1};
+		const uint64_t nrow = shape[lead], ncol = shape[1 - lead];      // rows(op(M)) = rows of Y, cols(op(M)) = rows of X
+		if (nrhs && (nrow || ncol) && (!X || !Y)) throw Error{SPSAMD_EINVAL, "null X or Y"};
+		if (ldx < nrhs || ldy < nrhs) throw Error{SPSAMD_EINVAL, "leading dimension of X or Y smaller than nrhs"};
+		if (policy < 0 || policy > 2) throw Error{SPSAMD_EINVAL, "bad duplicate_policy"};
+		if (mem != SPSAMD_MEM_HOST && mem != SPSAMD_MEM_DEVICE) throw Error{SPSAMD_EINVAL, "mem of X and Y must be SPSAMD_MEM_HOST or SPSAMD_MEM_DEVICE"};
+		if (nrhs > 0xFFFFFFFFull) throw Error{SPSAMD_EINVAL, "nrhs exceeds 2^32 - 1"};
+		// the bytes each array spans: rows - 1 full leading dimensions and nrhs values
+		const uint64_t xbytes = ncol && nrhs ? ((ncol - 1) * ldx + nrhs) * sizeof(double) : 0;
+		const uint64_t ybytes = nrow && nrhs ? ((nrow - 1) * ldy + nrhs) * sizeof(double) : 0;
+		if (xbytes && ybytes && (const char *)X < (const char *)Y + ybytes && (const char *)Y < (const char *)X + xbytes)
+			throw Error{SPSAMD_EINVAL, "X and Y overlap"};
+		const bool empty = M->mem == SPSAMD_MEM_PREPARED ? !M->idx0 || ((const spsamd_operand *)M->idx0)->p.m.nnz == 0 : M->nnz == 0;
+		if (!nrhs || empty) return SPSAMD_OK;
+		SPS_HIP(hipSetDevice(c->device));
+		c->arena.reset();
+		DenseOperand m;
+		dense_operand(c, M, lead, &m);
+		if (!m.nnz) return SPSAMD_OK;
+		const double *dX = X;
+		double *dY = Y;
+		uint64_t dldx = ldx, dldy = ldy;
+		if (mem == SPSAMD_MEM_HOST) {                                  // packed device copies, nrhs values per row
+			double *tx = c->arena.get<double>(ncol * nrhs), *ty = c->arena.get<double>(nrow * nrhs);
+			SPS_HIP(hipMemcpy2DAsync(tx, nrhs * sizeof(double), X, ldx * sizeof(double), nrhs * sizeof(double), ncol, hipMemcpyHostToDevice, c->stream));
+			SPS_HIP(hipMemcpy2DAsync(ty, nrhs * sizeof(double), Y, ldy * sizeof(double), nrhs * sizeof(double), nrow, hipMemcpyHostToDevice, c->stream));
+			dX = tx; dY = ty; dldx = dldy = nrhs;
+		}
+		spmm_dense(c, m, dX, dldx, dY, dldy, (uint32_t)nrhs, policy, handle_nan != 0);
+		if (mem == SPSAMD_MEM_HOST)
+			SPS_HIP(hipMemcpy2DAsync(Y, ldy * sizeof(double), dY, nrhs * sizeof(double), nrhs * sizeof(double), nrow, hipMemcpyDeviceToHost, c->stream));
 		SPS_HIP(hipStreamSynchronize(c->stream));
 		return SPSAMD_OK;
 	)

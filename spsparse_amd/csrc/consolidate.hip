@@ -172,6 +172,18 @@ __global__ void k_min_key(unsigned long long *first_key, const unsigned long lon
 	if (*global_key < *first_key) *first_key = *global_key;
 }
 
+uint32_t inspect_operand(spsamd_ctx *c, const int32_t *major, const int32_t *minor, const double *val, size_t n,
+	uint64_t nrow, uint64_t ncol)
+{
+	uint32_t *flags = c->arena.get<uint32_t>(1);
+	fill_zero(c, flags, sizeof(uint32_t));
+	if (n) {
+		k_inspect<<<dim3(std::min(grid_for(n, 1024), 2048u)), dim3(256), 0, c->stream>>>(major, minor, val, n, nrow, ncol, 0, flags);
+		SPS_LAUNCH_CHECK();
+	}
+	return read_back(c, flags);
+}
+
 void consolidate_operand(spsamd_ctx *c, const spsamd_coo *X, int lead, int ref_lead, int duplicate_policy, int zero_nan, ConMat *out,
 	Prepared **prep, const unsigned long long *global_first_key)
 {

@@ -90,6 +90,8 @@ struct Tuning {
 	int direct_min = 0;          // 0: default; products above which one window of a tile row becomes a direct cell (>= dense_min: never)
 	int trace = 0;               // 1: the symbolic phase prints its choices to stderr
 	int index_budget_mb = 0;     // 0: 80 % of the free device memory; cap (MB) of the heavy rows' window indices, beyond which the product goes by column blocks
+	int spmm_path = 0;           // multiply_dense: 0 auto | 1 serial kernel for every row | 2 lanes kernel for every row | 3 fold kernel for every row
+	int spmm_long_min = 0;       // multiply_dense, auto: rows of more tuples than this go to a wave kernel (0: 64)
 #ifdef SPSAMD_ABLATIONS
 	int dbg = 0;
 #endif
@@ -198,6 +200,11 @@ void consolidate_operand(spsamd_ctx *c, const spsamd_coo *X, int lead, int ref_l
 // -> *out_dev (all ones: none).  Same key as consolidate_operand's own first-kept search.
 void first_kept_key_raw(spsamd_ctx *c, const spsamd_coo *Xdev, int lead, int ref_lead, unsigned long long *out_dev);
 
+// Inspection flags of tuples (major, minor, val) on the device (k_inspect): bit0 an index out of [0, nrow) x [0, ncol),
+// bit4 the major index descends somewhere; the other bits are consolidate_operand's own.
+uint32_t inspect_operand(spsamd_ctx *c, const int32_t *major, const int32_t *minor, const double *val, size_t n,
+	uint64_t nrow, uint64_t ncol);
+
 // Row boundaries of a consolidated operand: dim_beginnings (algorithm.hpp:74-118):
 // beg[r] for each non-empty row + sentinel, and the row ids.
 struct RowList {
@@ -277,6 +284,7 @@ struct MultiplyArgs {
 };
 void spgemm(spsamd_ctx *c, MultiplyArgs &a, spsamd_result *res);
 void prepared_row_structure(spsamd_ctx *c, Prepared *p);      // its dense row pointer and longest row, now (spgemm.hip)
+BTup *prepared_btup(spsamd_ctx *c, Prepared *p);               // its packed (col, val) tuples, built on first use (spgemm.hip)
 
 // Shared body of the MM and MV entry points (capi.hip); `arena_ready`: the caller has reset the workspace
 // and may hold operands in it (the distributed step does); `parts`: records of derived structures the caller already
@@ -287,6 +295,23 @@ int multiply_body(spsamd_ctx *c, double C,
 	const spsamd_vec *scalej, const spsamd_coo *B, char transpose_B,
 	const spsamd_vec *scalek, int duplicate_policy, int zero_nan,
 	int sink_kind, int sink_flags, spsamd_result *res, const char *what, bool arena_ready, const OperandParts *parts = nullptr);
+
+// ---------------------------------------------------------------- dense right-hand sides (k_spmm.hip)
+
+// op(M)'s tuples in order of the output row (storage order inside a row) with a dense row pointer: workspace memory, or
+// the pieces of a prepared operand of the same transpose
+struct DenseOperand {
+	const uint32_t *rowptr = nullptr;   // nrow + 1 entries (at least)
+	const BTup *tup = nullptr;
+	uint64_t nrow = 0, ncol = 0;        // rows(op(M)), cols(op(M))
+	uint32_t nnz = 0;
+	bool sorted = false;                // the stable sort ran (the storage order was not row order)
+};
+// Checks the indices (SPSAMD_EINVAL) and orders the tuples; lead = 1 for 'T'.
+void dense_operand(spsamd_ctx *c, const spsamd_coo *M, int lead, DenseOperand *out);
+// Y[i * ldy + r] (op)= op(M)(i, j) * X[j * ldx + r] in storage order, X and Y device memory
+void spmm_dense(spsamd_ctx *c, const DenseOperand &m, const double *X, uint64_t ldx, double *Y, uint64_t ldy, uint32_t nrhs,
+	int policy, bool handle_nan);
 
 // Select the output set the next result is written to: the current one unless a device operand lives in it.
 void pick_output_set(spsamd_ctx *c, const spsamd_coo *const *operands, int n);

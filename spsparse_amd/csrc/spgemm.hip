@@ -497,6 +497,13 @@ static BTup *ensure_btup(spsamd_ctx *c, MultiplyArgs &a, Prepared *p)
 	return p->btup;
 }
 
+BTup *prepared_btup(spsamd_ctx *c, Prepared *p)
+{
+	MultiplyArgs a;
+	a.b_ready = nullptr;
+	return ensure_btup(c, a, p);
+}
+
 static void spgemm_once(spsamd_ctx *c, MultiplyArgs &a, spsamd_result *res)
 {
 	hipStream_t st = c->stream;
