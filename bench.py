@@ -1,22 +1,30 @@
 #!/usr/bin/env python3
 """bench.py -- nnz(C)/s of C = A*A on BASELINE.json's cfg2 (R-MAT scale-20, fp64,
 ~16M tuples) on N MI355X GPUs of one node, plus the dominant kernel's roofline
-line and (N=1) the CPU port of the reference algorithm beside it.
+line; with --full (N=1) also the other configs and the CPU port of the
+reference algorithm beside it.
 
     python bench.py --gpus 1 --steps K --warmup W
+    python bench.py --gpus 1 --steps K --warmup W --full      (the headline, then the other configs and the CPU baseline)
     python bench.py --workload poisson|galerkin|rmat [--scale S] [--grid G]     (one other config as the headline)
     python bench.py ... --dump-outputs DIR      (the last timed step's result as DIR/<name>.npy, for comparing builds)
     python -m torch.distributed.run --nnodes=1 --nproc-per-node N --master-addr 127.0.0.1 \
         --master-port P bench.py --gpus N --steps K --warmup W
 
+A plain run does only what the headline needs: set up, warm up, time the
+steps, dump if asked, print the line.  The roofline line comes from the timed
+steps' own kernel timers, so it stays in a plain run.
+
 One step = one pass of the hot path over the whole synthetic matrix:
   N = 1   spsamd_multiply(A, A) from the raw, device-resident COO tuples
           (device consolidate + symbolic + numeric) into the digest sink.
-          The JSON line's `other_configs` object carries, measured in the same
-          run (fewer steps each): cfg3 (Poisson 4096^2, digest and COO sinks),
-          cfg5 (Galerkin R*A*R^T on 256^3, two chained COO multiplies), cfg4 on
-          one GPU (R-MAT scale-23) and cfg2 into the COO sink with the
-          PCIe-inclusive host delivery rate.  --no-other-configs skips them.
+          With --full the JSON line's `other_configs` object carries, measured
+          in the same run after the headline (fewer steps each): cfg3 (Poisson
+          4096^2, digest and COO sinks), cfg5 (Galerkin R*A*R^T on 256^3, two
+          chained COO multiplies), cfg4 on one GPU (R-MAT scale-23), cfg2 into
+          the COO sink, the prepared-operand variants and the PCIe-inclusive
+          host delivery rate; `cpu_baseline` carries the CPU port.
+          --no-other-configs and --no-cpu-baseline drop either from --full.
   N > 1   strong scaling on the same matrix: every rank owns a contiguous row
           block of the raw tuples; a step = spsamd_dist_multiply (C ABI):
           consolidate the own block, exchange the needed B row panels with
@@ -61,8 +69,11 @@ def parse():
     ap.add_argument("--prepared", action="store_true",
                     help="N=1: the operands are prepared once before the timed steps (spsamd_operand_prepare); not the headline, "
                          "which starts from the raw tuples every step")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
-    ap.add_argument("--no-other-configs", action="store_true", help="N=1: only the headline workload")
+    ap.add_argument("--full", action="store_true",
+                    help="N=1, default workload: after the headline also measure the other configs and the CPU baseline "
+                         "(off: the run does only what the headline needs)")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="with --full: skip the CPU baseline")
+    ap.add_argument("--no-other-configs", action="store_true", help="with --full: skip the other configs")
     ap.add_argument("--cpu-scale", type=int, default=15, help="R-MAT scale of the bounded CPU sample (scale 15: ~25 s on one core)")
     ap.add_argument("--calibrate", type=int, default=3,
                     help="N>1 setup: measure/rebalance rounds of the row-block boundaries (0: cost estimate only)")
@@ -709,7 +720,8 @@ def headline(args, world, wname, n, ne, nnz_a, products, nnz_c, vsum, vhash, ms_
 
 
 def single_gpu(args, torch, capi, ctx, dev, stream):
-    """N = 1: the headline workload, then (default run only) the other configs in the same process."""
+    """N = 1: the headline workload, then (--full on the default workload only) the other configs and the CPU baseline
+    in the same process."""
     w = Workload(torch, capi, ctx, dev, args.workload, args.scale, args.grid, args.seed, args.sink, prepared=args.prepared)
     summary, results = run_workload(torch, w, args.steps, args.warmup)
     last = results[-1]
@@ -739,7 +751,7 @@ def single_gpu(args, torch, capi, ctx, dev, stream):
     w.release()
     ctx.close()                                   # the headline's workspace goes back before the other configs run
     default_line = args.workload == "rmat" and args.scale == 20 and args.sink == "digest" and not args.prepared
-    if default_line and not args.no_other_configs:
+    if args.full and default_line and not args.no_other_configs:
         others = {}
 
         def other(key, kind, steps, warmup, **kw):
@@ -780,7 +792,7 @@ def single_gpu(args, torch, capi, ctx, dev, stream):
         if "ms_per_step" in coo:
             line["config"]["coo_sink_ms_per_step"] = coo["ms_per_step"]
             line["config"]["coo_sink_nnz_c_per_s"] = coo["nnz_c_per_s"]
-    if not args.no_cpu_baseline and default_line:
+    if args.full and default_line and not args.no_cpu_baseline:
         line["cpu_baseline"] = cpu_baseline(args.cpu_scale, args.seed)
     return line
 
