@@ -195,6 +195,8 @@ const char *spsamd_version(void);
  *   spmm_path       1 | 2 | 3         multiply_dense: every row through the serial (thread per row and rhs) | lanes (wave per
  *                                     row, lanes across rhs) | fold (wave per row, ordered fold) kernel (default: by row length)
  *   spmm_long_min   > 0               multiply_dense: rows of more tuples than this go to a wave kernel (64)
+ *   add_path        1                 add: sort every operand, ignoring sort0, chained results and preparation (default:
+ *                                     an operand already in op()'s row-major order is read in place)
  * The environment variables of the same purpose (SPSAMD_W ...) are read once, inside spsamd_ctx_create; nothing reads
  * the environment later.  Unknown names: SPSAMD_EINVAL. */
 int spsamd_ctx_set_tuning(spsamd_ctx *ctx, const char *name, long value);
@@ -285,6 +287,37 @@ int spsamd_multiply_dense(spsamd_ctx *ctx,
 	double *Y, size_t ldy,
 	size_t nrhs, int mem,
 	int duplicate_policy, int handle_nan);
+
+/*
+ * ret = alpha * op(A) + beta * op(B)  -- sparse addition (rocSPARSE / cuSPARSE csrgeam).  The result is exactly what
+ *     VectorCooArray T;
+ *     for (i, j, v) in op(A), in storage order:  T.add({i, j}, alpha * v);
+ *     for (i, j, v) in op(B), in storage order:  T.add({i, j}, beta * v);
+ *     consolidate(ret, T, {0, 1}, duplicate_policy, zero_nan);          (algorithm.hpp:251-319)
+ * produces, bit for bit, NaN payloads included:
+ *   - op(X) swaps the two indices exactly when its flag is the character 'T'.
+ *   - the stable sort puts all of A's tuples of a key before B's; inside one operand a key's tuples keep storage order.
+ *   - every scaled value is alpha * v (also for alpha == 1 or 0: 0 * Inf is a NaN and survives); a NaN product or sum has
+ *     the bits x86-64 gives it, as in spsamd_multiply_dense.
+ *   - consolidate()'s quirks hold over the merged sequence: zeros (and under zero_nan NaNs) before its first kept entry are
+ *     dropped, after it only exact zeros (+-0); the rest is folded left to right by the policy (ADD: serial acc += v,
+ *     REPLACE: the last, LEAVE_ALONE: the first); a sum that cancels to 0.0 is emitted.
+ *   - sort0 and preparation only let the call skip a sort, they never change the result.  An operand whose sort0 names
+ *     op()'s row order while its (row, col) keys of op() are not in that order is rejected (SPSAMD_EINVAL).  A prepared
+ *     operand stands for its consolidated tuples.
+ * The shape of op(A) must equal that of op(B) (SPSAMD_EDIM); the result has that shape.  SPSAMD_EINVAL: nnz(A) + nnz(B)
+ * >= 2^31, an index out of bounds, a policy outside 0..2, a null pointer, both output buffers of the context operands
+ * of the call.  Sinks as for spsamd_multiply: SINK_COO (row-major tuples in the context's output set, chainable as a
+ * MEM_DEVICE sort0 = 0 operand -- sort0 = 1 with SINK_PERMUTE -- and fetchable), SINK_DIGEST (+ ROWSTATS); SINK_ORDERED
+ * and SINK_EXACT_PATTERN are accepted and change nothing.  result: nnz, shape, nnz_a / nnz_b (input tuples),
+ * ms_consolidate (the operands' sorts; 0 when none ran), ms_total, workspace_bytes.  Returns when the result is complete.
+ */
+int spsamd_add(spsamd_ctx *ctx,
+	double alpha, const spsamd_coo *A, char transpose_A,
+	double beta, const spsamd_coo *B, char transpose_B,
+	int duplicate_policy, int zero_nan,
+	int sink_kind, int sink_flags,
+	spsamd_result *result);
 
 /* Copy `bytes` between host and/or device memory of this context's device
  * (e.g. result->row_nnz to the host, result->idx0 into a caller's device

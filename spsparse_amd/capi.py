@@ -77,7 +77,7 @@ SYMBOLS = ["spsamd_ctx_create", "spsamd_ctx_destroy", "spsamd_last_error", "spsa
            "spsamd_gen_random_rows", "spsamd_gen_poisson2d", "spsamd_gen_laplace3d", "spsamd_gen_aggregation3d",
            "spsamd_dist_unique_id", "spsamd_dist_create", "spsamd_dist_destroy", "spsamd_dist_multiply",
            "spsamd_operand_prepare", "spsamd_operand_as_coo", "spsamd_operand_bytes", "spsamd_operand_destroy",
-           "spsamd_multiply_dense"]
+           "spsamd_multiply_dense", "spsamd_add"]
 
 _lib = None
 
@@ -117,6 +117,8 @@ def load():
     L.spsamd_result_scatter_dense.argtypes = [C.c_void_p, P(Result), C.c_void_p, C.c_size_t, C.c_int]
     L.spsamd_multiply_dense.argtypes = [C.c_void_p, P(Coo), C.c_char, C.c_void_p, C.c_size_t, C.c_void_p, C.c_size_t,
                                         C.c_size_t, C.c_int, C.c_int, C.c_int]
+    L.spsamd_add.argtypes = [C.c_void_p, C.c_double, P(Coo), C.c_char, C.c_double, P(Coo), C.c_char,
+                             C.c_int, C.c_int, C.c_int, C.c_int, P(Result)]
     L.spsamd_memcpy.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_size_t]
     L.spsamd_consolidate.argtypes = [C.c_void_p, P(Coo), C.c_int, C.c_int, C.c_int, P(Result)]
     L.spsamd_sorted_permutation.argtypes = [C.c_void_p, P(Coo), C.c_int, C.c_void_p]
@@ -218,6 +220,15 @@ class Context:
         ptr = [None if s is None else C.byref(s) for s in (scalei, scalej)]
         rc = self.L.spsamd_multiply_mv(self.h, float(C_), ptr[0], C.byref(A), tA.encode(), ptr[1], C.byref(V),
                                        duplicate_policy, int(zero_nan), sink, flags, C.byref(res))
+        self._check(rc)
+        return res
+
+    def add(self, A, B, alpha=1.0, beta=1.0, tA='.', tB='.', duplicate_policy=ADD, zero_nan=False, sink=SINK_COO, flags=0):
+        """spsamd_add: alpha * op(A) + beta * op(B), the reference's consolidate() of the two operands' scaled tuples
+        appended (A's first).  A, B: Coo structs."""
+        res = Result()
+        rc = self.L.spsamd_add(self.h, float(alpha), C.byref(A), tA.encode(), float(beta), C.byref(B), tB.encode(),
+                               duplicate_policy, int(zero_nan), sink, flags, C.byref(res))
         self._check(rc)
         return res
 

@@ -20,7 +20,8 @@ static int bits_for(uint64_t dim)
 }
 
 // flags: bit0 = an index is out of [0, shape); bit1 = not (strictly sorted, no zero values); bit2 = not strictly in
-// (minor, major) order; bit3 = holds a value consolidate() may drop; bit4 = the major index descends somewhere
+// (minor, major) order; bit3 = holds a value consolidate() may drop; bit4 = the major index descends somewhere; bit5 = the
+// (major, minor) key descends somewhere (not even non-decreasing: duplicates allowed)
 __global__ void k_inspect(const int32_t *major, const int32_t *minor, const double *val, size_t n,
 	uint64_t nrow, uint64_t ncol, int zero_nan, uint32_t *flags)
 {
@@ -36,6 +37,7 @@ __global__ void k_inspect(const int32_t *major, const int32_t *minor, const doub
 			int32_t pr = major[i - 1], pc = minor[i - 1];
 			if (!(pr < r || (pr == r && pc < c))) f |= 2u;
 			if (pr > r) f |= 16u;                                       // the MAJOR index itself descends: not even row-grouped
+			if (pr > r || (pr == r && pc > c)) f |= 32u;
 			if (!(pc < c || (pc == c && pr < r))) f |= 4u;          // not STRICTLY in (minor, major) order either
 		}
 	}
@@ -46,7 +48,7 @@ __global__ void k_inspect(const int32_t *major, const int32_t *minor, const doub
 	__syncthreads();
 	uint32_t wf = 0;
 #pragma unroll
-	for (uint32_t b = 1u; b <= 16u; b <<= 1) if (__ballot(f & b)) wf |= b;
+	for (uint32_t b = 1u; b <= 32u; b <<= 1) if (__ballot(f & b)) wf |= b;
 	if (wf && lane_id() == 0) atomicOr(&s_f, wf);
 	__syncthreads();
 	if (threadIdx.x == 0 && s_f && (*(volatile uint32_t *)flags & s_f) != s_f) atomicOr(flags, s_f);

@@ -92,6 +92,7 @@ struct Tuning {
 	int index_budget_mb = 0;     // 0: 80 % of the free device memory; cap (MB) of the heavy rows' window indices, beyond which the product goes by column blocks
 	int spmm_path = 0;           // multiply_dense: 0 auto | 1 serial kernel for every row | 2 lanes kernel for every row | 3 fold kernel for every row
 	int spmm_long_min = 0;       // multiply_dense, auto: rows of more tuples than this go to a wave kernel (0: 64)
+	int add_path = 0;            // add: 0 auto | 1 sort every operand (ignore sort0, chained results and preparation)
 #ifdef SPSAMD_ABLATIONS
 	int dbg = 0;
 #endif
@@ -201,7 +202,8 @@ void consolidate_operand(spsamd_ctx *c, const spsamd_coo *X, int lead, int ref_l
 void first_kept_key_raw(spsamd_ctx *c, const spsamd_coo *Xdev, int lead, int ref_lead, unsigned long long *out_dev);
 
 // Inspection flags of tuples (major, minor, val) on the device (k_inspect): bit0 an index out of [0, nrow) x [0, ncol),
-// bit4 the major index descends somewhere; the other bits are consolidate_operand's own.
+// bit4 the major index descends somewhere, bit5 the (major, minor) key descends somewhere; the other bits are
+// consolidate_operand's own.
 uint32_t inspect_operand(spsamd_ctx *c, const int32_t *major, const int32_t *minor, const double *val, size_t n,
 	uint64_t nrow, uint64_t ncol);
 
@@ -312,6 +314,12 @@ void dense_operand(spsamd_ctx *c, const spsamd_coo *M, int lead, DenseOperand *o
 // Y[i * ldy + r] (op)= op(M)(i, j) * X[j * ldx + r] in storage order, X and Y device memory
 void spmm_dense(spsamd_ctx *c, const DenseOperand &m, const double *X, uint64_t ldx, double *Y, uint64_t ldy, uint32_t nrhs,
 	int policy, bool handle_nan);
+
+// ---------------------------------------------------------------- sparse addition (k_add.hip)
+
+// C = alpha * op(A) + beta * op(B) into the sink: spsamd_add after its null checks
+void add_matrices(spsamd_ctx *c, double alpha, const spsamd_coo *A, char transpose_A, double beta, const spsamd_coo *B,
+	char transpose_B, int duplicate_policy, int zero_nan, int sink_kind, int sink_flags, spsamd_result *res);
 
 // Select the output set the next result is written to: the current one unless a device operand lives in it.
 void pick_output_set(spsamd_ctx *c, const spsamd_coo *const *operands, int n);

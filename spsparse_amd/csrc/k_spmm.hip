@@ -17,29 +17,11 @@
 //            lane each: long rows, nrhs < 16
 #include "internal.h"
 #include "devutil.h"
+#include "x86fp.h"
 
 namespace spsamd {
 
 static unsigned grid_of(size_t n, unsigned bs = 256) { return (unsigned)((n + bs - 1) / bs); }
-
-constexpr uint64_t X86_DEFAULT_NAN = 0xFFF8000000000000ull;
-
-__device__ __forceinline__ double quiet(double a)
-{
-	return __longlong_as_double(__double_as_longlong(a) | 0x0008000000000000ll);
-}
-
-// The NaN an x86-64 SSE mulsd / addsd returns for operands (a, b) when its result is a NaN.
-__device__ __forceinline__ double x86_nan(double a, double b)
-{
-	return a != a ? quiet(a) : b != b ? quiet(b) : __longlong_as_double((long long)X86_DEFAULT_NAN);
-}
-
-__device__ __forceinline__ double ref_mul(double a, double b)
-{
-	double r = a * b;
-	return r != r ? x86_nan(a, b) : r;
-}
 
 // One step of DenseAccum::add (accum.hpp:124-135) on the entry y with the product p.
 template <int POLICY, bool HNAN>

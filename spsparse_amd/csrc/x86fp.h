@@ -1,0 +1,37 @@
+// x86fp.h -- double arithmetic whose NaN results carry the bits x86-64 SSE gives them (the reference's build).
+// The GPU returns its own default NaN; an x86-64 mulsd / addsd returns the left operand's NaN, quieted, if it is one,
+// else the right operand's, else the default NaN 0xFFF8000000000000 (0 * Inf, Inf - Inf).  Used by multiply_dense
+// (k_spmm.hip) and add (k_add.hip); DESIGN.md §9.
+#pragma once
+
+#include <hip/hip_runtime.h>
+#include <stdint.h>
+
+namespace spsamd {
+
+constexpr uint64_t X86_DEFAULT_NAN = 0xFFF8000000000000ull;
+
+__device__ __forceinline__ double quiet(double a)
+{
+	return __longlong_as_double(__double_as_longlong(a) | 0x0008000000000000ll);
+}
+
+// The NaN an x86-64 SSE mulsd / addsd returns for operands (a, b) when its result is a NaN.
+__device__ __forceinline__ double x86_nan(double a, double b)
+{
+	return a != a ? quiet(a) : b != b ? quiet(b) : __longlong_as_double((long long)X86_DEFAULT_NAN);
+}
+
+__device__ __forceinline__ double ref_mul(double a, double b)
+{
+	double r = a * b;
+	return r != r ? x86_nan(a, b) : r;
+}
+
+__device__ __forceinline__ double ref_add(double a, double b)
+{
+	double r = a + b;
+	return r != r ? x86_nan(a, b) : r;
+}
+
+} // namespace spsamd
