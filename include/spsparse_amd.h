@@ -319,6 +319,62 @@ int spsamd_add(spsamd_ctx *ctx,
 	int sink_kind, int sink_flags,
 	spsamd_result *result);
 
+/*
+ * The product of spsamd_multiply, delivered to the host in row blocks while it is computed: the whole of C never sits in
+ * device memory at once, so a product larger than the device can still reach a host accumulator.
+ *   Tuples  cb receives consecutive chunks, each of at least one tuple, in ascending (i, j) order over the whole product.
+ *           Concatenated they are what spsamd_multiply(..., SPSAMD_SINK_COO, sink_flags) followed by
+ *           spsamd_result_fetch delivers: bit for bit (NaN payloads included) under SPSAMD_SINK_ORDERED; under
+ *           SINK_EXACT_PATTERN and flags 0 by the same rules as spsamd_multiply with those flags.  SINK_PERMUTE gives
+ *           (j, i, v) in C's row order; SINK_ROWSTATS is refused (SPSAMD_EINVAL).  The callback contract is
+ *           spsamd_result_fetch's: host pointers valid during the call, j never NULL.  A non-zero return stops the
+ *           delivery; the call returns that value once no work of the call is still running on the device.  cb is called
+ *           on the calling thread.
+ *   Blocks  Over the consolidated op(A) and op(B) (after the policy and zero_nan), P_r = the sum of len_op(B)(k) over the
+ *           tuples (r, k) of op(A), and bound_r = min(P_r, cols(op(B))) (scale vectors ignored: still an upper bound of
+ *           the row's tuples).  The blocks are the maximal runs of consecutive rows (from row 0, empty rows included)
+ *           whose bounds sum to at most block_tuples: a block ends where the next row would take the sum over it.
+ *           stats->blocks is their count.  A bound_r > block_tuples fails with SPSAMD_ECAPACITY before anything is
+ *           delivered; the message names the smallest budget that works (the largest bound_r).
+ *           block_tuples == 0: SPSAMD_STREAM_DEFAULT_BLOCK (2^30 tuples, 16 GiB per block output set).
+ *   Memory  At most two blocks' outputs exist at once, each sized to its block's bound sum at 16 bytes per tuple:
+ *           device_output_bytes <= 2 * 16 * block_tuples plus the rounding of six allocations to 256 bytes, whatever
+ *           nnz(C) is.  The workspace (context arena) and the operands' derived structures come on top, as for
+ *           spsamd_multiply.  Pinned host staging: two chunks of at most 2^22 tuples, 128 MiB, kept by the context.
+ *   Errors  Every check spsamd_multiply makes (SPSAMD_EDIM, an index out of bounds, an unsorted scale vector, a bad
+ *           policy) fails before cb is first called.  A failure after chunks were delivered returns its code, and the
+ *           context stays usable.
+ *   Context Neither output set of the context is written: a chained operand (an earlier SINK_COO result) is read in
+ *           place and keeps its tuples; treat any other SINK_COO result of the context as invalid after the call.
+ *           Any call on the same context from inside cb (spsamd_ctx_set_tuning included) returns SPSAMD_EINVAL
+ *           ("context busy").  Prepared operands (SPSAMD_MEM_PREPARED) are accepted; a handle the call uses must outlive
+ *           it (spsamd_operand_destroy on it from inside cb is undefined).
+ *   Columns A product spsamd_multiply would compute by column blocks of op(B) (a row of more than 4096 products and
+ *           more than 2^25 columns, or window indices over the budget -- index_budget_mb) is refused with
+ *           SPSAMD_EINVAL before any delivery.  The test is conservative: it uses P_r without the scale vectors.
+ * result gets the totals: shape, nnz, products, nnz_a / nnz_b, rows / products / tuples / cells by class, the stage times
+ * summed over the blocks, ms_consolidate, ms_total (the call's device time), workspace_bytes; idx0, idx1 and val are NULL.
+ * stats (may be NULL) gets the figures of the blocking.
+ */
+#define SPSAMD_STREAM_DEFAULT_BLOCK ((size_t)1 << 30)
+typedef struct {
+	uint64_t blocks;              /* row blocks the product was cut into */
+	uint64_t block_tuples;        /* the budget in effect (after the default was applied) */
+	uint64_t max_block_nnz;       /* largest block actually produced */
+	uint64_t device_output_bytes; /* peak device bytes held for block outputs during the call */
+	float ms_device;              /* sum of the blocks' device times (HIP events) */
+	float ms_callback;            /* host time spent inside cb */
+	float ms_wall;                /* whole call */
+} spsamd_stream_stats;
+
+int spsamd_multiply_stream(spsamd_ctx *ctx, double C,
+	const spsamd_vec *scalei, const spsamd_coo *A, char transpose_A,
+	const spsamd_vec *scalej, const spsamd_coo *B, char transpose_B,
+	const spsamd_vec *scalek, int duplicate_policy, int zero_nan,
+	int sink_flags, size_t block_tuples,
+	spsamd_chunk_fn cb, void *user,
+	spsamd_result *result, spsamd_stream_stats *stats);
+
 /* Copy `bytes` between host and/or device memory of this context's device
  * (e.g. result->row_nnz to the host, result->idx0 into a caller's device
  * buffer), ordered after everything queued on the context's stream; returns

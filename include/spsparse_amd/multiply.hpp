@@ -62,6 +62,11 @@ inline error_ptr spsparse_error = &default_error;
 // times slower on heavy rows), or to 0 for the fastest path (arrival-order sums, pattern exact unless terms cancel).
 inline int multiply_flags = SPSAMD_SINK_EXACT_PATTERN;
 
+// Opt-in: when non-zero, the matrix x matrix multiply() delivers through spsamd_multiply_stream with this many tuples per
+// row block (the product never sits in device memory whole: C may be larger than the device).  At 0 it multiplies into
+// the device sink and fetches, as always.
+inline size_t stream_block_tuples = 0;
+
 inline const std::array<int, 2> ROW_MAJOR = {0, 1};
 inline const std::array<int, 2> COL_MAJOR = {1, 0};
 
@@ -404,6 +409,13 @@ void multiply(
 	spsamd_ctx *ctx = default_context().get();
 	if (!ctx) return;
 	spsamd_result res;
+	if (stream_block_tuples) {
+		int rc = spsamd_multiply_stream(ctx, C, scalei ? &si : nullptr, &a, transpose_A, scalej ? &sj : nullptr, &b, transpose_B,
+			scalek ? &sk : nullptr, (int)duplicate_policy, zero_nan ? 1 : 0, multiply_flags, stream_block_tuples,
+			&detail::add_chunk<AccumulatorT>, &ret, &res, nullptr);
+		if (rc != 0) (*spsparse_error)(-1, "%s", spsamd_last_error(ctx));
+		return;
+	}
 	int rc = spsamd_multiply(ctx, C, scalei ? &si : nullptr, &a, transpose_A, scalej ? &sj : nullptr, &b, transpose_B,
 		scalek ? &sk : nullptr, (int)duplicate_policy, zero_nan ? 1 : 0, SPSAMD_SINK_COO, multiply_flags, &res);
 	if (rc != 0) { (*spsparse_error)(-1, "%s", spsamd_last_error(ctx)); return; }

@@ -59,6 +59,12 @@ class Result(C.Structure):
                 ("row_hash", C.c_void_p)]
 
 
+class StreamStats(C.Structure):
+    _fields_ = [("blocks", C.c_uint64), ("block_tuples", C.c_uint64), ("max_block_nnz", C.c_uint64),
+                ("device_output_bytes", C.c_uint64), ("ms_device", C.c_float), ("ms_callback", C.c_float),
+                ("ms_wall", C.c_float)]
+
+
 class DistStats(C.Structure):
     _fields_ = [("block_nnz_a", C.c_uint64), ("panel_tuples", C.c_uint64), ("remote_tuples", C.c_uint64),
                 ("sent_tuples", C.c_uint64), ("ms_exchange", C.c_float), ("pad_", C.c_float)]
@@ -77,7 +83,7 @@ SYMBOLS = ["spsamd_ctx_create", "spsamd_ctx_destroy", "spsamd_last_error", "spsa
            "spsamd_gen_random_rows", "spsamd_gen_poisson2d", "spsamd_gen_laplace3d", "spsamd_gen_aggregation3d",
            "spsamd_dist_unique_id", "spsamd_dist_create", "spsamd_dist_destroy", "spsamd_dist_multiply",
            "spsamd_operand_prepare", "spsamd_operand_as_coo", "spsamd_operand_bytes", "spsamd_operand_destroy",
-           "spsamd_multiply_dense", "spsamd_add"]
+           "spsamd_multiply_dense", "spsamd_add", "spsamd_multiply_stream"]
 
 _lib = None
 
@@ -119,6 +125,9 @@ def load():
                                         C.c_size_t, C.c_int, C.c_int, C.c_int]
     L.spsamd_add.argtypes = [C.c_void_p, C.c_double, P(Coo), C.c_char, C.c_double, P(Coo), C.c_char,
                              C.c_int, C.c_int, C.c_int, C.c_int, P(Result)]
+    L.spsamd_multiply_stream.argtypes = [C.c_void_p, C.c_double, P(Vec), P(Coo), C.c_char, P(Vec), P(Coo), C.c_char, P(Vec),
+                                         C.c_int, C.c_int, C.c_int, C.c_size_t, CHUNK_FN, C.c_void_p, P(Result),
+                                         P(StreamStats)]
     L.spsamd_memcpy.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_size_t]
     L.spsamd_consolidate.argtypes = [C.c_void_p, P(Coo), C.c_int, C.c_int, C.c_int, P(Result)]
     L.spsamd_sorted_permutation.argtypes = [C.c_void_p, P(Coo), C.c_int, C.c_void_p]
@@ -212,6 +221,38 @@ class Context:
                                     tB.encode(), ptr[2], duplicate_policy, int(zero_nan), sink, flags, C.byref(res))
         self._check(rc)
         return res
+
+    def multiply_stream(self, A, B, C_=1.0, scalei=None, tA='.', scalej=None, tB='.', scalek=None,
+                        duplicate_policy=ADD, zero_nan=False, flags=0, block_tuples=0, on_chunk=None):
+        """spsamd_multiply_stream: the product delivered in row blocks while it is computed.  on_chunk(i, j, v) gets
+        numpy views of each chunk (valid during the call only: copy what you keep) and returns None / 0 to go on or a
+        non-zero int to stop: the call then returns that value, raised as SpsamdError with that code.  An exception in
+        on_chunk stops the delivery and is re-raised.  Returns (Result, StreamStats)."""
+        if on_chunk is None:
+            raise ValueError("on_chunk is required")
+        res, stats = Result(), StreamStats()
+        raised = []
+
+        def cb(_user, pi, pj, pv, cnt):
+            try:
+                r = on_chunk(np.ctypeslib.as_array(pi, shape=(cnt,)), np.ctypeslib.as_array(pj, shape=(cnt,)),
+                             np.ctypeslib.as_array(pv, shape=(cnt,)))
+                return int(r or 0)
+            except BaseException as e:                      # never let an exception cross the C boundary
+                raised.append(e)
+                return 1
+
+        ptr = [None if s is None else C.byref(s) for s in (scalei, scalej, scalek)]
+        fn = CHUNK_FN(cb)
+        rc = self.L.spsamd_multiply_stream(self.h, float(C_), ptr[0], C.byref(A), tA.encode(), ptr[1], C.byref(B),
+                                           tB.encode(), ptr[2], duplicate_policy, int(zero_nan), flags, int(block_tuples),
+                                           fn, None, C.byref(res), C.byref(stats))
+        if raised:
+            raise raised[0]
+        if rc > 0:
+            raise SpsamdError(rc, "delivery stopped by on_chunk")
+        self._check(rc)
+        return res, stats
 
     def multiply_mv(self, A, V, C_=1.0, scalei=None, tA='.', scalej=None, duplicate_policy=ADD, zero_nan=False,
                     sink=SINK_COO, flags=0):

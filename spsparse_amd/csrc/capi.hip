@@ -13,7 +13,9 @@
 
 using namespace spsamd;
 
+// (a streamed multiply's callback runs while the call still works on the context: every entry point refuses it)
 #define API_GUARD(ctx, ...)                                                         \
+	if ((ctx)->busy) { (ctx)->last_error = "context busy: a streamed multiply is delivering on it"; return SPSAMD_EINVAL; } \
 	try { __VA_ARGS__ }                                                             \
 	catch (const spsamd::Error &e) { (ctx)->last_error = e.msg; return e.code; }    \
 	catch (const std::bad_alloc &) { (ctx)->last_error = "host allocation failed"; return SPSAMD_ENOMEM; } \
@@ -63,6 +65,7 @@ extern "C" int spsamd_ctx_create(spsamd_ctx **out, int device, void *hip_stream)
 extern "C" int spsamd_ctx_set_tuning(spsamd_ctx *c, const char *name, long value)
 {
 	if (!c || !name) return SPSAMD_EINVAL;
+	if (c->busy) { c->last_error = "context busy: a streamed multiply is delivering on it"; return SPSAMD_EINVAL; }
 	struct { const char *n; int *p; } tab[] = {
 		{"window", &c->tune.window}, {"cell_cap", &c->tune.cell_cap}, {"dense_min", &c->tune.dense_min},
 		{"no_tiles", &c->tune.no_tiles}, {"xcd", &c->tune.xcd}, {"emit_path", &c->tune.emit_path},
@@ -85,6 +88,7 @@ extern "C" void spsamd_ctx_destroy(spsamd_ctx *c)
 	c->out[0].release(); c->out[1].release();
 	c->rowstat_n.release(); c->rowstat_s.release(); c->rowstat_h.release();
 	if (c->pinned) (void)hipHostFree(c->pinned);
+	if (c->stream_pinned) (void)hipHostFree(c->stream_pinned);
 	for (auto &e : c->ev) if (e) (void)hipEventDestroy(e);
 	for (auto &e : c->ev2) if (e) (void)hipEventDestroy(e);
 	for (auto &e : c->ev_side) if (e) (void)hipEventDestroy(e);
@@ -113,22 +117,24 @@ extern "C" int spsamd_ctx_reserve(spsamd_ctx *c, size_t workspace_bytes, size_t 
 	)
 }
 
+bool spsamd::output_set_aliased(const spsamd_ctx *c, int s, const spsamd_coo *const *operands, int n)
+{
+	for (int k = 0; k < n; ++k) {
+		const spsamd_coo *X = operands[k];
+		if (X && X->mem == SPSAMD_MEM_DEVICE && (c->out[s].holds(X->idx0) || c->out[s].holds(X->idx1) || c->out[s].holds(X->val))) return true;
+	}
+	return false;
+}
+
 void spsamd::pick_output_set(spsamd_ctx *c, const spsamd_coo *const *operands, int n)
 {
-	auto aliased = [&](int s) {
-		for (int k = 0; k < n; ++k) {
-			const spsamd_coo *X = operands[k];
-			if (X && X->mem == SPSAMD_MEM_DEVICE && (c->out[s].holds(X->idx0) || c->out[s].holds(X->idx1) || c->out[s].holds(X->val))) return true;
-		}
-		return false;
-	};
-	if (!aliased(c->cur_out)) return;
-	if (aliased(c->cur_out ^ 1))
+	if (!output_set_aliased(c, c->cur_out, operands, n)) return;
+	if (output_set_aliased(c, c->cur_out ^ 1, operands, n))
 		throw Error{SPSAMD_EINVAL, "both result buffers of this context are operands of the call: copy one of them out first (spsamd_memcpy)"};
 	c->cur_out ^= 1;
 }
 
-static bool same_operand(const spsamd_coo *a, const spsamd_coo *b)
+bool spsamd::same_operand(const spsamd_coo *a, const spsamd_coo *b)
 {
 	return a->idx0 == b->idx0 && a->idx1 == b->idx1 && a->val == b->val && a->nnz == b->nnz &&
 		a->shape0 == b->shape0 && a->shape1 == b->shape1 && a->sort0 == b->sort0 && a->mem == b->mem;
@@ -212,6 +218,23 @@ extern "C" int spsamd_multiply(spsamd_ctx *c, double C,
 		if (!A || !B || !res) throw Error{SPSAMD_EINVAL, "null operand or result"};
 		return multiply_body(c, C, scalei, A, transpose_A, scalej, B, transpose_B, scalek, duplicate_policy, zero_nan,
 			sink_kind, sink_flags, res, "B", false);
+	)
+}
+
+// The product delivered in row blocks while it is computed (k_stream.hip)
+extern "C" int spsamd_multiply_stream(spsamd_ctx *c, double C,
+	const spsamd_vec *scalei, const spsamd_coo *A, char transpose_A,
+	const spsamd_vec *scalej, const spsamd_coo *B, char transpose_B,
+	const spsamd_vec *scalek, int duplicate_policy, int zero_nan,
+	int sink_flags, size_t block_tuples, spsamd_chunk_fn cb, void *user,
+	spsamd_result *res, spsamd_stream_stats *stats)
+{
+	if (!c) return SPSAMD_EINVAL;
+	API_GUARD(c,
+		if (!A || !B || !res || !cb) throw Error{SPSAMD_EINVAL, "null operand, callback or result"};
+		struct Busy { spsamd_ctx *c; Busy(spsamd_ctx *x) : c(x) { c->busy = true; } ~Busy() { c->busy = false; } } busy{c};
+		return multiply_stream(c, C, scalei, A, transpose_A, scalej, B, transpose_B, scalek, duplicate_policy, zero_nan,
+			sink_flags, block_tuples, cb, user, res, stats);
 	)
 }
 

@@ -124,6 +124,9 @@ struct spsamd_ctx {
 	void join_side(bool wm, bool sort);      // make the main stream wait for it (no-op where nothing is pending)
 	int num_cu = 256;
 	void *host_staging(size_t bytes);
+	bool busy = false;                       // a streamed multiply is delivering: every entry point refuses the context
+	void *stream_pinned = nullptr;           // the streamed multiply's two chunk buffers (host staging of its own)
+	size_t stream_pinned_cap = 0;
 };
 
 namespace spsamd {
@@ -283,6 +286,7 @@ struct MultiplyArgs {
 	Prepared *pa = nullptr, *pb = nullptr;   // derived structures of A / B that already exist (or are kept once built): may be null
 	hipEvent_t b_ready = nullptr;            // the TUPLES of B arrive on another stream (the distributed step's panel): wait for this
 	                                         // event before the first kernel that reads them; its row pointer (pb->rowptr) is valid at once
+	OutSet *out = nullptr;                   // SINK_COO: the arrays the tuples go to (null: the context's current output set)
 };
 void spgemm(spsamd_ctx *c, MultiplyArgs &a, spsamd_result *res);
 void prepared_row_structure(spsamd_ctx *c, Prepared *p);      // its dense row pointer and longest row, now (spgemm.hip)
@@ -297,6 +301,16 @@ int multiply_body(spsamd_ctx *c, double C,
 	const spsamd_vec *scalej, const spsamd_coo *B, char transpose_B,
 	const spsamd_vec *scalek, int duplicate_policy, int zero_nan,
 	int sink_kind, int sink_flags, spsamd_result *res, const char *what, bool arena_ready, const OperandParts *parts = nullptr);
+
+// ---------------------------------------------------------------- streamed product (k_stream.hip)
+
+// spsamd_multiply_stream after its null checks
+int multiply_stream(spsamd_ctx *c, double C,
+	const spsamd_vec *scalei, const spsamd_coo *A, char transpose_A,
+	const spsamd_vec *scalej, const spsamd_coo *B, char transpose_B,
+	const spsamd_vec *scalek, int duplicate_policy, int zero_nan,
+	int sink_flags, size_t block_tuples, spsamd_chunk_fn cb, void *user,
+	spsamd_result *res, spsamd_stream_stats *stats);
 
 // ---------------------------------------------------------------- dense right-hand sides (k_spmm.hip)
 
@@ -323,5 +337,9 @@ void add_matrices(spsamd_ctx *c, double alpha, const spsamd_coo *A, char transpo
 
 // Select the output set the next result is written to: the current one unless a device operand lives in it.
 void pick_output_set(spsamd_ctx *c, const spsamd_coo *const *operands, int n);
+// Does output set `s` of the context hold an array of one of the device operands?
+bool output_set_aliased(const spsamd_ctx *c, int s, const spsamd_coo *const *operands, int n);
+// The same operand struct twice (A * A): one consolidation can serve both sides.
+bool same_operand(const spsamd_coo *a, const spsamd_coo *b);
 
 } // namespace spsamd

@@ -379,7 +379,7 @@ static void spgemm_all_light(spsamd_ctx *c, MultiplyArgs &a, spsamd_result *res,
 		uint32_t *segactual = c->arena.get<uint32_t>(nsegs + 1);
 		int64_t *segoff = c->arena.get<int64_t>(nsegs + 1);
 		sk.segcount = segcount; sk.segactual = segactual;
-		OutSet &os = c->out[c->cur_out];
+		OutSet &os = a.out ? *a.out : c->out[c->cur_out];
 		// ONE compute pass where the memory is there: every wave round writes the tuples of its G rows, packed, to its own 64
 		// slots of a sparse buffer and says how many; scan; a gather packs the rounds.  The other way -- count, scan, store
 		// -- evaluates every product twice: Poisson 4096^2 8.1 ms against 3.8 for the digest.
@@ -697,7 +697,7 @@ static void spgemm_once(spsamd_ctx *c, MultiplyArgs &a, spsamd_result *res)
 		launch_heavy_dense<MODE_COUNT>(c, hv, m, ep, sk);
 		scan_exclusive_u32_i64(c, segcount, segoff, (size_t)nsegs);
 		int64_t reserved = read_back(c, segoff + nsegs);
-		OutSet &os = c->out[c->cur_out];              // chosen by multiply_body: never the set an operand lives in
+		OutSet &os = a.out ? *a.out : c->out[c->cur_out];   // chosen by multiply_body: never the set an operand lives in
 		os.i.ensure((size_t)reserved * sizeof(int32_t));
 		os.j.ensure((size_t)reserved * sizeof(int32_t));
 		os.v.ensure((size_t)reserved * sizeof(double));
@@ -873,6 +873,11 @@ static void spgemm_column_blocks(spsamd_ctx *c, MultiplyArgs &a, spsamd_result *
 	}
 	res->nnz = total;
 	res->idx0 = oi; res->idx1 = oj; res->val = ov;
+}
+
+void spgemm_row_slice(spsamd_ctx *c, MultiplyArgs &a, spsamd_result *res)
+{
+	spgemm_once(c, a, res);
 }
 
 void spgemm(spsamd_ctx *c, MultiplyArgs &a, spsamd_result *res)

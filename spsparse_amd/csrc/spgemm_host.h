@@ -79,10 +79,15 @@ template <int MODE> void launch_tiles_direct(spsamd_ctx *c, const Heavy &hv, con
 template <int MODE> void launch_heavy_dense(spsamd_ctx *c, const Heavy &hv, const RowMeta &m0, const EmitParams &ep, const SinkParams &sk);   // k_dense.hip
 
 // ---- the heavy rows' symbolic phase (symbolic_heavy.hip)
+int heavy_b_index(spsamd_ctx *c, const ConMat &B, const uint32_t *bptr, uint32_t extra, uint64_t nheavy, Prepared *pb);
 void heavy_prepare(spsamd_ctx *c, Heavy &hv, const Bins &bins, const RowMeta &m, const ConMat &B, const uint32_t *bptr,
 	uint32_t extra, uint32_t *nseg, bool ordered, bool pattern, Prepared *pb);
 void heavy_cells(spsamd_ctx *c, Heavy &hv, const RowMeta &m, const uint32_t *segbase);
 void heavy_sort_lists(spsamd_ctx *c, Heavy &hv);
+
+// ---- the streamed product's row slice (spgemm.hip): a.A holds a run of whole rows of op(A) (its tuple arrays offset, nrow
+// unchanged); the COO result goes to a.out.  Never by column blocks: a product that would need them throws TooWide.
+void spgemm_row_slice(spsamd_ctx *c, MultiplyArgs &a, spsamd_result *res);
 
 #ifdef SPSAMD_ABLATIONS
 void set_ablation_word(spsamd_ctx *c, int word);          // k_hash.hip (the only unit that reads it through ABLG)

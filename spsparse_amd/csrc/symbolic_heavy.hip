@@ -465,65 +465,75 @@ static void heavy_window_major(spsamd_ctx *c, Heavy &hv, const ConMat &B, uint32
 	SPS_LAUNCH_CHECK();
 }
 
+// The column-window index of B (bwin and its 16-bit counts) into pb, unless pb holds it already for this width; `nheavy`:
+// the heavy rows it is for (their histograms count against the budget).  Throws TooWide where op(B) has more windows than
+// the heavy-row path indexes or the index would not fit.  Returns the window width.
+int heavy_b_index(spsamd_ctx *c, const ConMat &B, const uint32_t *bptr, uint32_t extra, uint64_t nheavy, Prepared *pb)
+{
+	hipStream_t st = c->stream;
+	int W = B.ncol > (uint64_t(1) << 21) ? 16384 : 8192;
+	if (c->tune.window == 8192 || c->tune.window == 16384) W = c->tune.window;
+	const uint32_t wshift = W == 8192 ? 13 : 14;
+	const uint32_t nwin = (uint32_t)((B.ncol + W - 1) >> wshift);
+	if (nwin > (uint32_t)WH_MAXW) throw TooWide{COLBLK};             // spgemm() then multiplies by column blocks of B
+	const uint64_t nrowb = B.nrow + extra;
+	// B's record already holds the indices for this window width (a prepared operand after its first multiply with heavy rows)
+	if (pb->bwin && pb->W == W && pb->nrowb == nrowb) return W;
+	// The window indices (bwin, its 16-bit counts, the window-major pointer with its counts, the heavy rows' histograms)
+	// grow with rows(B) x windows: 12 bytes per B row and window.  Where they would not fit what the device has left
+	// (or the cap a test sets), the product goes by column blocks narrow enough for them to fit.
+	const uint64_t per_window = nrowb * 12u + nheavy * 4u;
+	uint64_t budget;
+	const uint64_t room = (pb->owns || c->arena.slabs.empty()) ? 0 : c->arena.slabs.back().cap - c->arena.slabs.back().used;
+	if (c->tune.index_budget_mb > 0) budget = (uint64_t)c->tune.index_budget_mb << 20;
+	else if (per_window * (nwin + 1ull) <= room) budget = room;     // (the steady state: the workspace of an earlier call holds them)
+	else {
+		size_t freeb = 0, totalb = 0;
+		SPS_HIP(hipMemGetInfo(&freeb, &totalb));
+		budget = (uint64_t)((double)(freeb + room) * 0.8);
+	}
+	if (per_window * (nwin + 1ull) > budget && nwin > 1) {
+		uint64_t fit = budget / per_window;                             // windows per block that fit
+		if (fit < 2) throw Error{SPSAMD_ENOMEM, "the window index of one column window of op(B) does not fit the device"};
+		uint64_t w2 = 1;
+		while (w2 * 2 <= fit - 1) w2 *= 2;
+		throw TooWide{w2 << wshift};
+	}
+	const uint32_t nwin1 = nwin + 1, nwp = (nwin + 7u) & ~7u;
+	pb->reserve(nrowb * nwin1 * 4 + nrowb * nwp * 2 + (nrowb * nwin + 1) * 4 + ((size_t)B.nnz + DENSE_R) * sizeof(BTup) + 4096);   // (a handle: one slab for all four)
+	pb->bwin = pb->get<uint32_t>(nrowb * nwin1);
+	pb->wcnt = pb->get<uint16_t>(nrowb * nwp);
+	pb->W = W; pb->nwin = nwin; pb->nwp = nwp; pb->nrowb = nrowb;
+	pb->wptr = nullptr; pb->btw = nullptr;
+	fill_zero(c, pb->wcnt, nrowb * nwp * sizeof(uint16_t));
+	k_wcnt_count<<<dim3((unsigned)c->num_cu * 16u), dim3(BT_NT), 0, st>>>(B.row, B.col, B.nnz, wshift, nwp, reinterpret_cast<uint32_t *>(pb->wcnt));
+	SPS_LAUNCH_CHECK();
+	// tile rows: as many as the LDS budget holds (128 at 136 windows, 32 at 512, 8 at 2048)
+	uint32_t tr = 256;
+	while (tr > 4 && (size_t)tr * (nwp * 2 + 4) > BT_LDS) tr >>= 1;
+	static bool lds_attr = false;                                   // (more than the default 64 KB of dynamic LDS)
+	if (!lds_attr) { SPS_HIP(hipFuncSetAttribute((const void *)k_bwin_scan, hipFuncAttributeMaxDynamicSharedMemorySize, (int)BT_LDS)); lds_attr = true; }
+	k_bwin_scan<<<dim3((unsigned)((nrowb + tr - 1) / tr)), dim3(BT_NT), (size_t)tr * (nwp * 2 + 4), st>>>(pb->wcnt, bptr, nrowb, tr, nwin, nwp, pb->bwin);
+	SPS_LAUNCH_CHECK();
+	return W;
+}
+
 // Heavy rows: window index of B, per-row window histogram, counting pass of the cell grouping.
 void heavy_prepare(spsamd_ctx *c, Heavy &hv, const Bins &bins, const RowMeta &m, const ConMat &B, const uint32_t *bptr,
 	uint32_t extra, uint32_t *nseg, bool ordered, bool pattern, Prepared *pb)
 {
 	hipStream_t st = c->stream;
-	hv.W = B.ncol > (uint64_t(1) << 21) ? 16384 : 8192;
-	if (c->tune.window == 8192 || c->tune.window == 16384) hv.W = c->tune.window;
+	hv.W = heavy_b_index(c, B, bptr, extra, hv.n, pb);
 	const uint32_t wshift = hv.W == 8192 ? 13 : 14;
 	hv.nwin = (uint32_t)((B.ncol + hv.W - 1) >> wshift);
-	if (hv.nwin > (uint32_t)WH_MAXW) throw TooWide{COLBLK};         // spgemm() then multiplies by column blocks of B
 	hv.nwin1 = hv.nwin + 1;
 	const uint64_t nrowb = B.nrow + extra;
-	// B's record already holds the indices for this window width (a prepared operand after its first multiply with heavy rows)
-	const bool have_index = pb->bwin && pb->W == hv.W && pb->nrowb == nrowb;
-	const bool have_wmajor = have_index && pb->wptr;
-	if (!have_index) {
-		// The window indices (bwin, its 16-bit counts, the window-major pointer with its counts, the heavy rows' histograms)
-		// grow with rows(B) x windows: 12 bytes per B row and window.  Where they would not fit what the device has left
-		// (or the cap a test sets), the product goes by column blocks narrow enough for them to fit.
-		const uint64_t per_window = nrowb * 12u + (uint64_t)hv.n * 4u;
-		uint64_t budget;
-		const uint64_t room = (pb->owns || c->arena.slabs.empty()) ? 0 : c->arena.slabs.back().cap - c->arena.slabs.back().used;
-		if (c->tune.index_budget_mb > 0) budget = (uint64_t)c->tune.index_budget_mb << 20;
-		else if (per_window * (hv.nwin + 1ull) <= room) budget = room;  // (the steady state: the workspace of an earlier call holds them)
-		else {
-			size_t freeb = 0, totalb = 0;
-			SPS_HIP(hipMemGetInfo(&freeb, &totalb));
-			budget = (uint64_t)((double)(freeb + room) * 0.8);
-		}
-		if (per_window * (hv.nwin + 1ull) > budget && hv.nwin > 1) {
-			uint64_t fit = budget / per_window;                         // windows per block that fit
-			if (fit < 2) throw Error{SPSAMD_ENOMEM, "the window index of one column window of op(B) does not fit the device"};
-			uint64_t w2 = 1;
-			while (w2 * 2 <= fit - 1) w2 *= 2;
-			throw TooWide{w2 << wshift};
-		}
-	}
+	const bool have_wmajor = pb->wptr != nullptr;                      // (heavy_b_index clears it where it builds the index)
 	hv.nrowb = nrowb;
 	hv.nnzb = B.nnz;
 	hv.rows = bins.rows + bins.off[8];
 	hv.winprod = c->arena.get<uint32_t>((uint64_t)hv.n * hv.nwin);
 	const uint32_t nwp = (hv.nwin + 7u) & ~7u;
-	if (!have_index) {
-		pb->reserve(nrowb * hv.nwin1 * 4 + nrowb * nwp * 2 + (nrowb * hv.nwin + 1) * 4 + ((size_t)B.nnz + DENSE_R) * sizeof(BTup) + 4096);   // (a handle: one slab for all four)
-		pb->bwin = pb->get<uint32_t>(nrowb * hv.nwin1);
-		pb->wcnt = pb->get<uint16_t>(nrowb * nwp);
-		pb->W = hv.W; pb->nwin = hv.nwin; pb->nwp = nwp; pb->nrowb = nrowb;
-		pb->wptr = nullptr; pb->btw = nullptr;
-		fill_zero(c, pb->wcnt, nrowb * nwp * sizeof(uint16_t));
-		k_wcnt_count<<<dim3((unsigned)c->num_cu * 16u), dim3(BT_NT), 0, st>>>(B.row, B.col, B.nnz, wshift, nwp, reinterpret_cast<uint32_t *>(pb->wcnt));
-		SPS_LAUNCH_CHECK();
-		// tile rows: as many as the LDS budget holds (128 at 136 windows, 32 at 512, 8 at 2048)
-		uint32_t tr = 256;
-		while (tr > 4 && (size_t)tr * (nwp * 2 + 4) > BT_LDS) tr >>= 1;
-		static bool lds_attr = false;                               // (more than the default 64 KB of dynamic LDS)
-		if (!lds_attr) { SPS_HIP(hipFuncSetAttribute((const void *)k_bwin_scan, hipFuncAttributeMaxDynamicSharedMemorySize, (int)BT_LDS)); lds_attr = true; }
-		k_bwin_scan<<<dim3((unsigned)((nrowb + tr - 1) / tr)), dim3(BT_NT), (size_t)tr * (nwp * 2 + 4), st>>>(pb->wcnt, bptr, nrowb, tr, hv.nwin, nwp, pb->bwin);
-		SPS_LAUNCH_CHECK();
-	}
 	hv.bwin = pb->bwin;
 	uint16_t *wcnt = pb->wcnt;
 	// The window-major copy of B needs only the index just built: it goes to the context's side stream now, beside the
