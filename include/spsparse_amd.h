@@ -197,6 +197,9 @@ const char *spsamd_version(void);
  *   spmm_long_min   > 0               multiply_dense: rows of more tuples than this go to a wave kernel (64)
  *   add_path        1                 add: sort every operand, ignoring sort0, chained results and preparation (default:
  *                                     an operand already in op()'s row-major order is read in place)
+ *   masked_path     1 | 2 | 3         multiply_masked: every mask key through the entry kernel (lane per key) | the row kernel
+ *                                     wherever A_i fits its LDS copy (4096 tuples; the other keys: entry) | the wave kernel
+ *                                     (wave per key) (default: by the lengths of A_i and B_j)
  * The environment variables of the same purpose (SPSAMD_W ...) are read once, inside spsamd_ctx_create; nothing reads
  * the environment later.  Unknown names: SPSAMD_EINVAL. */
 int spsamd_ctx_set_tuning(spsamd_ctx *ctx, const char *name, long value);
@@ -318,6 +321,42 @@ int spsamd_add(spsamd_ctx *ctx,
 	int duplicate_policy, int zero_nan,
 	int sink_kind, int sink_flags,
 	spsamd_result *result);
+
+/*
+ * ret = (C * diag(scalei) * op(A) * diag(scalej) * op(B) * diag(scalek)) restricted to the keys of M  -- a masked product
+ * (SDDMM-style sampling of a sparse product: (L*L) o L counts triangles).  The result is exactly those tuples of
+ *     spsparse::multiply(ret, C, scalei, A, transpose_A, scalej, B, transpose_B, scalek, duplicate_policy, zero_nan)
+ * whose key (i, j) is a key of M, in ascending (i, j), bit for bit (NaN payloads included) -- the reference being the
+ * inner-product loop of multiply_sparse.hpp:192-243 (the test oracle's orc_multiply_mm / orc_multiply_mm_rowwise), run
+ * over M's keys only:
+ *   - op(A) is consolidated by rows, op(B) by its columns (:187-188), with duplicate_policy and zero_nan.
+ *   - a row, column or k whose scale entry is missing or zero (isnone) is skipped (:195, :211, the join3 over scalej).
+ *   - sum starts at 0 and adds the products of the matched k in ascending k, serially, no FMA: a * b, or (a * sj) * b under
+ *     scalej; a NaN product or sum has the bits x86-64 gives it.
+ *   - the tuple is emitted when the PRE-scale sum is not 0 (:238): a NaN sum is emitted, and so is a sum that the scales
+ *     then turn into 0.0.  Its value is sum * C * a_scale * b_scale, left to right (a missing scale vector counts 1).
+ *   - C == 0, an empty scale vector, an empty operand (:178-184) or an empty M: an empty result of the product's shape.
+ * M is structural: its shape must be rows(op(A)) x cols(op(B)) (SPSAMD_EDIM otherwise; M has no transpose flag, it is
+ * given in C's orientation); M->val is never read and may be NULL; duplicate keys count once and explicit zeros count.  M
+ * may be host, device, a chained SINK_COO result of this context, or prepared (SPSAMD_MEM_PREPARED: its consolidated
+ * tuples; prepared for 'T', it is read as a device operand sorted the other way).  sort0 == 0 only lets the call skip the
+ * sort: keys that are not actually ascending are rejected.  SPSAMD_EINVAL: M NULL, an index of M out of bounds, a false
+ * sort0 == 0, nnz(M) >= 2^31, a policy outside 0..2, both output buffers of the context operands of the call (A, B and M
+ * count), and every check spsamd_multiply makes.
+ * Sinks: SINK_COO (row-major tuples in the context's output set, fetchable, usable with spsamd_result_scatter_dense,
+ * chainable as a MEM_DEVICE sort0 = 0 operand -- sort0 = 1 with SINK_PERMUTE, which swaps the index arrays), SINK_DIGEST
+ * (+ ROWSTATS over rows(op(A))); SINK_ORDERED and SINK_EXACT_PATTERN are accepted and change nothing.
+ * result: shape, nnz, nnz_a / nnz_b (the consolidated operands), products (the matched and summed k over all evaluated
+ * keys), ms_consolidate, ms_numeric, ms_total, workspace_bytes; the other fields are 0.  Returns when the result is
+ * complete.  The work is proportional to the keys of M and the lengths of their rows of op(A) and columns of op(B), not to
+ * the whole product.
+ */
+int spsamd_multiply_masked(spsamd_ctx *ctx, double C,
+	const spsamd_vec *scalei, const spsamd_coo *A, char transpose_A,
+	const spsamd_vec *scalej, const spsamd_coo *B, char transpose_B,
+	const spsamd_vec *scalek, const spsamd_coo *M,
+	int duplicate_policy, int zero_nan,
+	int sink_kind, int sink_flags, spsamd_result *result);
 
 /*
  * The product of spsamd_multiply, delivered to the host in row blocks while it is computed: the whole of C never sits in

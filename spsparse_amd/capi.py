@@ -83,7 +83,7 @@ SYMBOLS = ["spsamd_ctx_create", "spsamd_ctx_destroy", "spsamd_last_error", "spsa
            "spsamd_gen_random_rows", "spsamd_gen_poisson2d", "spsamd_gen_laplace3d", "spsamd_gen_aggregation3d",
            "spsamd_dist_unique_id", "spsamd_dist_create", "spsamd_dist_destroy", "spsamd_dist_multiply",
            "spsamd_operand_prepare", "spsamd_operand_as_coo", "spsamd_operand_bytes", "spsamd_operand_destroy",
-           "spsamd_multiply_dense", "spsamd_add", "spsamd_multiply_stream"]
+           "spsamd_multiply_dense", "spsamd_add", "spsamd_multiply_stream", "spsamd_multiply_masked"]
 
 _lib = None
 
@@ -128,6 +128,8 @@ def load():
     L.spsamd_multiply_stream.argtypes = [C.c_void_p, C.c_double, P(Vec), P(Coo), C.c_char, P(Vec), P(Coo), C.c_char, P(Vec),
                                          C.c_int, C.c_int, C.c_int, C.c_size_t, CHUNK_FN, C.c_void_p, P(Result),
                                          P(StreamStats)]
+    L.spsamd_multiply_masked.argtypes = [C.c_void_p, C.c_double, P(Vec), P(Coo), C.c_char, P(Vec), P(Coo), C.c_char, P(Vec),
+                                         P(Coo), C.c_int, C.c_int, C.c_int, C.c_int, P(Result)]
     L.spsamd_memcpy.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_size_t]
     L.spsamd_consolidate.argtypes = [C.c_void_p, P(Coo), C.c_int, C.c_int, C.c_int, P(Result)]
     L.spsamd_sorted_permutation.argtypes = [C.c_void_p, P(Coo), C.c_int, C.c_void_p]
@@ -219,6 +221,18 @@ class Context:
         ptr = [None if s is None else C.byref(s) for s in (scalei, scalej, scalek)]
         rc = self.L.spsamd_multiply(self.h, float(C_), ptr[0], C.byref(A), tA.encode(), ptr[1], C.byref(B),
                                     tB.encode(), ptr[2], duplicate_policy, int(zero_nan), sink, flags, C.byref(res))
+        self._check(rc)
+        return res
+
+    def multiply_masked(self, A, B, M, C_=1.0, scalei=None, tA='.', scalej=None, tB='.', scalek=None,
+                        duplicate_policy=ADD, zero_nan=False, sink=SINK_COO, flags=0):
+        """spsamd_multiply_masked: the tuples of multiply(A, B, ...) whose key is a key of M, bit for bit.  A, B, M: Coo
+        structs (M in the product's orientation, its values never read); scale*: Vec structs or None."""
+        res = Result()
+        ptr = [None if s is None else C.byref(s) for s in (scalei, scalej, scalek)]
+        rc = self.L.spsamd_multiply_masked(self.h, float(C_), ptr[0], C.byref(A), tA.encode(), ptr[1], C.byref(B),
+                                           tB.encode(), ptr[2], C.byref(M), duplicate_policy, int(zero_nan), sink, flags,
+                                           C.byref(res))
         self._check(rc)
         return res
 

@@ -93,6 +93,7 @@ struct Tuning {
 	int spmm_path = 0;           // multiply_dense: 0 auto | 1 serial kernel for every row | 2 lanes kernel for every row | 3 fold kernel for every row
 	int spmm_long_min = 0;       // multiply_dense, auto: rows of more tuples than this go to a wave kernel (0: 64)
 	int add_path = 0;            // add: 0 auto | 1 sort every operand (ignore sort0, chained results and preparation)
+	int masked_path = 0;         // multiply_masked: 0 auto | 1 entry kernel for every key | 2 row kernel wherever A_i fits LDS | 3 wave kernel for every key
 #ifdef SPSAMD_ABLATIONS
 	int dbg = 0;
 #endif
@@ -334,6 +335,15 @@ void spmm_dense(spsamd_ctx *c, const DenseOperand &m, const double *X, uint64_t 
 // C = alpha * op(A) + beta * op(B) into the sink: spsamd_add after its null checks
 void add_matrices(spsamd_ctx *c, double alpha, const spsamd_coo *A, char transpose_A, double beta, const spsamd_coo *B,
 	char transpose_B, int duplicate_policy, int zero_nan, int sink_kind, int sink_flags, spsamd_result *res);
+
+// ---------------------------------------------------------------- masked product (k_masked.hip)
+
+// op(A) * op(B) on the pattern of M: spsamd_multiply_masked after its null checks
+void multiply_masked(spsamd_ctx *c, double C,
+	const spsamd_vec *scalei, const spsamd_coo *A, char transpose_A,
+	const spsamd_vec *scalej, const spsamd_coo *B, char transpose_B,
+	const spsamd_vec *scalek, const spsamd_coo *M, int duplicate_policy, int zero_nan,
+	int sink_kind, int sink_flags, spsamd_result *res);
 
 // Select the output set the next result is written to: the current one unless a device operand lives in it.
 void pick_output_set(spsamd_ctx *c, const spsamd_coo *const *operands, int n);
