@@ -200,6 +200,10 @@ const char *spsamd_version(void);
  *   masked_path     1 | 2 | 3         multiply_masked: every mask key through the entry kernel (lane per key) | the row kernel
  *                                     wherever A_i fits its LDS copy (4096 tuples; the other keys: entry) | the wave kernel
  *                                     (wave per key) (default: by the lengths of A_i and B_j)
+ *   sampled_path    1 | 2             multiply_sampled: every tuple through the lane kernel (lane per tuple, rows read into
+ *                                     registers) | the slab kernel (wave per 64 tuples, rows staged through LDS in slabs of
+ *                                     16 values) (default: by k and a sampled probe of M's column locality and row
+ *                                     order)
  * The environment variables of the same purpose (SPSAMD_W ...) are read once, inside spsamd_ctx_create; nothing reads
  * the environment later.  Unknown names: SPSAMD_EINVAL. */
 int spsamd_ctx_set_tuning(spsamd_ctx *ctx, const char *name, long value);
@@ -290,6 +294,40 @@ int spsamd_multiply_dense(spsamd_ctx *ctx,
 	double *Y, size_t ldy,
 	size_t nrhs, int mem,
 	int duplicate_policy, int handle_nan);
+
+/*
+ * The sampled dense-dense product (SDDMM): for every tuple of M, the dot product of a row of P with a row of Q -- the
+ * dense-factor form of spsamd_multiply_masked.  For each tuple t of M IN STORAGE ORDER, as (i, j, v) -- (j, i, v) when
+ * transpose is the character 'T':
+ *     d = +0.0;   for r = 0 .. k-1:  d = d + P[i*ldp + r] * Q[j*ldq + r]      (serially, in ascending r)
+ *     o = alpha * d;   if (beta != 0)  o = o + beta * v;                      (beta == 0: v is never read)
+ *     out[t] = o
+ * Every out[t] is bit-identical to that loop: products and sums are rounded separately (no FMA), there is no tree or
+ * split sum over r, and a NaN result has the bits x86-64 gives it (the left operand's NaN, quieted, else the right one's,
+ * else 0xFFF8000000000000; the left operand is the one written on the left above), as in spsamd_multiply_dense.
+ *   P      rows(op(M)) rows of k values, row-major: P[i*ldp + r], ldp >= k
+ *   Q      cols(op(M)) rows of k values, row-major: Q[j*ldq + r], ldq >= k
+ *   out    one value per tuple of M, aligned with M's arrays (out[t] belongs to M's tuple t): M is NOT consolidated --
+ *          duplicates and explicit zeros each get their own output.  out == M->val is allowed (an in-place update of M's
+ *          values: each tuple's v is read before its slot is written).
+ *   mem    SPSAMD_MEM_HOST or SPSAMD_MEM_DEVICE, for P, Q and out together (M has its own `mem`)
+ * Gradient: for Y = op(M) * X (spsamd_multiply_dense) and G = dL/dY, the gradient of L with respect to M's values is this
+ * product with P = G, Q = X, alpha = 1, beta = 0.
+ * A prepared operand (SPSAMD_MEM_PREPARED) stands for its consolidated tuples, in the order spsamd_consolidate gives them
+ * for the transpose it was prepared with; out is aligned with those.  A SINK_COO result of this context may be M (read in
+ * place, its indices trusted); neither output set of the context is written, so it stays fetchable.
+ * SPSAMD_EINVAL, with out not written: M NULL; P or Q NULL while k > 0 and M has tuples; out NULL while M has tuples;
+ * M->val NULL while beta != 0; ldp < k or ldq < k; a bad mem; an index of M out of bounds; out overlapping P, Q or M's index
+ * arrays; out overlapping M->val without being equal to it (or overlapping a prepared operand's arrays); M with 2^31 or
+ * more tuples; a dimension of M above 2^31; k >= 2^31.  An empty M: 0, nothing touched.  k == 0: out[t] = alpha * 0 (+ beta * v); P and Q are not read.
+ * Index arithmetic is 64-bit (rows * ld may exceed 2^32 values).  Returns when out holds the result.
+ */
+int spsamd_multiply_sampled(spsamd_ctx *ctx,
+	const spsamd_coo *M, char transpose,
+	const double *P, size_t ldp,
+	const double *Q, size_t ldq,
+	size_t k, double alpha, double beta,
+	double *out, int mem);
 
 /*
  * ret = alpha * op(A) + beta * op(B)  -- sparse addition (rocSPARSE / cuSPARSE csrgeam).  The result is exactly what

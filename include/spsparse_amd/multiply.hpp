@@ -489,6 +489,22 @@ void multiply_dense(MatT const &M, const double *x, double *y, bool handle_nan =
 	if (rc != 0) (*spsparse_error)(-1, "%s", spsamd_last_error(ctx));
 }
 
+// ---- sampled dense-dense product (SDDMM) ----------------------------------------------------------------------------
+// out[t] = alpha * (P_i . Q_j) (+ beta * v when beta != 0) for every tuple t = (i, j, v) of op(M) in storage order, through
+// spsamd_multiply_sampled: the k terms of each tuple summed serially in ascending order, bit for bit.  Host pointers: P holds
+// rows(op(M)) rows of k values ldp apart, Q cols(op(M)) rows ldq apart, out M.size() values (it may be &M.val(0)).
+// transpose = true is the reference's 'T'.  The gradient of multiply_dense with respect to M's values: P = dL/dy, Q = x.
+template <class MatT>
+void multiply_sampled(MatT const &M, const double *P, size_t ldp, const double *Q, size_t ldq, size_t k, double *out,
+	double alpha = 1.0, double beta = 0.0, bool transpose = false)
+{
+	spsamd_coo m = detail::as_coo(M);
+	spsamd_ctx *ctx = default_context().get();
+	if (!ctx) return;
+	int rc = spsamd_multiply_sampled(ctx, &m, transpose ? 'T' : '.', P, ldp, Q, ldq, k, alpha, beta, out, SPSAMD_MEM_HOST);
+	if (rc != 0) (*spsparse_error)(-1, "%s", spsamd_last_error(ctx));
+}
+
 // ---- VectorCooArray::consolidate on the device ---------------------------
 template <class IndexT, class ValT, int RANK>
 void VectorCooArray<IndexT, ValT, RANK>::consolidate(std::array<int, RANK> const &_sort_order,

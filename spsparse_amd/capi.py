@@ -83,7 +83,8 @@ SYMBOLS = ["spsamd_ctx_create", "spsamd_ctx_destroy", "spsamd_last_error", "spsa
            "spsamd_gen_random_rows", "spsamd_gen_poisson2d", "spsamd_gen_laplace3d", "spsamd_gen_aggregation3d",
            "spsamd_dist_unique_id", "spsamd_dist_create", "spsamd_dist_destroy", "spsamd_dist_multiply",
            "spsamd_operand_prepare", "spsamd_operand_as_coo", "spsamd_operand_bytes", "spsamd_operand_destroy",
-           "spsamd_multiply_dense", "spsamd_add", "spsamd_multiply_stream", "spsamd_multiply_masked"]
+           "spsamd_multiply_dense", "spsamd_add", "spsamd_multiply_stream", "spsamd_multiply_masked",
+           "spsamd_multiply_sampled"]
 
 _lib = None
 
@@ -130,6 +131,8 @@ def load():
                                          P(StreamStats)]
     L.spsamd_multiply_masked.argtypes = [C.c_void_p, C.c_double, P(Vec), P(Coo), C.c_char, P(Vec), P(Coo), C.c_char, P(Vec),
                                          P(Coo), C.c_int, C.c_int, C.c_int, C.c_int, P(Result)]
+    L.spsamd_multiply_sampled.argtypes = [C.c_void_p, P(Coo), C.c_char, C.c_void_p, C.c_size_t, C.c_void_p, C.c_size_t,
+                                          C.c_size_t, C.c_double, C.c_double, C.c_void_p, C.c_int]
     L.spsamd_memcpy.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_size_t]
     L.spsamd_consolidate.argtypes = [C.c_void_p, P(Coo), C.c_int, C.c_int, C.c_int, P(Result)]
     L.spsamd_sorted_permutation.argtypes = [C.c_void_p, P(Coo), C.c_int, C.c_void_p]
@@ -344,6 +347,36 @@ class Context:
         self._check(self.L.spsamd_multiply_dense(self.h, C.byref(M), transpose.encode(), px, ldx, py, ldy, nx, mx,
                                                  duplicate_policy, int(handle_nan)))
         return Y
+
+    def multiply_sampled(self, M, P, Q, out=None, transpose='.', alpha=1.0, beta=0.0):
+        """spsamd_multiply_sampled: out[t] = alpha * (P[i] . Q[j]) (+ beta * v) for every tuple t = (i, j, v) of op(M) in
+        storage order, the k terms of each summed serially in ascending order, bit for bit.  M: a Coo struct.  P, Q: 2-D
+        float64 numpy arrays (host) or float64 torch tensors on this context's device, rows contiguous, with rows(op(M)) and
+        cols(op(M)) rows of k values; a 1-D P / Q means k = 1.  out: one float64 per tuple of M (1-D, contiguous, the same
+        kind as P and Q; it may be M's value array), allocated when None.  Returns out."""
+        (pp, ldp, kp, mp), (pq, ldq, kq, mq) = _dense_arg(P, "P", writable=False), _dense_arg(Q, "Q", writable=False)
+        if mp != mq:
+            raise ValueError("P and Q must both be host (numpy) or both device (torch) arrays")
+        if kp != kq:
+            raise ValueError("P has rows of %d values, Q of %d" % (kp, kq))
+        nrow, ncol = (M.shape1, M.shape0) if transpose == 'T' else (M.shape0, M.shape1)
+        if _rows(P) != nrow or _rows(Q) != ncol:
+            raise ValueError("P needs %d rows and Q %d rows for op(M) of shape (%d, %d)" % (nrow, ncol, nrow, ncol))
+        nnz = int(M.nnz)
+        if out is None:
+            if mp == MEM_HOST:
+                out = np.empty(nnz, dtype=np.float64)
+            else:
+                import torch
+                out = torch.empty(nnz, dtype=torch.float64, device=P.device)
+        po, _ldo, _n1, mo = _dense_arg(out, "out", writable=True)
+        if mo != mp:
+            raise ValueError("out must be the same kind of array as P and Q")
+        if out.ndim != 1 or int(out.shape[0]) != nnz or (nnz > 1 and _ldo != 1):
+            raise ValueError("out must be a contiguous 1-D array of %d values (one per tuple of M)" % nnz)
+        self._check(self.L.spsamd_multiply_sampled(self.h, C.byref(M), transpose.encode(), pp, ldp, pq, ldq, kp,
+                                                   float(alpha), float(beta), po, mp))
+        return out
 
     def to_host(self, dev_ptr, count, dtype):
         """numpy copy of `count` elements of device memory (spsamd_memcpy)."""
