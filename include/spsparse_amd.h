@@ -230,7 +230,8 @@ int spsamd_multiply(spsamd_ctx *ctx, double C,
 /*
  * ret = C * diag(scalei) * op(A) * diag(scalej) * V
  * -- spsparse::multiply, matrix x sparse vector (multiply_sparse.hpp:281-365).
- * V is consolidated with sort order {0} (:313).  The result is rank 1:
+ * V is consolidated with sort order {0} (:313); a V with sort0 == 0 is taken
+ * as stored, also under zero_nan (Consolidate<>, algorithm.hpp:360).  The result is rank 1:
  * result->idx0 holds the row indices, idx1 is NULL (spsamd_result_fetch then
  * passes j = NULL to the callback), shape1 is 0.
  */

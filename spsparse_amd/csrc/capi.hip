@@ -147,7 +147,7 @@ int spsamd::multiply_body(spsamd_ctx *c, double C,
 	const spsamd_vec *scalei, const spsamd_coo *A, char transpose_A,
 	const spsamd_vec *scalej, const spsamd_coo *B, char transpose_B,
 	const spsamd_vec *scalek, int duplicate_policy, int zero_nan,
-	int sink_kind, int sink_flags, spsamd_result *res, const char *what, bool arena_ready, const OperandParts *parts)
+	int sink_kind, int sink_flags, spsamd_result *res, const char *what, bool arena_ready, const OperandParts *parts, bool b_rank1)
 {
 	if (duplicate_policy < 0 || duplicate_policy > 2) throw Error{SPSAMD_EINVAL, "bad duplicate_policy"};
 	if (sink_kind != SPSAMD_SINK_COO && sink_kind != SPSAMD_SINK_DIGEST) throw Error{SPSAMD_EINVAL, "bad sink_kind"};
@@ -185,7 +185,8 @@ int spsamd::multiply_body(spsamd_ctx *c, double C,
 	// of the leading run of the reference's column-major sequence (:168), not of A's row-major one
 	// (a prepared operand is taken as it was prepared, like any operand that carries the wanted sort order)
 	if (a0 == bk && same_operand(A, B) && (!zero_nan || hp)) { a.B = a.A; if (a.pa) a.pb = a.pa; }
-	else { consolidate_operand(c, B, bk, bj, duplicate_policy, zero_nan, &a.B, &hp); if (hp) a.pb = hp; }  // :188
+	// (MV's V: Consolidate<VecT>(&V, {0}), :313 -- the reference's order is V's own, so a V that carries it is taken as stored)
+	else { consolidate_operand(c, B, bk, b_rank1 ? bk : bj, duplicate_policy, zero_nan, &a.B, &hp); if (hp) a.pb = hp; }  // :188
 	if (sink_kind == SPSAMD_SINK_COO) c->own[c->cur_out].sort0 = -1;           // that set is about to be overwritten
 	upload_scale(c, scalei, ashape[a0], "scalei", &a.si);
 	upload_scale(c, scalej, ashape[a1], "scalej", &a.sj);
@@ -297,7 +298,7 @@ extern "C" int spsamd_multiply_mv(spsamd_ctx *c, double C,
 			Vm.idx0 = vi; Vm.idx1 = vz; Vm.val = vv;
 		}
 		int rc = multiply_body(c, C, scalei, A, transpose_A, scalej, &Vm, '.', nullptr, duplicate_policy, zero_nan,
-			sink_kind, sink_flags & ~SPSAMD_SINK_PERMUTE, res, "V", true);     // a rank-1 result has nothing to permute
+			sink_kind, sink_flags & ~SPSAMD_SINK_PERMUTE, res, "V", true, nullptr, true);     // a rank-1 result has nothing to permute
 		res->shape1 = 0;                              // rank-1 result: ret.set_shape({rows}) (:295)
 		res->idx1 = nullptr;                          // ... with one index array: nothing to copy for a second one
 		return rc;

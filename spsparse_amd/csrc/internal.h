@@ -296,13 +296,14 @@ BTup *prepared_btup(spsamd_ctx *c, Prepared *p);               // its packed (co
 
 // Shared body of the MM and MV entry points (capi.hip); `arena_ready`: the caller has reset the workspace
 // and may hold operands in it (the distributed step does); `parts`: records of derived structures the caller already
-// has for A / B (the distributed step: its panel's row pointer, and the event that says the panel's tuples have arrived).
+// has for A / B (the distributed step: its panel's row pointer, and the event that says the panel's tuples have arrived);
+// `b_rank1`: B stands for a rank-1 array (MV's V as a k x 1 matrix), which the reference consolidates by its own order {0}.
 struct OperandParts { Prepared *pa = nullptr, *pb = nullptr; hipEvent_t b_ready = nullptr; };
 int multiply_body(spsamd_ctx *c, double C,
 	const spsamd_vec *scalei, const spsamd_coo *A, char transpose_A,
 	const spsamd_vec *scalej, const spsamd_coo *B, char transpose_B,
 	const spsamd_vec *scalek, int duplicate_policy, int zero_nan,
-	int sink_kind, int sink_flags, spsamd_result *res, const char *what, bool arena_ready, const OperandParts *parts = nullptr);
+	int sink_kind, int sink_flags, spsamd_result *res, const char *what, bool arena_ready, const OperandParts *parts = nullptr, bool b_rank1 = false);
 
 // ---------------------------------------------------------------- streamed product (k_stream.hip)
 
