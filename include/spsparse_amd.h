@@ -204,6 +204,11 @@ const char *spsamd_version(void);
  *                                     registers) | the slab kernel (wave per 64 tuples, rows staged through LDS in slabs of
  *                                     16 values) (default: by k and a sampled probe of M's column locality and row
  *                                     order)
+ *   select_path     1 | 2 | 3         select, ROW_TOPK: every row of more than k tuples through the light (a wave per row,
+ *                                     rows of at most 64 tuples) | mid (a workgroup per row, keys in LDS, at most 4096 tuples) |
+ *                                     heavy (a workgroup per row, keys re-read from memory) kernel wherever that kernel can
+ *                                     hold the row; a row too long for the forced class falls to the next one (default: by
+ *                                     row length)
  * The environment variables of the same purpose (SPSAMD_W ...) are read once, inside spsamd_ctx_create; nothing reads
  * the environment later.  Unknown names: SPSAMD_EINVAL. */
 int spsamd_ctx_set_tuning(spsamd_ctx *ctx, const char *name, long value);
@@ -360,6 +365,57 @@ int spsamd_add(spsamd_ctx *ctx,
 	int duplicate_policy, int zero_nan,
 	int sink_kind, int sink_flags,
 	spsamd_result *result);
+
+/*
+ * ret = the tuples of op(A) that a predicate keeps  -- dropping entries (rocSPARSE / cuSPARSE prune_csr2csr, GraphBLAS
+ * GrB_select).  No value is computed: the result is a subsequence of op(A)'s tuples.
+ *   - Operand.  op(A) (indices swapped exactly when transpose is the character 'T') is taken the way spsamd_multiply takes
+ *     its left operand, with duplicate_policy and zero_nan: a raw operand is consolidated by op()'s rows (stable sort,
+ *     leading-run rule, zero drop, duplicates folded by the policy); an operand whose sort0 names op()'s row order is
+ *     trusted as stored (duplicates, zeros and the order inside a row included) and rejected (SPSAMD_EINVAL) if its leading
+ *     index descends; a SINK_COO result of this context and a prepared handle of the same transpose are read in place; a
+ *     prepared handle of the other transpose is re-sorted.  Host and device operands.  Call the resulting sequence S.  The
+ *     result is a SUBSEQUENCE of S: order kept, values bit for bit untouched (NaN payloads, signalling NaNs, -0.0 included).
+ *   - mag(x) is the 64-bit pattern of x with the sign bit cleared, compared as an unsigned integer.  For non-NaN values that
+ *     is the order of |x|; every NaN ranks above +Inf (by payload).  All three value predicates compare through it, so a NaN
+ *     entry is never dropped by a value predicate and counts as the largest in a top-k.  No floating-point comparison
+ *     decides an entry's fate.
+ *   - TRIL / TRIU / DIAG / OFFDIAG use j - i in 64-bit arithmetic on op(A)'s indices; d = iparam may be any int64.
+ *   - ABS_GE: theta = dparam must be >= 0 and not NaN (+Inf allowed: only Inf and NaN entries stay).
+ *   - ROW_REL: m_i is the largest |v| over the non-NaN entries of row i of S (+0.0 when there are none); the threshold
+ *     t_i = theta * m_i is one rounded double multiply (0 * Inf gives a NaN threshold: then only NaN entries whose mag is at
+ *     or above it pass -- the rule above, nothing special-cased).  theta >= 0, not NaN.  theta = 0 with finite rows keeps S.
+ *   - ROW_TOPK: k = iparam >= 0.  Within a row of S the tuples are ranked by (mag descending, position in S ascending);
+ *     those of rank < k are kept.  In a consolidated row positions ascend with the column, so ties at the k-th magnitude
+ *     go to the lowest columns; for a trusted operand the order is the stored one.  k = 0: empty result; a row of at most
+ *     k tuples is kept whole.  Column-wise top-k is transpose = 'T' plus SPSAMD_SINK_PERMUTE.
+ *   - SPSAMD_SELECT_COMPLEMENT inverts the decision per tuple, for every predicate (top-k: the tuples of rank >= k).
+ *     For any input, predicate and parameters, select and its complement partition S.
+ * Sinks as for spsamd_add: SINK_COO (tuples in the context's output set, fetchable, usable with
+ * spsamd_result_scatter_dense, chainable as a MEM_DEVICE sort0 = 0 operand -- sort0 = 1 with SINK_PERMUTE), SINK_DIGEST
+ * (+ ROWSTATS over rows(op(A)): row_nnz is the number of kept tuples per row); SINK_ORDERED and SINK_EXACT_PATTERN are
+ * accepted and change nothing.  The operand may be the context's current output set (filtering a product in a chain):
+ * the result goes to the other set.
+ * result: shape, nnz, nnz_a (= |S|), ms_consolidate, ms_numeric, ms_total, workspace_bytes; for ROW_TOPK also
+ * rows_light / rows_mid / rows_heavy and tuples_light / tuples_mid / tuples_heavy: the rows of S with more than k tuples,
+ * and their tuples, by the kernel class that served them (rows of at most k tuples are in none).  Everything else 0 / NULL.
+ * SPSAMD_EINVAL: A or result NULL, an unknown predicate, select_flags or sink, a policy outside 0..2, theta < 0 or NaN,
+ * k < 0, an index out of bounds, 2^31 or more tuples.  An empty A: an empty result of op(A)'s shape.  Returns when the
+ * result is complete.
+ */
+#define SPSAMD_SELECT_TRIL     1   /* keep (i, j) with  j - i <= d          d = iparam (int64, any sign)            */
+#define SPSAMD_SELECT_TRIU     2   /*                   j - i >= d                                                  */
+#define SPSAMD_SELECT_DIAG     3   /*                   j - i == d                                                  */
+#define SPSAMD_SELECT_OFFDIAG  4   /*                   j - i != d                                                  */
+#define SPSAMD_SELECT_ABS_GE   5   /* keep v with  mag(v) >= mag(theta)            theta = dparam                   */
+#define SPSAMD_SELECT_ROW_REL  6   /* keep v with  mag(v) >= mag(theta * m_i)      m_i: the row's largest non-NaN |v| */
+#define SPSAMD_SELECT_ROW_TOPK 7   /* keep the k first tuples of each row in the order (mag descending, position ascending)  k = iparam */
+#define SPSAMD_SELECT_COMPLEMENT 1 /* select_flags: keep exactly the tuples the predicate would drop                */
+
+int spsamd_select(spsamd_ctx *ctx, const spsamd_coo *A, char transpose,
+	int predicate, int64_t iparam, double dparam, int select_flags,
+	int duplicate_policy, int zero_nan,
+	int sink_kind, int sink_flags, spsamd_result *result);
 
 /*
  * ret = (C * diag(scalei) * op(A) * diag(scalej) * op(B) * diag(scalek)) restricted to the keys of M  -- a masked product

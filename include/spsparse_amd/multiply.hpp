@@ -505,6 +505,28 @@ void multiply_sampled(MatT const &M, const double *P, size_t ldp, const double *
 	if (rc != 0) (*spsparse_error)(-1, "%s", spsamd_last_error(ctx));
 }
 
+// ---- dropping entries ----------------------------------------------------------------------------------------------
+// ret receives the tuples of op(A) that a SPSAMD_SELECT_* predicate keeps (spsamd_select: TRIL / TRIU / DIAG / OFFDIAG with
+// the diagonal in iparam, ABS_GE / ROW_REL with theta in dparam, ROW_TOPK with k in iparam; select_flags =
+// SPSAMD_SELECT_COMPLEMENT for the tuples it drops), in op(A)'s row order, values bit for bit as stored.  op(A) is taken
+// like multiply's left operand: consolidated with duplicate_policy and zero_nan unless it carries op()'s sort order.
+template <class MatT, class AccumulatorT>
+void select(AccumulatorT &ret, MatT const &A, char transpose, int predicate, int64_t iparam = 0, double dparam = 0.0,
+	int select_flags = 0, DuplicatePolicy duplicate_policy = DuplicatePolicy::ADD, bool zero_nan = false)
+{
+	std::array<int, 2> const &a_sort_order(transpose == 'T' ? COL_MAJOR : ROW_MAJOR);
+	ret.set_shape({A.shape[a_sort_order[0]], A.shape[a_sort_order[1]]});
+	spsamd_coo a = detail::as_coo(A);
+	spsamd_ctx *ctx = default_context().get();
+	if (!ctx) return;
+	spsamd_result res;
+	int rc = spsamd_select(ctx, &a, transpose, predicate, iparam, dparam, select_flags, (int)duplicate_policy, zero_nan ? 1 : 0,
+		SPSAMD_SINK_COO, 0, &res);
+	if (rc != 0) { (*spsparse_error)(-1, "%s", spsamd_last_error(ctx)); return; }
+	rc = spsamd_result_fetch(ctx, &res, &detail::add_chunk<AccumulatorT>, &ret);
+	if (rc != 0) (*spsparse_error)(-1, "%s", spsamd_last_error(ctx));
+}
+
 // ---- VectorCooArray::consolidate on the device ---------------------------
 template <class IndexT, class ValT, int RANK>
 void VectorCooArray<IndexT, ValT, RANK>::consolidate(std::array<int, RANK> const &_sort_order,

@@ -21,6 +21,10 @@ SINK_ROWSTATS = 1
 SINK_ORDERED = 2
 SINK_PERMUTE = 4
 SINK_EXACT_PATTERN = 8
+SELECT_TRIL, SELECT_TRIU, SELECT_DIAG, SELECT_OFFDIAG, SELECT_ABS_GE, SELECT_ROW_REL, SELECT_ROW_TOPK = 1, 2, 3, 4, 5, 6, 7
+SELECT_COMPLEMENT = 1
+# ROW_TOPK: the longest row of the light (a wave per row) and of the mid (a workgroup per row, keys in LDS) kernel class
+select_light_max, select_mid_max = 64, 4096
 
 ERRORS = {-1: "EDIM", -2: "EINVAL", -3: "EHIP", -4: "ENOMEM", -5: "ECAPACITY", -6: "ENODEVICE", -7: "EPEER"}
 
@@ -84,7 +88,7 @@ SYMBOLS = ["spsamd_ctx_create", "spsamd_ctx_destroy", "spsamd_last_error", "spsa
            "spsamd_dist_unique_id", "spsamd_dist_create", "spsamd_dist_destroy", "spsamd_dist_multiply",
            "spsamd_operand_prepare", "spsamd_operand_as_coo", "spsamd_operand_bytes", "spsamd_operand_destroy",
            "spsamd_multiply_dense", "spsamd_add", "spsamd_multiply_stream", "spsamd_multiply_masked",
-           "spsamd_multiply_sampled"]
+           "spsamd_multiply_sampled", "spsamd_select"]
 
 _lib = None
 
@@ -133,6 +137,8 @@ def load():
                                          P(Coo), C.c_int, C.c_int, C.c_int, C.c_int, P(Result)]
     L.spsamd_multiply_sampled.argtypes = [C.c_void_p, P(Coo), C.c_char, C.c_void_p, C.c_size_t, C.c_void_p, C.c_size_t,
                                           C.c_size_t, C.c_double, C.c_double, C.c_void_p, C.c_int]
+    L.spsamd_select.argtypes = [C.c_void_p, P(Coo), C.c_char, C.c_int, C.c_int64, C.c_double, C.c_int, C.c_int, C.c_int,
+                                C.c_int, C.c_int, P(Result)]
     L.spsamd_memcpy.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_size_t]
     L.spsamd_consolidate.argtypes = [C.c_void_p, P(Coo), C.c_int, C.c_int, C.c_int, P(Result)]
     L.spsamd_sorted_permutation.argtypes = [C.c_void_p, P(Coo), C.c_int, C.c_void_p]
@@ -287,6 +293,18 @@ class Context:
         res = Result()
         rc = self.L.spsamd_add(self.h, float(alpha), C.byref(A), tA.encode(), float(beta), C.byref(B), tB.encode(),
                                duplicate_policy, int(zero_nan), sink, flags, C.byref(res))
+        self._check(rc)
+        return res
+
+    def select(self, A, predicate, iparam=0, dparam=0.0, complement=False, transpose='.', duplicate_policy=ADD,
+               zero_nan=False, sink=SINK_COO, flags=0):
+        """spsamd_select: the tuples of op(A) that a SELECT_* predicate keeps (its complement: those it drops), in
+        op(A)'s order, values untouched.  iparam: the diagonal d of TRIL / TRIU / DIAG / OFFDIAG or the k of ROW_TOPK;
+        dparam: the theta of ABS_GE / ROW_REL.  A: a Coo struct."""
+        res = Result()
+        rc = self.L.spsamd_select(self.h, C.byref(A), transpose.encode(), int(predicate), int(iparam), float(dparam),
+                                  SELECT_COMPLEMENT if complement else 0, duplicate_policy, int(zero_nan), sink, flags,
+                                  C.byref(res))
         self._check(rc)
         return res
 

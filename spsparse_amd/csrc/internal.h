@@ -95,6 +95,7 @@ struct Tuning {
 	int add_path = 0;            // add: 0 auto | 1 sort every operand (ignore sort0, chained results and preparation)
 	int masked_path = 0;         // multiply_masked: 0 auto | 1 entry kernel for every key | 2 row kernel wherever A_i fits LDS | 3 wave kernel for every key
 	int sampled_path = 0;        // multiply_sampled: 0 auto | 1 lane kernel for every tuple | 2 slab kernel for every tuple (auto: by k and a probe of M's order)
+	int select_path = 0;         // select, ROW_TOPK: 0 by row length | 1 light | 2 mid | 3 heavy kernel for every row it can hold
 #ifdef SPSAMD_ABLATIONS
 	int dbg = 0;
 #endif
@@ -352,6 +353,12 @@ void multiply_masked(spsamd_ctx *c, double C,
 // out[t] = alpha * (P_i . Q_j) (+ beta * v) for every tuple (i, j, v) of op(M): spsamd_multiply_sampled after the context check
 void multiply_sampled(spsamd_ctx *c, const spsamd_coo *M, char transpose, const double *P, size_t ldp, const double *Q,
 	size_t ldq, size_t k, double alpha, double beta, double *out, int mem);
+
+// ---------------------------------------------------------------- dropping entries (k_select.hip)
+
+// the tuples of op(A) a predicate keeps, into the sink: spsamd_select after its null checks
+void select_tuples(spsamd_ctx *c, const spsamd_coo *A, char transpose, int predicate, int64_t iparam, double dparam,
+	int select_flags, int duplicate_policy, int zero_nan, int sink_kind, int sink_flags, spsamd_result *res);
 
 // Select the output set the next result is written to: the current one unless a device operand lives in it.
 void pick_output_set(spsamd_ctx *c, const spsamd_coo *const *operands, int n);
