@@ -118,23 +118,6 @@ extern "C" int spsamd_ctx_reserve(spsamd_ctx *c, size_t workspace_bytes, size_t 
 	)
 }
 
-bool spsamd::output_set_aliased(const spsamd_ctx *c, int s, const spsamd_coo *const *operands, int n)
-{
-	for (int k = 0; k < n; ++k) {
-		const spsamd_coo *X = operands[k];
-		if (X && X->mem == SPSAMD_MEM_DEVICE && (c->out[s].holds(X->idx0) || c->out[s].holds(X->idx1) || c->out[s].holds(X->val))) return true;
-	}
-	return false;
-}
-
-void spsamd::pick_output_set(spsamd_ctx *c, const spsamd_coo *const *operands, int n)
-{
-	if (!output_set_aliased(c, c->cur_out, operands, n)) return;
-	if (output_set_aliased(c, c->cur_out ^ 1, operands, n))
-		throw Error{SPSAMD_EINVAL, "both result buffers of this context are operands of the call: copy one of them out first (spsamd_memcpy)"};
-	c->cur_out ^= 1;
-}
-
 bool spsamd::same_operand(const spsamd_coo *a, const spsamd_coo *b)
 {
 	return a->idx0 == b->idx0 && a->idx1 == b->idx1 && a->val == b->val && a->nnz == b->nnz &&
@@ -152,22 +135,12 @@ int spsamd::multiply_body(spsamd_ctx *c, double C,
 	if (duplicate_policy < 0 || duplicate_policy > 2) throw Error{SPSAMD_EINVAL, "bad duplicate_policy"};
 	if (sink_kind != SPSAMD_SINK_COO && sink_kind != SPSAMD_SINK_DIGEST) throw Error{SPSAMD_EINVAL, "bad sink_kind"};
 	std::memset(res, 0, sizeof(*res));
-	// multiply_sparse.hpp:167-169: op(A) rows = A.shape[a0]; op(B) is read by ROWS here
-	// (inner index first), its columns are B.shape[bj]
-	const int a0 = transpose_A == 'T' ? 1 : 0, a1 = 1 - a0;
-	const int bk = transpose_B == 'T' ? 1 : 0, bj = 1 - bk;
-	const size_t ashape[2] = {A->shape0, A->shape1}, bshape[2] = {B->shape0, B->shape1};
 	const bool permute = (sink_flags & SPSAMD_SINK_PERMUTE) && sink_kind == SPSAMD_SINK_COO;
-	res->shape0 = permute ? bshape[bj] : ashape[a0];
-	res->shape1 = permute ? ashape[a0] : bshape[bj];
-	if (ashape[a1] != bshape[bk]) {                                  // :172-174
-		char buf[160];
-		std::snprintf(buf, sizeof buf, "Inner dimensions for A (%ld) and %s (%ld) must match!", (long)ashape[a1], what, (long)bshape[bk]);
-		throw Error{SPSAMD_EDIM, buf};
-	}
-	if (C == 0 || (scalei && scalei->nnz == 0) || A->nnz == 0 || (scalej && scalej->nnz == 0) ||
-		B->nnz == 0 || (scalek && scalek->nnz == 0))                 // :178-184
-		return SPSAMD_OK;
+	const ProductFrame f(A, transpose_A, B, transpose_B, permute);
+	const int a0 = f.a0, bk = f.bk, bj = f.bj;
+	res->shape0 = f.shape0; res->shape1 = f.shape1;
+	f.check_inner(what);
+	if (product_is_empty(C, scalei, A, scalej, B, scalek)) return SPSAMD_OK;
 
 	SPS_HIP(hipSetDevice(c->device));
 	if (!arena_ready) c->arena.reset();
@@ -188,24 +161,16 @@ int spsamd::multiply_body(spsamd_ctx *c, double C,
 	// (MV's V: Consolidate<VecT>(&V, {0}), :313 -- the reference's order is V's own, so a V that carries it is taken as stored)
 	else { consolidate_operand(c, B, bk, b_rank1 ? bk : bj, duplicate_policy, zero_nan, &a.B, &hp); if (hp) a.pb = hp; }  // :188
 	if (sink_kind == SPSAMD_SINK_COO) c->own[c->cur_out].sort0 = -1;           // that set is about to be overwritten
-	upload_scale(c, scalei, ashape[a0], "scalei", &a.si);
-	upload_scale(c, scalej, ashape[a1], "scalej", &a.sj);
-	upload_scale(c, scalek, bshape[bj], "scalek", &a.sk);
+	upload_scale(c, scalei, f.nrow, "scalei", &a.si);
+	upload_scale(c, scalej, f.inner, "scalej", &a.sj);
+	upload_scale(c, scalek, f.ncol, "scalek", &a.sk);
 	spgemm(c, a, res);
-	if (sink_kind == SPSAMD_SINK_COO && res->idx0 && res->idx1) {
-		// row-major sorted, every (i, j) once, no zero: consolidated by sort order {0, 1} (read permuted: by {1, 0})
-		auto &o = c->own[c->cur_out];
-		o.d0 = permute ? res->idx1 : res->idx0; o.d1 = permute ? res->idx0 : res->idx1; o.v = res->val; o.nnz = res->nnz;
-		o.shape0 = res->shape0; o.shape1 = res->shape1; o.sort0 = permute ? 1 : 0;
-	}
-	if (permute) std::swap(res->idx0, res->idx1);                             // PermuteAccum {1,0}: same tuples, indices swapped
-	SPS_HIP(hipEventRecord(c->ev[7], st));
-	SPS_HIP(hipEventSynchronize(c->ev[7]));
+	// (spgemm grew the output set itself and stored there; no tuples: nothing to hand over, and nothing to swap)
+	if (sink_kind == SPSAMD_SINK_COO && res->idx0 && res->idx1) publish_coo(c, res, res->idx0, res->idx1, res->val, res->nnz, permute);
+	finish_call(c, res);
 	if (res->nnz_a && res->nnz_b) {
 		SPS_HIP(hipEventElapsedTime(&res->ms_consolidate, c->ev[0], c->ev[1]));
 	}
-	SPS_HIP(hipEventElapsedTime(&res->ms_total, c->ev[0], c->ev[7]));
-	res->workspace_bytes = c->arena.call_used;
 	return SPSAMD_OK;
 }
 
@@ -396,19 +361,6 @@ extern "C" void spsamd_operand_destroy(spsamd_operand *h)
 	delete h;
 }
 
-// The stand-alone algorithms read an operand's arrays themselves: a prepared operand is handed to them as the device
-// COO it holds (sorted by its lead).
-static const spsamd_coo *plain_operand(spsamd_ctx *c, const spsamd_coo *X, spsamd_coo *tmp)
-{
-	if (!X || X->mem != SPSAMD_MEM_PREPARED) return X;
-	const spsamd_operand *h = (const spsamd_operand *)X->idx0;
-	if (!h || h->p.ctx != c) throw Error{SPSAMD_EINVAL, "a prepared operand belongs to the context that prepared it"};
-	const Prepared &p = h->p;
-	tmp->idx0 = p.lead == 0 ? p.m.row : p.m.col; tmp->idx1 = p.lead == 0 ? p.m.col : p.m.row; tmp->val = p.m.val;
-	tmp->nnz = p.m.nnz; tmp->shape0 = h->shape0; tmp->shape1 = h->shape1; tmp->sort0 = p.lead; tmp->mem = SPSAMD_MEM_DEVICE;
-	return tmp;
-}
-
 extern "C" int spsamd_result_fetch(spsamd_ctx *c, const spsamd_result *res, spsamd_chunk_fn cb, void *user)
 {
 	if (!c) return SPSAMD_EINVAL;
@@ -494,8 +446,8 @@ extern "C" int spsamd_multiply_dense(spsamd_ctx *c, const spsamd_coo *M, char tr
 		const uint64_t ybytes = nrow && nrhs ? ((nrow - 1) * ldy + nrhs) * sizeof(double) : 0;
 		if (xbytes && ybytes && (const char *)X < (const char *)Y + ybytes && (const char *)Y < (const char *)X + xbytes)
 			throw Error{SPSAMD_EINVAL, "X and Y overlap"};
-		const bool empty = M->mem == SPSAMD_MEM_PREPARED ? !M->idx0 || ((const spsamd_operand *)M->idx0)->p.m.nnz == 0 : M->nnz == 0;
-		if (!nrhs || empty) return SPSAMD_OK;
+		// (the unchecked count: a null prepared handle is an empty M here, as it always was; dense_operand checks the handle)
+		if (!nrhs || operand_tuples(M) == 0) return SPSAMD_OK;
 		SPS_HIP(hipSetDevice(c->device));
 		c->arena.reset();
 		DenseOperand m;
@@ -561,8 +513,9 @@ extern "C" int spsamd_consolidate(spsamd_ctx *c, const spsamd_coo *A, int so0, i
 	API_GUARD(c,
 		if (!A || !res || (so0 != 0 && so0 != 1)) throw Error{SPSAMD_EINVAL, "bad argument"};
 		if (duplicate_policy < 0 || duplicate_policy > 2) throw Error{SPSAMD_EINVAL, "bad duplicate_policy"};
-		spsamd_coo plain;
-		A = plain_operand(c, A, &plain);
+		// (the stand-alone algorithms read an operand's arrays themselves: a prepared one as the device COO it holds)
+		const OperandView view = operand_view(c, A);
+		A = &view.coo;
 		std::memset(res, 0, sizeof(*res));
 		res->shape0 = A->shape0; res->shape1 = A->shape1;
 		if (A->nnz == 0) return SPSAMD_OK;
@@ -575,18 +528,14 @@ extern "C" int spsamd_consolidate(spsamd_ctx *c, const spsamd_coo *A, int so0, i
 		size_t n = m.nnz;
 		const spsamd_coo *ops[1] = {A};
 		pick_output_set(c, ops, 1);
-		OutSet &o = c->out[c->cur_out];
-		c->own[c->cur_out].sort0 = -1;
-		o.i.ensure(n * 4 + 4); o.j.ensure(n * 4 + 4); o.v.ensure(n * 8 + 8);
-		// m.row is the leading (sorted) dimension: put dimensions back in place
-		int32_t *d0 = (int32_t *)o.i.p, *d1 = (int32_t *)o.j.p;
-		SPS_HIP(hipMemcpyAsync(so0 == 0 ? d0 : d1, m.row, n * 4, hipMemcpyDeviceToDevice, c->stream));
-		SPS_HIP(hipMemcpyAsync(so0 == 0 ? d1 : d0, m.col, n * 4, hipMemcpyDeviceToDevice, c->stream));
-		SPS_HIP(hipMemcpyAsync(o.v.p, m.val, n * 8, hipMemcpyDeviceToDevice, c->stream));
+		const CooOut o = coo_output(c, n);
+		SPS_HIP(hipMemcpyAsync(o.row, m.row, n * 4, hipMemcpyDeviceToDevice, c->stream));
+		SPS_HIP(hipMemcpyAsync(o.col, m.col, n * 4, hipMemcpyDeviceToDevice, c->stream));
+		SPS_HIP(hipMemcpyAsync(o.val, m.val, n * 8, hipMemcpyDeviceToDevice, c->stream));
 		SPS_HIP(hipStreamSynchronize(c->stream));
-		res->nnz = n; res->nnz_a = n;
-		res->idx0 = d0; res->idx1 = d1; res->val = (double *)o.v.p;
-		{ auto &w = c->own[c->cur_out]; w.d0 = d0; w.d1 = d1; w.v = res->val; w.nnz = n; w.shape0 = A->shape0; w.shape1 = A->shape1; w.sort0 = so0; }
+		res->nnz_a = n;
+		// m.row is the leading (sorted) dimension: so0 == 1 is the permuted reading, which puts the dimensions back in place
+		publish_coo(c, res, o.row, o.col, o.val, n, so0 == 1);
 		return SPSAMD_OK;
 	)
 }
@@ -597,8 +546,8 @@ extern "C" int spsamd_sorted_permutation(spsamd_ctx *c, const spsamd_coo *A, int
 	API_GUARD(c,
 		if (!A || (so0 != 0 && so0 != 1) || (A->nnz && !perm_host)) throw Error{SPSAMD_EINVAL, "bad argument"};
 		if (A->nnz == 0) return SPSAMD_OK;
-		spsamd_coo plain;
-		A = plain_operand(c, A, &plain);
+		const OperandView view = operand_view(c, A);
+		A = &view.coo;
 		SPS_HIP(hipSetDevice(c->device));
 		c->arena.reset();
 		uint32_t *perm = sorted_permutation(c, A, so0);
@@ -615,8 +564,8 @@ extern "C" int spsamd_dim_beginnings(spsamd_ctx *c, const spsamd_coo *A, int so0
 	if (!c) return SPSAMD_EINVAL;
 	API_GUARD(c,
 		if (!A || !count || (so0 != 0 && so0 != 1)) throw Error{SPSAMD_EINVAL, "bad argument"};
-		spsamd_coo plain;
-		A = plain_operand(c, A, &plain);
+		const OperandView view = operand_view(c, A);
+		A = &view.coo;
 		if (A->sort0 != so0) throw Error{SPSAMD_EINVAL, "dim_beginnings() required the VectorCooArray is sorted first."};
 		*count = 0;
 		if (A->nnz == 0) return SPSAMD_OK;                         // algorithm.hpp:89

@@ -11,14 +11,6 @@
 
 namespace spsamd {
 
-static int bits_for(uint64_t dim)
-{
-	// bits needed to hold indices 0 .. dim-1
-	int b = 0;
-	while (b < 63 && (uint64_t(1) << b) < dim) ++b;
-	return b;
-}
-
 // flags: bit0 = an index is out of [0, shape); bit1 = not (strictly sorted, no zero values); bit2 = not strictly in
 // (minor, major) order; bit3 = holds a value consolidate() may drop; bit4 = the major index descends somewhere; bit5 = the
 // (major, minor) key descends somewhere (not even non-decreasing: duplicates allowed)
@@ -52,12 +44,6 @@ __global__ void k_inspect(const int32_t *major, const int32_t *minor, const doub
 	if (wf && lane_id() == 0) atomicOr(&s_f, wf);
 	__syncthreads();
 	if (threadIdx.x == 0 && s_f && (*(volatile uint32_t *)flags & s_f) != s_f) atomicOr(flags, s_f);
-}
-
-__global__ void k_build_keys(const int32_t *major, const int32_t *minor, size_t n, int minor_bits, uint64_t *keys)
-{
-	size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
-	if (i < n) keys[i] = ((uint64_t)(uint32_t)major[i] << minor_bits) | (uint64_t)(uint32_t)minor[i];
 }
 
 // Gather the values into sorted order and flag the tuples consolidate() keeps:
@@ -146,29 +132,6 @@ __global__ void k_merge(const uint64_t *kk, const double *kv, const uint8_t *hea
 	val[o] = acc;
 }
 
-// An operand with nothing to drop and nothing to merge: the sorted tuples are the consolidated ones.
-__global__ void k_gather_sorted(const uint64_t *keys, const uint32_t *perm, const double *val, size_t n, int minor_bits,
-	int32_t *row, int32_t *col, double *oval)
-{
-	size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
-	if (i >= n) return;
-	const uint64_t key = keys[i];
-	row[i] = (int32_t)(key >> minor_bits);
-	col[i] = (int32_t)(key & ((uint64_t(1) << minor_bits) - 1));
-	oval[i] = val[perm[i]];
-}
-
-static unsigned grid_for(size_t n, unsigned bs = 256) { return (unsigned)((n + bs - 1) / bs); }
-
-template <class T>
-static const T *to_device(spsamd_ctx *c, const T *p, size_t n, int mem)
-{
-	if (mem != SPSAMD_MEM_HOST || n == 0) return p;
-	T *d = c->arena.get<T>(n);
-	SPS_HIP(hipMemcpyAsync(d, p, n * sizeof(T), hipMemcpyHostToDevice, c->stream));
-	return d;
-}
-
 __global__ void k_min_key(unsigned long long *first_key, const unsigned long long *global_key)
 {
 	if (*global_key < *first_key) *first_key = *global_key;
@@ -190,21 +153,12 @@ void consolidate_operand(spsamd_ctx *c, const spsamd_coo *X, int lead, int ref_l
 	Prepared **prep, const unsigned long long *global_first_key)
 {
 	if (prep) *prep = nullptr;
-	if (X->mem == SPSAMD_MEM_PREPARED) {
-		// a prepared operand (spsamd_operand_prepare): consolidated once, by the lead it was prepared for.  Used the other way
-		// round ('T' now, '.' then) its tuples are an ordinary device operand sorted by the other dimension.
-		Prepared *p = (Prepared *)const_cast<int32_t *>(X->idx0);
-		if (!p || p->ctx != c) throw Error{SPSAMD_EINVAL, "a prepared operand belongs to the context that prepared it"};
-		if (p->lead == lead) { *out = p->m; if (prep) *prep = p; return; }
-		spsamd_coo Y;
-		Y.idx0 = p->lead == 0 ? p->m.row : p->m.col; Y.idx1 = p->lead == 0 ? p->m.col : p->m.row; Y.val = p->m.val;
-		Y.nnz = p->m.nnz; Y.shape0 = X->shape0; Y.shape1 = X->shape1; Y.sort0 = p->lead; Y.mem = SPSAMD_MEM_DEVICE;
-		consolidate_operand(c, &Y, lead, ref_lead, duplicate_policy, zero_nan, out, nullptr, global_first_key);
-		return;
-	}
+	// a prepared operand of this lead is the consolidated operand; of the other lead, a device operand sorted the other way
+	const OperandView view = operand_view(c, X);
+	if (view.prep && view.prep->lead == lead) { *out = view.prep->m; if (prep) *prep = view.prep; return; }
+	X = &view.coo;
+	check_operand(*X, OPERAND_VALUES);
 	size_t n = X->nnz;
-	if (n >= (size_t(1) << 31))
-		throw Error{SPSAMD_EINVAL, "operand has 2^31 or more tuples (the reference's int positions cap it too, algorithm.hpp:419)"};
 	uint64_t shape[2] = {X->shape0, X->shape1};
 	out->nrow = shape[lead];
 	out->ncol = shape[1 - lead];
@@ -212,15 +166,10 @@ void consolidate_operand(spsamd_ctx *c, const spsamd_coo *X, int lead, int ref_l
 	out->row = out->col = nullptr;
 	out->val = nullptr;
 	if (n == 0) return;
-	if (!X->idx0 || !X->idx1 || !X->val) throw Error{SPSAMD_EINVAL, "operand with nnz > 0 has a null array"};
-	if (shape[0] > (uint64_t(1) << 31) || shape[1] > (uint64_t(1) << 31))
-		throw Error{SPSAMD_EINVAL, "shape exceeds the int32 index range"};
 
-	bool own_result = false;                                            // a result of this context, chained back in as it stands
-	if (X->mem == SPSAMD_MEM_DEVICE && X->sort0 == lead)
-		for (const auto &o : c->own)
-			if (o.sort0 == X->sort0 && o.d0 == X->idx0 && o.d1 == X->idx1 && o.v == X->val && o.nnz == n && o.shape0 == X->shape0 && o.shape1 == X->shape1) own_result = true;
-	if ((X->mem == SPSAMD_MEM_DEVICE_VERIFIED || own_result) && X->sort0 == lead) {       // the distributed step's own block / panel
+	// a result of this context, chained back in as it stands; the distributed step's own block / panel
+	// (this test never asked for o.sort0 >= 0 as is_own_result does: under sort0 == lead it holds anyway)
+	if (X->sort0 == lead && (X->mem == SPSAMD_MEM_DEVICE_VERIFIED || is_own_result(c, *X))) {
 		out->row = const_cast<int32_t *>(lead == 0 ? X->idx0 : X->idx1);
 		out->col = const_cast<int32_t *>(lead == 0 ? X->idx1 : X->idx0);
 		out->val = const_cast<double *>(X->val);
@@ -257,11 +206,10 @@ void consolidate_operand(spsamd_ctx *c, const spsamd_coo *X, int lead, int ref_l
 		return;
 	}
 
-	int mb = bits_for(out->ncol), Mb = bits_for(out->nrow);
+	int mb = bits_of(out->ncol), Mb = bits_of(out->nrow);
 	uint64_t *keys0 = c->arena.get<uint64_t>(n), *keys1 = c->arena.get<uint64_t>(n);
 	uint32_t *pay0 = c->arena.get<uint32_t>(n), *pay1 = c->arena.get<uint32_t>(n);
-	k_build_keys<<<dim3(grid_for(n)), dim3(256), 0, c->stream>>>(major, minor, n, mb, keys0);
-	SPS_LAUNCH_CHECK();
+	build_keys(c, major, minor, n, mb, keys0);
 	// An operand that is STRICTLY in (minor, major) order -- a matrix kept sorted by rows and used with 'T', cfg5's R -- needs
 	// the stable passes over the MAJOR digits only: an LSD sort that skips the low digits leaves ties in input order, which is
 	// the minor order already (Galerkin 256^3, R^T: 3 passes instead of 6).  Strictly: no two tuples share their indices, so
@@ -271,12 +219,11 @@ void consolidate_operand(spsamd_ctx *c, const spsamd_coo *X, int lead, int ref_l
 	uint64_t *ks = where ? keys1 : keys0;
 	uint32_t *ps = where ? pay1 : pay0;
 	uint64_t *kk = where ? keys0 : keys1;      // the other key buffer is free now
-	if (!(f & 4u) && !(f & 8u)) {
+	if (!(f & 4u) && !(f & 8u)) {                  // nothing to drop and nothing to merge: the sorted tuples are the consolidated ones
 		out->row = c->arena.get<int32_t>(n);
 		out->col = c->arena.get<int32_t>(n);
 		out->val = c->arena.get<double>(n);
-		k_gather_sorted<<<dim3(grid_for(n)), dim3(256), 0, c->stream>>>(ks, ps, dv, n, mb, out->row, out->col, out->val);
-		SPS_LAUNCH_CHECK();
+		gather_sorted(c, ks, ps, dv, n, mb, out->row, out->col, out->val);
 		out->nnz = (uint32_t)n;
 		return;
 	}
@@ -345,7 +292,7 @@ void first_kept_key_raw(spsamd_ctx *c, const spsamd_coo *Xdev, int lead, int ref
 	const size_t n = Xdev->nnz;
 	if (!n) return;
 	const uint64_t shape[2] = {Xdev->shape0, Xdev->shape1};
-	const int mb = bits_for(shape[1 - lead]), Mb = bits_for(shape[lead]);
+	const int mb = bits_of(shape[1 - lead]), Mb = bits_of(shape[lead]);
 	const int32_t *major = lead == 0 ? Xdev->idx0 : Xdev->idx1, *minor = lead == 0 ? Xdev->idx1 : Xdev->idx0;
 	k_first_key_raw<<<dim3(std::min(grid_for(n), 2048u)), dim3(256), 0, c->stream>>>(major, minor, Xdev->val, n, mb, Mb, ref_lead != lead ? 1 : 0, out_dev);
 	SPS_LAUNCH_CHECK();
@@ -362,11 +309,10 @@ uint32_t *sorted_permutation(spsamd_ctx *c, const spsamd_coo *X, int lead)
 	const int32_t *d1 = to_device(c, X->idx1, n, X->mem);
 	const int32_t *major = lead == 0 ? d0 : d1;
 	const int32_t *minor = lead == 0 ? d1 : d0;
-	int mb = bits_for(shape[1 - lead]), Mb = bits_for(shape[lead]);
+	int mb = bits_of(shape[1 - lead]), Mb = bits_of(shape[lead]);
 	uint64_t *keys0 = c->arena.get<uint64_t>(n), *keys1 = c->arena.get<uint64_t>(n);
 	uint32_t *pay0 = c->arena.get<uint32_t>(n), *pay1 = c->arena.get<uint32_t>(n);
-	k_build_keys<<<dim3(grid_for(n)), dim3(256), 0, c->stream>>>(major, minor, n, mb, keys0);
-	SPS_LAUNCH_CHECK();
+	build_keys(c, major, minor, n, mb, keys0);
 	int where = radix_sort_pairs(c, keys0, pay0, keys1, pay1, n, mb + Mb);
 	return where ? pay1 : pay0;
 }

@@ -94,8 +94,6 @@ constexpr int MAX_WORLD = 64;      // ranks of one communicator (per-peer tables
 		if (e_ != 0) throw Error{SPSAMD_EHIP, std::string(#call) + ": " + (rccl() ? rccl()->GetErrorString(e_) : "RCCL error")}; \
 	} while (0)
 
-unsigned grid_for(size_t n, unsigned bs = 256) { return (unsigned)((n + bs - 1) / bs); }
-
 // ---- kernels ---------------------------------------------------------------------------------------------
 
 __global__ void k_mark_need(const int32_t *acol, uint32_t n, uint8_t *need)
@@ -344,12 +342,8 @@ const spsamd_coo *on_device(spsamd_ctx *c, const spsamd_coo *X, spsamd_coo *tmp)
 	if (X->mem != SPSAMD_MEM_HOST || X->nnz == 0) return X;
 	if (!X->idx0 || !X->idx1 || !X->val) throw Error{SPSAMD_EINVAL, "operand with nnz > 0 has a null array"};
 	*tmp = *X;
-	int32_t *d0 = c->arena.get<int32_t>(X->nnz), *d1 = c->arena.get<int32_t>(X->nnz);
-	double *dv = c->arena.get<double>(X->nnz);
-	SPS_HIP(hipMemcpyAsync(d0, X->idx0, X->nnz * sizeof(int32_t), hipMemcpyHostToDevice, c->stream));
-	SPS_HIP(hipMemcpyAsync(d1, X->idx1, X->nnz * sizeof(int32_t), hipMemcpyHostToDevice, c->stream));
-	SPS_HIP(hipMemcpyAsync(dv, X->val, X->nnz * sizeof(double), hipMemcpyHostToDevice, c->stream));
-	tmp->idx0 = d0; tmp->idx1 = d1; tmp->val = dv; tmp->mem = SPSAMD_MEM_DEVICE;
+	tmp->idx0 = to_device(c, X->idx0, X->nnz, X->mem); tmp->idx1 = to_device(c, X->idx1, X->nnz, X->mem);
+	tmp->val = to_device(c, X->val, X->nnz, X->mem); tmp->mem = SPSAMD_MEM_DEVICE;
 	return tmp;
 }
 
@@ -372,16 +366,10 @@ void fetch_panel(spsamd_dist *d, const spsamd_coo *A_block, char transpose_A, co
 	auto fail = [&](int code, std::string msg) { if (!local.code) local = Error{code, std::move(msg)}; };
 
 	// ---- arguments.  Shapes and bounds must be the same on every rank; what a rank can check alone it reports through round 1.
-	const int a0 = transpose_A == 'T' ? 1 : 0, a1 = 1 - a0;
-	const int bk = transpose_B == 'T' ? 1 : 0, bj = 1 - bk;
-	const spsamd_coo *Bsrc = B_block ? B_block : A_block;
-	const uint64_t ashape[2] = {A_block->shape0, A_block->shape1}, bshape[2] = {Bsrc->shape0, Bsrc->shape1};
-	const uint64_t n_inner = ashape[a1];
-	if (bshape[bk] != n_inner) {
-		char buf[160];
-		std::snprintf(buf, sizeof buf, "Inner dimensions for A (%ld) and B (%ld) must match!", (long)n_inner, (long)bshape[bk]);
-		throw Error{SPSAMD_EDIM, buf};                               // (multiply_sparse.hpp:172-174; every rank sees the same shapes: no round needed)
-	}
+	const ProductFrame f(A_block, transpose_A, B_block ? B_block : A_block, transpose_B, false);
+	const int a0 = f.a0, bk = f.bk, bj = f.bj;
+	const uint64_t n_inner = f.inner;
+	f.check_inner("B");                                              // (multiply_sparse.hpp:172-174; every rank sees the same shapes: no round needed)
 	if (!B_block && a0 != bk) throw Error{SPSAMD_EINVAL, "B_block may be NULL only where op(B)'s rows are op(A)'s rows of the same array (equal transpose flags)"};
 	if (b_bounds[0] != 0 || b_bounds[W] != n_inner) throw Error{SPSAMD_EINVAL, "b_bounds must run from 0 to the inner dimension"};
 	for (int p = 0; p < W; ++p) if (b_bounds[p] > b_bounds[p + 1]) throw Error{SPSAMD_EINVAL, "b_bounds must be ascending"};
@@ -537,7 +525,7 @@ void fetch_panel(spsamd_dist *d, const spsamd_coo *A_block, char transpose_A, co
 
 	*Aout = Ac;
 	P->m.row = prow; P->m.col = pcol; P->m.val = pval; P->m.nnz = pn;
-	P->m.nrow = n_inner; P->m.ncol = bshape[bj];
+	P->m.nrow = n_inner; P->m.ncol = f.ncol;
 	P->ptr = pptr;
 	P->remote = pn - (recv_at[me + 1] - recv_at[me]);
 }
@@ -570,13 +558,11 @@ extern "C" int spsamd_dist_multiply(spsamd_dist *d, double C,
 		SPS_HIP(hipEventRecord(d->ev[1], st));
 
 		// ---- 4. the block product: both operands consolidated, trusted as they are; the panel's row pointer exists already
-		const int a0 = transpose_A == 'T' ? 1 : 0, bk = transpose_B == 'T' ? 1 : 0;
-		const spsamd_coo *Bsrc = B_block ? B_block : A_block;
-		const uint64_t ashape[2] = {A_block->shape0, A_block->shape1}, bshape[2] = {Bsrc->shape0, Bsrc->shape1};
+		const ProductFrame f(A_block, transpose_A, B_block ? B_block : A_block, transpose_B, false);
 		spsamd_coo Ad, Bd;
-		Ad.idx0 = Ac.row; Ad.idx1 = Ac.col; Ad.val = Ac.val; Ad.nnz = Ac.nnz; Ad.shape0 = ashape[a0]; Ad.shape1 = ashape[1 - a0];
+		Ad.idx0 = Ac.row; Ad.idx1 = Ac.col; Ad.val = Ac.val; Ad.nnz = Ac.nnz; Ad.shape0 = f.nrow; Ad.shape1 = f.inner;
 		Ad.sort0 = 0; Ad.mem = SPSAMD_MEM_DEVICE_VERIFIED;
-		Bd.idx0 = P.m.row; Bd.idx1 = P.m.col; Bd.val = P.m.val; Bd.nnz = P.m.nnz; Bd.shape0 = bshape[bk]; Bd.shape1 = bshape[1 - bk];
+		Bd.idx0 = P.m.row; Bd.idx1 = P.m.col; Bd.val = P.m.val; Bd.nnz = P.m.nnz; Bd.shape0 = f.inner_b; Bd.shape1 = f.ncol;
 		Bd.sort0 = 0; Bd.mem = SPSAMD_MEM_DEVICE_VERIFIED;
 		Prepared view;
 		view.ctx = c; view.m = P.m; view.lead = 0; view.rowptr = P.ptr;

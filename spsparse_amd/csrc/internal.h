@@ -71,9 +71,8 @@ struct OutSet {
 } // namespace spsamd
 
 namespace spsamd {
-// Developer knobs of one context.  Read from the environment ONCE, at spsamd_ctx_create
-// (SPSAMD_W, SPSAMD_CELL_CAP, SPSAMD_DENSE_MIN, SPSAMD_NO_TILES, SPSAMD_XCD, SPSAMD_EMIT_PATH),
-// or set through spsamd_ctx_set_tuning; results are identical for every setting.
+// Developer knobs of one context.  Read from the environment ONCE, at spsamd_ctx_create (one SPSAMD_* variable per knob:
+// the `knobs` / `envs` table there, capi.hip), or set through spsamd_ctx_set_tuning; results are identical for every setting.
 struct Tuning {
 	int window = 0;              // 0: chosen from the column count; 8192 / 16384
 	int cell_cap = 0;            // 0: default grouping target of the hash cells
@@ -174,13 +173,67 @@ T read_back(spsamd_ctx *c, const T *dev)
 	return *h;
 }
 
+inline unsigned grid_for(size_t n, unsigned bs = 256) { return (unsigned)((n + bs - 1) / bs); }
+
 // Internal value of spsamd_coo::mem (never part of the public ABI): device arrays this library produced itself and
 // knows to be consolidated with valid indices -- consolidate_operand takes them as they are, without the inspection pass.
 #define SPSAMD_MEM_DEVICE_VERIFIED 3
 
-// ---------------------------------------------------------------- consolidated operand (consolidate.hip)
+// ---------------------------------------------------------------- operand intake (operand.hip)
+// What every entry point settles about an operand before its own work starts.  These return facts; what an operation
+// does with them (consolidate, sort without merging, pack rows, make unique keys, only inspect) stays in its own file.
 
 struct Prepared;
+
+// Any operand as a plain one.  SPSAMD_MEM_PREPARED: the handle is checked (non-null, prepared by `c`) and `coo` holds its
+// consolidated tuples as stored (idx0 / idx1 by its lead, sort0 = its lead, device memory; the shape is X's), `prep` the
+// handle.  Host and device operands: `coo` is *X, `prep` null.  Either way coo.nnz is the operand's tuple count.
+struct OperandView { spsamd_coo coo; Prepared *prep = nullptr; };
+OperandView operand_view(spsamd_ctx *c, const spsamd_coo *X);
+// The tuple count alone, nothing checked (a null handle counts as empty): for the short circuits that run before intake.
+uint64_t operand_tuples(const spsamd_coo *X);
+
+// The argument checks of a plain operand, all SPSAMD_EINVAL: mem (under OPERAND_PLAIN_MEM), then, where it has tuples,
+// 2^31 or more of them, a null array (val counts under OPERAND_VALUES), a dimension beyond the int32 index range.
+enum { OPERAND_VALUES = 1,        // the caller reads X.val
+       OPERAND_PLAIN_MEM = 2 };   // mem must be SPSAMD_MEM_HOST or SPSAMD_MEM_DEVICE (the multiply's intake also takes _VERIFIED)
+void check_operand(const spsamd_coo &X, int flags);
+
+// Is the device operand X a result this context wrote itself and still holds (c->own): consolidated by X.sort0, indices valid?
+bool is_own_result(const spsamd_ctx *c, const spsamd_coo &X);
+
+// Upload if host: p itself for device memory (or n == 0), else a copy in the workspace.
+template <class T>
+const T *to_device(spsamd_ctx *c, const T *p, size_t n, int mem)
+{
+	if (mem != SPSAMD_MEM_HOST || n == 0) return p;
+	T *d = c->arena.get<T>(n);
+	SPS_HIP(hipMemcpyAsync(d, p, n * sizeof(T), hipMemcpyHostToDevice, c->stream));
+	return d;
+}
+
+int bits_of(uint64_t dim);        // bits needed to hold indices 0 .. dim-1
+// keys[i] = major[i] << minor_bits | minor[i]: the sort key of radix_sort_pairs (payload: the storage position) ...
+void build_keys(spsamd_ctx *c, const int32_t *major, const int32_t *minor, size_t n, int minor_bits, uint64_t *keys);
+// ... and tuple i of the sorted operand: its indices out of sorted key i, its value from storage position perm[i]
+void gather_sorted(spsamd_ctx *c, const uint64_t *keys, const uint32_t *perm, const double *val, size_t n, int minor_bits,
+	int32_t *row, int32_t *col, double *oval);
+
+// The frame of a product op(A) * op(B) (multiply_sparse.hpp:167-169): op(A) rows = A.shape[a0]; op(B) is read by ROWS
+// (inner index first), its columns are B.shape[bj].
+struct ProductFrame {
+	int a0, a1, bk, bj;
+	uint64_t nrow, inner, ncol;   // rows(op(A)), its columns, cols(op(B))
+	uint64_t inner_b;             // rows(op(B)): must equal `inner`
+	uint64_t shape0, shape1;      // the result's shape (nrow x ncol, the other way round under `permute`)
+	ProductFrame(const spsamd_coo *A, char transpose_A, const spsamd_coo *B, char transpose_B, bool permute);
+	void check_inner(const char *what) const;   // SPSAMD_EDIM (:172-174); `what` names the right operand, "B" or "V" (:173,299)
+};
+// The reference's short circuits (:178-184): the product is empty whatever the operands hold.
+bool product_is_empty(double C, const spsamd_vec *scalei, const spsamd_coo *A, const spsamd_vec *scalej, const spsamd_coo *B,
+	const spsamd_vec *scalek);
+
+// ---------------------------------------------------------------- consolidated operand (consolidate.hip)
 
 // op(X) in row-major consolidated form on the device.
 struct ConMat {
@@ -360,11 +413,34 @@ void multiply_sampled(spsamd_ctx *c, const spsamd_coo *M, char transpose, const 
 void select_tuples(spsamd_ctx *c, const spsamd_coo *A, char transpose, int predicate, int64_t iparam, double dparam,
 	int select_flags, int duplicate_policy, int zero_nan, int sink_kind, int sink_flags, spsamd_result *res);
 
+// The same operand struct twice (A * A): one consolidation can serve both sides (capi.hip).
+bool same_operand(const spsamd_coo *a, const spsamd_coo *b);
+
+// ---------------------------------------------------------------- sink tail (sink.hip)
+// How an operation hands its result over.  A new operation calls these (and the intake above), it does not copy them.
+
 // Select the output set the next result is written to: the current one unless a device operand lives in it.
 void pick_output_set(spsamd_ctx *c, const spsamd_coo *const *operands, int n);
 // Does output set `s` of the context hold an array of one of the device operands?
 bool output_set_aliased(const spsamd_ctx *c, int s, const spsamd_coo *const *operands, int n);
-// The same operand struct twice (A * A): one consolidation can serve both sides.
-bool same_operand(const spsamd_coo *a, const spsamd_coo *b);
+
+struct CooOut { int32_t *row, *col; double *val; };
+// The current output set, about to be overwritten (its entry of c->own is dropped), grown to `total` tuples.
+CooOut coo_output(spsamd_ctx *c, size_t total);
+// Workspace arrays for `total` tuples: where the DIGEST sink of an operation that stores its tuples first keeps them.
+CooOut scratch_output(spsamd_ctx *c, size_t total);
+// SINK_COO: fill res (nnz, idx0, idx1, val; its shape is set already) and register the tuples in c->own -- row-major sorted,
+// every (i, j) once, indices valid: consolidated by sort order {0, 1}.  `permute` (PermuteAccum {1,0}): the same tuples
+// with res->idx0 / idx1 swapped, which read that way are consolidated by {1, 0}.
+void publish_coo(spsamd_ctx *c, spsamd_result *res, const int32_t *orow, const int32_t *ocol, const double *oval, uint64_t total, bool permute);
+// DIGEST | ROWSTATS: the context's three per-row arrays (tuple count, value sum, index hash), zeroed and attached to res.
+// `slack`: bytes each buffer is asked for beyond its nrow entries.
+struct RowStats { long long *nnz = nullptr; double *sum = nullptr; unsigned long long *hash = nullptr; };
+RowStats rowstats_begin(spsamd_ctx *c, uint64_t nrow, size_t slack, spsamd_result *res);
+// SINK_DIGEST over stored tuples: the row statistics if sink_flags asks, index hash and value sum into res.
+void digest_stored(spsamd_ctx *c, spsamd_result *res, const int32_t *orow, const int32_t *ocol, const double *oval, uint32_t total,
+	uint64_t nrow, int sink_flags);
+// The end of a call: ev[7] recorded and waited for, ms_total (from ev[0]) and workspace_bytes filled.
+void finish_call(spsamd_ctx *c, spsamd_result *res);
 
 } // namespace spsamd

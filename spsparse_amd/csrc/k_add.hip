@@ -32,15 +32,6 @@ constexpr int ADD_NT = 256;                    // lanes per tile
 constexpr int ADD_IPT = 8;                     // merged items per lane
 constexpr int ADD_TILE = ADD_NT * ADD_IPT;     // merged items per tile
 
-static unsigned grid_add(size_t n, unsigned bs = 256) { return (unsigned)((n + bs - 1) / bs); }
-
-static int bits_of(uint64_t dim)
-{
-	int b = 0;
-	while (b < 63 && (uint64_t(1) << b) < dim) ++b;
-	return b;
-}
-
 // op(X) on the device, ordered by (row, col), storage order inside a key
 struct AddStream {
 	const int32_t *row = nullptr, *col = nullptr;
@@ -233,84 +224,21 @@ __global__ void __launch_bounds__(ADD_NT) k_add_merge(AddStream a, AddStream b, 
 	}
 }
 
-__global__ void __launch_bounds__(256) k_add_keys(const int32_t *__restrict__ major, const int32_t *__restrict__ minor, uint32_t n,
-	int minor_bits, uint64_t *__restrict__ keys)
-{
-	const uint32_t i = blockIdx.x * blockDim.x + threadIdx.x;
-	if (i < n) keys[i] = ((uint64_t)(uint32_t)major[i] << minor_bits) | (uint64_t)(uint32_t)minor[i];
-}
-
-// tuple i of the sorted stream: its indices from the sorted key, its value from storage position perm[i]
-__global__ void __launch_bounds__(256) k_add_gather(const uint64_t *__restrict__ keys, const uint32_t *__restrict__ perm,
-	const double *__restrict__ val, uint32_t n, int minor_bits, int32_t *__restrict__ row, int32_t *__restrict__ col,
-	double *__restrict__ oval)
-{
-	const uint32_t i = blockIdx.x * blockDim.x + threadIdx.x;
-	if (i >= n) return;
-	const uint64_t k = keys[i];
-	row[i] = (int32_t)(k >> minor_bits);
-	col[i] = (int32_t)(k & ((uint64_t(1) << minor_bits) - 1));
-	oval[i] = val[perm[i]];
-}
-
-// DIGEST sink over the stored tuples: count, index hash, sum (and the per-row statistics under ROWSTATS)
-__global__ void __launch_bounds__(256) k_add_digest(const int32_t *__restrict__ row, const int32_t *__restrict__ col,
-	const double *__restrict__ val, uint32_t n, unsigned long long *hash, double *sum,
-	long long *row_nnz, double *row_sum, unsigned long long *row_hash)
-{
-	unsigned long long h = 0;
-	double s = 0;
-	for (uint32_t t = blockIdx.x * blockDim.x + threadIdx.x; t < n; t += gridDim.x * blockDim.x) {
-		const unsigned long long x = mix64((uint32_t)row[t], (uint32_t)col[t]);
-		h += x; s += val[t];
-		if (row_nnz) { atomicAdd((unsigned long long *)&row_nnz[row[t]], 1ull); atomicAdd(&row_sum[row[t]], val[t]); atomicAdd(&row_hash[row[t]], x); }
-	}
-	h = wave_reduce_sum(h); s = wave_reduce_sum(s);
-	if (lane_id() == 0) { atomicAdd(hash, h); atomicAdd(sum, s); }
-}
-
-template <class T>
-static const T *add_upload(spsamd_ctx *c, const T *p, size_t n, int mem)
-{
-	if (mem != SPSAMD_MEM_HOST || n == 0) return p;
-	T *d = c->arena.get<T>(n);
-	SPS_HIP(hipMemcpyAsync(d, p, n * sizeof(T), hipMemcpyHostToDevice, c->stream));
-	return d;
-}
-
-static const Prepared *prepared_of(spsamd_ctx *c, const spsamd_coo *X)
-{
-	const Prepared *p = (const Prepared *)X->idx0;
-	if (!p || p->ctx != c) throw Error{SPSAMD_EINVAL, "a prepared operand belongs to the context that prepared it"};
-	return p;
-}
-
 // op(X) as a sorted stream; *sorted: a sort ran.  lead = 1 for 'T'.
 static void add_stream(spsamd_ctx *c, const spsamd_coo *X, int lead, bool force_sort, AddStream *out, bool *sorted)
 {
 	*out = AddStream();
-	if (X->mem == SPSAMD_MEM_PREPARED) {
-		const Prepared *p = prepared_of(c, X);
-		if (p->lead == lead && !force_sort) { out->row = p->m.row; out->col = p->m.col; out->val = p->m.val; out->n = p->m.nnz; return; }
-		spsamd_coo Y;                                                   // its consolidated tuples as stored
-		Y.idx0 = p->lead == 0 ? p->m.row : p->m.col; Y.idx1 = p->lead == 0 ? p->m.col : p->m.row; Y.val = p->m.val;
-		Y.nnz = p->m.nnz; Y.shape0 = X->shape0; Y.shape1 = X->shape1; Y.sort0 = p->lead; Y.mem = SPSAMD_MEM_DEVICE;
-		add_stream(c, &Y, lead, force_sort, out, sorted);
-		return;
-	}
+	// a prepared handle of the same transpose is the stream; of the other, its consolidated tuples as stored
+	const OperandView view = operand_view(c, X);
+	if (view.prep && view.prep->lead == lead && !force_sort) { const ConMat &m = view.prep->m; out->row = m.row; out->col = m.col; out->val = m.val; out->n = m.nnz; return; }
+	X = &view.coo;
 	const size_t n = X->nnz;
 	if (n == 0) return;
-	if (X->mem != SPSAMD_MEM_HOST && X->mem != SPSAMD_MEM_DEVICE) throw Error{SPSAMD_EINVAL, "bad mem of an operand"};
-	if (!X->idx0 || !X->idx1 || !X->val) throw Error{SPSAMD_EINVAL, "operand with nnz > 0 has a null array"};
+	check_operand(*X, OPERAND_VALUES | OPERAND_PLAIN_MEM);
 	const uint64_t shape[2] = {X->shape0, X->shape1};
-	if (shape[0] > (uint64_t(1) << 31) || shape[1] > (uint64_t(1) << 31)) throw Error{SPSAMD_EINVAL, "shape exceeds the int32 index range"};
-	bool own_result = false;                                            // a SINK_COO result of this context handed back in
-	if (X->mem == SPSAMD_MEM_DEVICE)
-		for (const auto &o : c->own)
-			if (o.sort0 >= 0 && o.sort0 == X->sort0 && o.d0 == X->idx0 && o.d1 == X->idx1 && o.v == X->val && o.nnz == n &&
-				o.shape0 == X->shape0 && o.shape1 == X->shape1) own_result = true;
-	const int32_t *d0 = add_upload(c, X->idx0, n, X->mem), *d1 = add_upload(c, X->idx1, n, X->mem);
-	const double *dv = add_upload(c, X->val, n, X->mem);
+	const bool own_result = is_own_result(c, *X);                       // a SINK_COO result of this context handed back in
+	const int32_t *d0 = to_device(c, X->idx0, n, X->mem), *d1 = to_device(c, X->idx1, n, X->mem);
+	const double *dv = to_device(c, X->val, n, X->mem);
 	const int32_t *major = lead == 0 ? d0 : d1, *minor = lead == 0 ? d1 : d0;
 	bool ordered = own_result && X->sort0 == lead;
 	int low_bit = 0;
@@ -330,20 +258,13 @@ static void add_stream(spsamd_ctx *c, const spsamd_coo *X, int lead, bool force_
 	const int mb = bits_of(shape[1 - lead]), Mb = bits_of(shape[lead]);
 	uint64_t *keys0 = c->arena.get<uint64_t>(n), *keys1 = c->arena.get<uint64_t>(n);
 	uint32_t *pay0 = c->arena.get<uint32_t>(n), *pay1 = c->arena.get<uint32_t>(n);
-	k_add_keys<<<dim3(grid_add(n)), dim3(256), 0, c->stream>>>(major, minor, (uint32_t)n, mb, keys0);
-	SPS_LAUNCH_CHECK();
+	build_keys(c, major, minor, n, mb, keys0);
 	const int where = radix_sort_pairs(c, keys0, pay0, keys1, pay1, n, mb + Mb, low_bit < 0 ? mb : 0);
 	int32_t *row = c->arena.get<int32_t>(n), *col = c->arena.get<int32_t>(n);
 	double *val = c->arena.get<double>(n);
-	k_add_gather<<<dim3(grid_add(n)), dim3(256), 0, c->stream>>>(where ? keys1 : keys0, where ? pay1 : pay0, dv, (uint32_t)n, mb, row, col, val);
-	SPS_LAUNCH_CHECK();
+	gather_sorted(c, where ? keys1 : keys0, where ? pay1 : pay0, dv, n, mb, row, col, val);
 	out->row = row; out->col = col; out->val = val; out->n = (uint32_t)n;
 	*sorted = true;
-}
-
-static uint64_t operand_nnz(spsamd_ctx *c, const spsamd_coo *X)
-{
-	return X->mem == SPSAMD_MEM_PREPARED ? prepared_of(c, X)->m.nnz : X->nnz;
 }
 
 template <int MODE>
@@ -370,7 +291,7 @@ void add_matrices(spsamd_ctx *c, double alpha, const spsamd_coo *A, char transpo
 			(unsigned long long)ncol, (unsigned long long)bsh[lb], (unsigned long long)bsh[1 - lb]);
 		throw Error{SPSAMD_EDIM, buf};
 	}
-	const uint64_t na = operand_nnz(c, A), nb = operand_nnz(c, B);
+	const uint64_t na = operand_view(c, A).coo.nnz, nb = operand_view(c, B).coo.nnz;
 	if (na + nb >= (uint64_t(1) << 31))
 		throw Error{SPSAMD_EINVAL, "nnz(A) + nnz(B) is 2^31 or more: the result would not be a legal operand"};
 	const bool coo = sink_kind == SPSAMD_SINK_COO;
@@ -399,73 +320,30 @@ void add_matrices(spsamd_ctx *c, double alpha, const spsamd_coo *A, char transpo
 		uint32_t *idx = c->arena.get<uint32_t>(2);
 		first = c->arena.get<FirstKept>(1);
 		fill_u32(c, idx, 0xFFFFFFFFu, 2);
-		if (sa.n) { k_add_first_idx<<<dim3(std::min(grid_add(sa.n), 1024u)), dim3(256), 0, st>>>(sa.val, sa.n, alpha, idx); SPS_LAUNCH_CHECK(); }
-		if (sb.n) { k_add_first_idx<<<dim3(std::min(grid_add(sb.n), 1024u)), dim3(256), 0, st>>>(sb.val, sb.n, beta, idx + 1); SPS_LAUNCH_CHECK(); }
+		if (sa.n) { k_add_first_idx<<<dim3(std::min(grid_for(sa.n), 1024u)), dim3(256), 0, st>>>(sa.val, sa.n, alpha, idx); SPS_LAUNCH_CHECK(); }
+		if (sb.n) { k_add_first_idx<<<dim3(std::min(grid_for(sb.n), 1024u)), dim3(256), 0, st>>>(sb.val, sb.n, beta, idx + 1); SPS_LAUNCH_CHECK(); }
 		k_add_first_pick<<<dim3(1), dim3(1), 0, st>>>(sa, sb, idx, first);
 		SPS_LAUNCH_CHECK();
 	}
 	uint32_t *split = c->arena.get<uint32_t>((size_t)ntiles + 1);
 	uint32_t *tile_count = c->arena.get<uint32_t>((size_t)ntiles + 1), *tile_off = c->arena.get<uint32_t>((size_t)ntiles + 1);
-	k_add_partition<<<dim3(grid_add((size_t)ntiles + 1)), dim3(256), 0, st>>>(sa, sb, ntiles, split);
+	k_add_partition<<<dim3(grid_for((size_t)ntiles + 1)), dim3(256), 0, st>>>(sa, sb, ntiles, split);
 	SPS_LAUNCH_CHECK();
 	launch_merge<ADD_COUNT>(c, ntiles, sa, sb, alpha, beta, zero_nan, first, split, tile_count, nullptr, nullptr, nullptr, nullptr);
 	scan_exclusive_u32_u32(c, tile_count, tile_off, ntiles);
 	const uint32_t total = read_back(c, tile_off + ntiles);
 
-	int32_t *orow, *ocol;
-	double *oval;
-	if (coo) {
-		OutSet &o = c->out[c->cur_out];
-		c->own[c->cur_out].sort0 = -1;                                 // that set is about to be overwritten
-		o.i.ensure((size_t)total * 4 + 4); o.j.ensure((size_t)total * 4 + 4); o.v.ensure((size_t)total * 8 + 8);
-		orow = (int32_t *)o.i.p; ocol = (int32_t *)o.j.p; oval = (double *)o.v.p;
-	} else {
-		orow = c->arena.get<int32_t>((size_t)total + 1); ocol = c->arena.get<int32_t>((size_t)total + 1);
-		oval = c->arena.get<double>((size_t)total + 1);
-	}
+	const CooOut o = coo ? coo_output(c, total) : scratch_output(c, total);
 	switch (duplicate_policy) {
-	case SPSAMD_ADD: launch_merge<SPSAMD_ADD>(c, ntiles, sa, sb, alpha, beta, zero_nan, first, split, nullptr, tile_off, orow, ocol, oval); break;
-	case SPSAMD_REPLACE: launch_merge<SPSAMD_REPLACE>(c, ntiles, sa, sb, alpha, beta, zero_nan, first, split, nullptr, tile_off, orow, ocol, oval); break;
-	default: launch_merge<SPSAMD_LEAVE_ALONE>(c, ntiles, sa, sb, alpha, beta, zero_nan, first, split, nullptr, tile_off, orow, ocol, oval); break;
+	case SPSAMD_ADD: launch_merge<SPSAMD_ADD>(c, ntiles, sa, sb, alpha, beta, zero_nan, first, split, nullptr, tile_off, o.row, o.col, o.val); break;
+	case SPSAMD_REPLACE: launch_merge<SPSAMD_REPLACE>(c, ntiles, sa, sb, alpha, beta, zero_nan, first, split, nullptr, tile_off, o.row, o.col, o.val); break;
+	default: launch_merge<SPSAMD_LEAVE_ALONE>(c, ntiles, sa, sb, alpha, beta, zero_nan, first, split, nullptr, tile_off, o.row, o.col, o.val); break;
 	}
 	res->nnz = total;
-
-	if (coo) {
-		res->idx0 = orow; res->idx1 = ocol; res->val = oval;
-		// row-major sorted, every (i, j) once, no zero: consolidated by sort order {0, 1} (read permuted: by {1, 0})
-		auto &w = c->own[c->cur_out];
-		w.d0 = permute ? ocol : orow; w.d1 = permute ? orow : ocol; w.v = oval; w.nnz = total;
-		w.shape0 = res->shape0; w.shape1 = res->shape1; w.sort0 = permute ? 1 : 0;
-		if (permute) std::swap(res->idx0, res->idx1);
-	} else {
-		unsigned long long *hs = c->arena.get<unsigned long long>(2);
-		fill_zero(c, hs, 2 * sizeof(unsigned long long));
-		long long *rn = nullptr; double *rs = nullptr; unsigned long long *rh = nullptr;
-		if (sink_flags & SPSAMD_SINK_ROWSTATS) {
-			c->rowstat_n.ensure(nrow * sizeof(long long) + 8);
-			c->rowstat_s.ensure(nrow * sizeof(double) + 8);
-			c->rowstat_h.ensure(nrow * sizeof(unsigned long long) + 8);
-			fill_zero(c, c->rowstat_n.p, nrow * sizeof(long long));
-			fill_zero(c, c->rowstat_s.p, nrow * sizeof(double));
-			fill_zero(c, c->rowstat_h.p, nrow * sizeof(unsigned long long));
-			rn = (long long *)c->rowstat_n.p; rs = (double *)c->rowstat_s.p; rh = (unsigned long long *)c->rowstat_h.p;
-			res->row_nnz = (const int64_t *)rn; res->row_sum = rs; res->row_hash = (const uint64_t *)rh;
-		}
-		if (total) {
-			k_add_digest<<<dim3(std::min(grid_add(total), 2048u)), dim3(256), 0, st>>>(orow, ocol, oval, total, hs, (double *)(hs + 1), rn, rs, rh);
-			SPS_LAUNCH_CHECK();
-		}
-		unsigned long long *h = (unsigned long long *)c->host_staging(2 * sizeof(unsigned long long));
-		SPS_HIP(hipMemcpyAsync(h, hs, 2 * sizeof(unsigned long long), hipMemcpyDeviceToHost, st));
-		SPS_HIP(hipStreamSynchronize(st));
-		res->hash = h[0];
-		std::memcpy(&res->sum, &h[1], sizeof(double));
-	}
-	SPS_HIP(hipEventRecord(c->ev[7], st));
-	SPS_HIP(hipEventSynchronize(c->ev[7]));
+	if (coo) publish_coo(c, res, o.row, o.col, o.val, total, permute);
+	else digest_stored(c, res, o.row, o.col, o.val, total, nrow, sink_flags);
+	finish_call(c, res);
 	if (sorted_a || sorted_b) SPS_HIP(hipEventElapsedTime(&res->ms_consolidate, c->ev[0], c->ev[1]));
-	SPS_HIP(hipEventElapsedTime(&res->ms_total, c->ev[0], c->ev[7]));
-	res->workspace_bytes = c->arena.call_used;
 }
 
 } // namespace spsamd

@@ -36,15 +36,6 @@ constexpr uint32_t MASK_WAVE_MIN = 32;         // auto: a key goes to the wave k
 
 enum : uint8_t { MCLS_NONE = 0, MCLS_ENTRY = 1, MCLS_ROW = 2, MCLS_WAVE = 3 };
 
-static unsigned grid_m(size_t n, unsigned bs = 256) { return (unsigned)((n + bs - 1) / bs); }
-
-static int bits_of_m(uint64_t dim)
-{
-	int b = 0;
-	while (b < 63 && (uint64_t(1) << b) < dim) ++b;
-	return b;
-}
-
 // What every evaluation kernel reads
 struct MaskedArgs {
 	const uint32_t *arp;            // op(A): row pointer over rows(op(A)) + 1
@@ -362,13 +353,6 @@ __global__ void __launch_bounds__(256) k_mask_inspect(const int32_t *__restrict_
 	if (lane_id() == 0 && wf) atomicOr(flags, wf);
 }
 
-__global__ void __launch_bounds__(256) k_mask_keys(const int32_t *__restrict__ r, const int32_t *__restrict__ c, uint32_t n, int cbits,
-	uint64_t *__restrict__ keys)
-{
-	const uint32_t t = blockIdx.x * blockDim.x + threadIdx.x;
-	if (t < n) keys[t] = ((uint64_t)(uint32_t)r[t] << cbits) | (uint64_t)(uint32_t)c[t];
-}
-
 __global__ void __launch_bounds__(256) k_mask_first(const uint64_t *__restrict__ keys, uint32_t n, uint8_t *__restrict__ first)
 {
 	const uint32_t t = blockIdx.x * blockDim.x + threadIdx.x;
@@ -385,15 +369,6 @@ __global__ void __launch_bounds__(256) k_mask_unique(const uint64_t *__restrict_
 	mj[off[t]] = (int32_t)(k & ((uint64_t(1) << cbits) - 1));
 }
 
-template <class T>
-static const T *masked_upload(spsamd_ctx *c, const T *p, size_t n, int mem)
-{
-	if (mem != SPSAMD_MEM_HOST || n == 0) return p;
-	T *d = c->arena.get<T>(n);
-	SPS_HIP(hipMemcpyAsync(d, p, n * sizeof(T), hipMemcpyHostToDevice, c->stream));
-	return d;
-}
-
 // M's keys, row-major and each once (arena memory, or M's own arrays where they already are that)
 struct MaskKeys {
 	const int32_t *i = nullptr, *j = nullptr;
@@ -403,31 +378,24 @@ struct MaskKeys {
 static void mask_keys(spsamd_ctx *c, const spsamd_coo *M, uint64_t nrow, uint64_t ncol, MaskKeys *out)
 {
 	*out = MaskKeys();
-	spsamd_coo X = *M;
-	if (M->mem == SPSAMD_MEM_PREPARED) {
-		const Prepared *p = (const Prepared *)M->idx0;
-		if (!p || p->ctx != c) throw Error{SPSAMD_EINVAL, "a prepared operand belongs to the context that prepared it"};
-		if (p->lead == 0) { out->i = p->m.row; out->j = p->m.col; out->n = p->m.nnz; return; }     // consolidated row-major
-		// prepared for 'T': its consolidated tuples, sorted the other way
-		X.idx0 = p->m.col; X.idx1 = p->m.row; X.val = p->m.val; X.nnz = p->m.nnz; X.sort0 = 1; X.mem = SPSAMD_MEM_DEVICE;
-	}
+	const OperandView view = operand_view(c, M);
+	if (view.prep && view.prep->lead == 0) { out->i = view.prep->m.row; out->j = view.prep->m.col; out->n = view.prep->m.nnz; return; }     // consolidated row-major
+	const spsamd_coo &X = view.coo;                  // (prepared for 'T': its consolidated tuples, sorted the other way)
 	const size_t n = X.nnz;
 	if (n == 0) return;
-	if (X.mem != SPSAMD_MEM_HOST && X.mem != SPSAMD_MEM_DEVICE) throw Error{SPSAMD_EINVAL, "bad mem of M"};
-	if (!X.idx0 || !X.idx1) throw Error{SPSAMD_EINVAL, "M with nnz > 0 has a null index array"};
-	const int32_t *r = masked_upload(c, X.idx0, n, X.mem), *cc = masked_upload(c, X.idx1, n, X.mem);
+	check_operand(X, OPERAND_PLAIN_MEM);             // only M's keys are read: val may be null
+	const int32_t *r = to_device(c, X.idx0, n, X.mem), *cc = to_device(c, X.idx1, n, X.mem);
 	uint32_t *flags = c->arena.get<uint32_t>(1);
 	fill_zero(c, flags, sizeof(uint32_t));
-	k_mask_inspect<<<dim3(std::min(grid_m(n, 1024), 2048u)), dim3(256), 0, c->stream>>>(r, cc, n, nrow, ncol, flags);
+	k_mask_inspect<<<dim3(std::min(grid_for(n, 1024), 2048u)), dim3(256), 0, c->stream>>>(r, cc, n, nrow, ncol, flags);
 	SPS_LAUNCH_CHECK();
 	const uint32_t f = read_back(c, flags);
 	if (f & 1u) throw Error{SPSAMD_EINVAL, "M: index out of bounds"};
 	if (X.sort0 == 0 && (f & 2u)) throw Error{SPSAMD_EINVAL, "M claims sort_order {0, 1} but its (row, col) keys are not in that order"};
 	if (!(f & 6u)) { out->i = r; out->j = cc; out->n = (uint32_t)n; return; }      // in order, no repeats: read in place
-	const int cb = bits_of_m(ncol), rb = bits_of_m(nrow);
+	const int cb = bits_of(ncol), rb = bits_of(nrow);
 	uint64_t *keys0 = c->arena.get<uint64_t>(n);
-	k_mask_keys<<<dim3(grid_m(n)), dim3(256), 0, c->stream>>>(r, cc, (uint32_t)n, cb, keys0);
-	SPS_LAUNCH_CHECK();
+	build_keys(c, r, cc, n, cb, keys0);
 	const uint64_t *keys = keys0;
 	if (f & 2u) {
 		uint64_t *keys1 = c->arena.get<uint64_t>(n);
@@ -436,20 +404,14 @@ static void mask_keys(spsamd_ctx *c, const spsamd_coo *M, uint64_t nrow, uint64_
 	}
 	uint8_t *first = c->arena.get<uint8_t>(n);
 	uint32_t *off = c->arena.get<uint32_t>(n + 1);
-	k_mask_first<<<dim3(grid_m(n)), dim3(256), 0, c->stream>>>(keys, (uint32_t)n, first);
+	k_mask_first<<<dim3(grid_for(n)), dim3(256), 0, c->stream>>>(keys, (uint32_t)n, first);
 	SPS_LAUNCH_CHECK();
 	scan_exclusive_u8_u32(c, first, off, n);
 	const uint32_t nu = read_back(c, off + n);
 	int32_t *mi = c->arena.get<int32_t>(nu), *mj = c->arena.get<int32_t>(nu);
-	k_mask_unique<<<dim3(grid_m(n)), dim3(256), 0, c->stream>>>(keys, first, off, (uint32_t)n, cb, mi, mj);
+	k_mask_unique<<<dim3(grid_for(n)), dim3(256), 0, c->stream>>>(keys, first, off, (uint32_t)n, cb, mi, mj);
 	SPS_LAUNCH_CHECK();
 	out->i = mi; out->j = mj; out->n = nu;
-}
-
-static uint64_t masked_nnz(const spsamd_coo *X)
-{
-	if (X->mem == SPSAMD_MEM_PREPARED) return X->idx0 ? ((const Prepared *)X->idx0)->m.nnz : 0;
-	return X->nnz;
 }
 
 void multiply_masked(spsamd_ctx *c, double C,
@@ -461,31 +423,24 @@ void multiply_masked(spsamd_ctx *c, double C,
 	if (duplicate_policy < 0 || duplicate_policy > 2) throw Error{SPSAMD_EINVAL, "bad duplicate_policy"};
 	if (sink_kind != SPSAMD_SINK_COO && sink_kind != SPSAMD_SINK_DIGEST) throw Error{SPSAMD_EINVAL, "bad sink_kind"};
 	std::memset(res, 0, sizeof(*res));
-	// multiply_sparse.hpp:167-169: op(A) by rows, op(B) by its columns (the reference's Bcon)
-	const int a0 = transpose_A == 'T' ? 1 : 0, a1 = 1 - a0;
-	const int bk = transpose_B == 'T' ? 1 : 0, bj = 1 - bk;
-	const uint64_t ashape[2] = {A->shape0, A->shape1}, bshape[2] = {B->shape0, B->shape1};
-	const uint64_t nrow = ashape[a0], ncol = bshape[bj];
 	const bool coo = sink_kind == SPSAMD_SINK_COO;
 	const bool permute = coo && (sink_flags & SPSAMD_SINK_PERMUTE);
-	res->shape0 = permute ? ncol : nrow;
-	res->shape1 = permute ? nrow : ncol;
-	if (ashape[a1] != bshape[bk]) {                                      // :172-174
-		char buf[160];
-		std::snprintf(buf, sizeof buf, "Inner dimensions for A (%ld) and B (%ld) must match!", (long)ashape[a1], (long)bshape[bk]);
-		throw Error{SPSAMD_EDIM, buf};
-	}
+	// op(A) by rows, op(B) by its columns (the reference's Bcon)
+	const ProductFrame f(A, transpose_A, B, transpose_B, permute);
+	const uint64_t nrow = f.nrow, ncol = f.ncol;
+	res->shape0 = f.shape0; res->shape1 = f.shape1;
+	f.check_inner("B");
 	if (M->shape0 != nrow || M->shape1 != ncol) {
 		char buf[200];
 		std::snprintf(buf, sizeof buf, "Shape of M (%llu x %llu) must be that of op(A) * op(B) (%llu x %llu)",
 			(unsigned long long)M->shape0, (unsigned long long)M->shape1, (unsigned long long)nrow, (unsigned long long)ncol);
 		throw Error{SPSAMD_EDIM, buf};
 	}
-	const uint64_t nm_in = masked_nnz(M);
+	// (the unchecked count, as this call always took it: a null prepared handle is an empty mask here, where add's intake
+	// throws, and a handle of another context fails only once mask_keys reads it)
+	const uint64_t nm_in = operand_tuples(M);
 	if (nm_in >= (uint64_t(1) << 31)) throw Error{SPSAMD_EINVAL, "nnz(M) is 2^31 or more"};
-	if (C == 0 || (scalei && scalei->nnz == 0) || A->nnz == 0 || (scalej && scalej->nnz == 0) ||
-		B->nnz == 0 || (scalek && scalek->nnz == 0) || nm_in == 0)          // :178-184, and an empty mask
-		return;
+	if (product_is_empty(C, scalei, A, scalej, B, scalek) || nm_in == 0) return;      // and an empty mask
 
 	SPS_HIP(hipSetDevice(c->device));
 	c->arena.reset();
@@ -493,13 +448,13 @@ void multiply_masked(spsamd_ctx *c, double C,
 	SPS_HIP(hipEventRecord(c->ev[0], st));
 	{ const spsamd_coo *ops[3] = {A, B, M}; pick_output_set(c, ops, 3); }
 	ConMat ca, cb;
-	consolidate_operand(c, A, a0, a0, duplicate_policy, zero_nan, &ca);           // :187
-	consolidate_operand(c, B, bj, bj, duplicate_policy, zero_nan, &cb);           // :188, by the columns of op(B)
+	consolidate_operand(c, A, f.a0, f.a0, duplicate_policy, zero_nan, &ca);       // :187
+	consolidate_operand(c, B, f.bj, f.bj, duplicate_policy, zero_nan, &cb);       // :188, by the columns of op(B)
 	res->nnz_a = ca.nnz; res->nnz_b = cb.nnz;
 	const uint32_t *arp = dense_rowptr(c, ca, 0), *brp = dense_rowptr(c, cb, 0);
 	ScaleDev si, sj, sk;
 	upload_scale(c, scalei, nrow, "scalei", &si);
-	upload_scale(c, scalej, ashape[a1], "scalej", &sj);
+	upload_scale(c, scalej, f.inner, "scalej", &sj);
 	upload_scale(c, scalek, ncol, "scalek", &sk);
 	SPS_HIP(hipEventRecord(c->ev[1], st));
 	MaskKeys mk;
@@ -520,9 +475,9 @@ void multiply_masked(spsamd_ctx *c, double C,
 	fill_zero(c, acc, 4 * sizeof(unsigned long long));
 	fill_zero(c, emit, nm + 1);
 	const int32_t *si_pos = si.present ? si.pos : nullptr, *sk_pos = sk.present ? sk.pos : nullptr;
-	if (nrow) { k_masked_rows<<<dim3(grid_m(nrow)), dim3(256), 0, st>>>(mrp, arp, nrow, si_pos, si.val, path, rowflag); SPS_LAUNCH_CHECK(); }
+	if (nrow) { k_masked_rows<<<dim3(grid_for(nrow)), dim3(256), 0, st>>>(mrp, arp, nrow, si_pos, si.val, path, rowflag); SPS_LAUNCH_CHECK(); }
 	if (nm) {
-		k_masked_classify<<<dim3(grid_m(nm)), dim3(256), 0, st>>>(mk.i, mk.j, nm, arp, brp, si_pos, si.val, sk_pos, sk.val, rowflag, path,
+		k_masked_classify<<<dim3(grid_for(nm)), dim3(256), 0, st>>>(mk.i, mk.j, nm, arp, brp, si_pos, si.val, sk_pos, sk.val, rowflag, path,
 			cls, f_entry, f_wave);
 		SPS_LAUNCH_CHECK();
 	}
@@ -536,8 +491,8 @@ void multiply_masked(spsamd_ctx *c, double C,
 	const uint32_t n_entry = cnt[0], n_wave = cnt[1], n_row = cnt[2];
 	uint32_t *list_entry = c->arena.get<uint32_t>(n_entry + 1), *list_wave = c->arena.get<uint32_t>(n_wave + 1);
 	int32_t *rows = c->arena.get<int32_t>(n_row + 1);
-	if (nm) { k_masked_lists<<<dim3(grid_m(nm)), dim3(256), 0, st>>>(f_entry, f_wave, off_entry, off_wave, nm, list_entry, list_wave); SPS_LAUNCH_CHECK(); }
-	if (n_row) { k_masked_rowlist<<<dim3(grid_m(nrow)), dim3(256), 0, st>>>(rowflag, off_row, nrow, rows); SPS_LAUNCH_CHECK(); }
+	if (nm) { k_masked_lists<<<dim3(grid_for(nm)), dim3(256), 0, st>>>(f_entry, f_wave, off_entry, off_wave, nm, list_entry, list_wave); SPS_LAUNCH_CHECK(); }
+	if (n_row) { k_masked_rowlist<<<dim3(grid_for(nrow)), dim3(256), 0, st>>>(rowflag, off_row, nrow, rows); SPS_LAUNCH_CHECK(); }
 
 	// evaluation: one launch per class
 	SPS_HIP(hipEventRecord(c->ev[2], st));
@@ -548,9 +503,9 @@ void multiply_masked(spsamd_ctx *c, double C,
 	g.sj_pos = sj.present ? sj.pos : nullptr; g.sj_val = sj.val;
 	g.sum = sums; g.emit = emit; g.products = acc;
 	const unsigned cap = (unsigned)c->num_cu * 32u;                    // workgroups of the grid-stride launches
-	if (n_entry) { k_masked_entry<<<dim3(std::min(grid_m(n_entry), cap)), dim3(256), 0, st>>>(g, list_entry, n_entry); SPS_LAUNCH_CHECK(); }
+	if (n_entry) { k_masked_entry<<<dim3(std::min(grid_for(n_entry), cap)), dim3(256), 0, st>>>(g, list_entry, n_entry); SPS_LAUNCH_CHECK(); }
 	if (n_row) { k_masked_row<<<dim3(std::min(n_row, cap)), dim3(256), 0, st>>>(g, rows, n_row, mrp, cls); SPS_LAUNCH_CHECK(); }
-	if (n_wave) { k_masked_wave<<<dim3(std::min(grid_m(n_wave, 4), cap)), dim3(256), 0, st>>>(g, list_wave, n_wave); SPS_LAUNCH_CHECK(); }
+	if (n_wave) { k_masked_wave<<<dim3(std::min(grid_for(n_wave, 4), cap)), dim3(256), 0, st>>>(g, list_wave, n_wave); SPS_LAUNCH_CHECK(); }
 	SPS_HIP(hipEventRecord(c->ev[3], st));
 
 	// sinks
@@ -563,38 +518,19 @@ void multiply_masked(spsamd_ctx *c, double C,
 		read_back_words(c, w2, h);
 		const uint32_t total = h[0];
 		res->products = (uint64_t)h[1] | ((uint64_t)h[2] << 32);
-		OutSet &o = c->out[c->cur_out];
-		c->own[c->cur_out].sort0 = -1;                                   // that set is about to be overwritten
-		o.i.ensure((size_t)total * 4 + 4); o.j.ensure((size_t)total * 4 + 4); o.v.ensure((size_t)total * 8 + 8);
-		int32_t *orow = (int32_t *)o.i.p, *ocol = (int32_t *)o.j.p;
-		double *oval = (double *)o.v.p;
+		const CooOut o = coo_output(c, total);
 		if (total) {
-			k_masked_compact<<<dim3(grid_m(nm)), dim3(256), 0, st>>>(mk.i, mk.j, sums, emit, off, nm, C, si_pos, si.val, sk_pos, sk.val,
-				orow, ocol, oval);
+			k_masked_compact<<<dim3(grid_for(nm)), dim3(256), 0, st>>>(mk.i, mk.j, sums, emit, off, nm, C, si_pos, si.val, sk_pos, sk.val,
+				o.row, o.col, o.val);
 			SPS_LAUNCH_CHECK();
 		}
-		res->nnz = total;
-		res->idx0 = orow; res->idx1 = ocol; res->val = oval;
-		// row-major sorted, every (i, j) once, no zero: consolidated by sort order {0, 1} (read permuted: by {1, 0})
-		auto &w = c->own[c->cur_out];
-		w.d0 = permute ? ocol : orow; w.d1 = permute ? orow : ocol; w.v = oval; w.nnz = total;
-		w.shape0 = res->shape0; w.shape1 = res->shape1; w.sort0 = permute ? 1 : 0;
-		if (permute) std::swap(res->idx0, res->idx1);
+		publish_coo(c, res, o.row, o.col, o.val, total, permute);
 	} else {
-		long long *rn = nullptr; double *rs = nullptr; unsigned long long *rh = nullptr;
-		if (sink_flags & SPSAMD_SINK_ROWSTATS) {
-			c->rowstat_n.ensure(nrow * sizeof(long long) + 8);
-			c->rowstat_s.ensure(nrow * sizeof(double) + 8);
-			c->rowstat_h.ensure(nrow * sizeof(unsigned long long) + 8);
-			fill_zero(c, c->rowstat_n.p, nrow * sizeof(long long));
-			fill_zero(c, c->rowstat_s.p, nrow * sizeof(double));
-			fill_zero(c, c->rowstat_h.p, nrow * sizeof(unsigned long long));
-			rn = (long long *)c->rowstat_n.p; rs = (double *)c->rowstat_s.p; rh = (unsigned long long *)c->rowstat_h.p;
-			res->row_nnz = (const int64_t *)rn; res->row_sum = rs; res->row_hash = (const uint64_t *)rh;
-		}
+		RowStats rs;
+		if (sink_flags & SPSAMD_SINK_ROWSTATS) rs = rowstats_begin(c, nrow, 8, res);      // (8 bytes of slack, as this sink always asked for)
 		if (nm) {
-			k_masked_digest<<<dim3(std::min(grid_m(nm), 2048u)), dim3(256), 0, st>>>(mk.i, mk.j, sums, emit, nm, C, si_pos, si.val, sk_pos,
-				sk.val, acc + 1, rn, rs, rh);
+			k_masked_digest<<<dim3(std::min(grid_for(nm), 2048u)), dim3(256), 0, st>>>(mk.i, mk.j, sums, emit, nm, C, si_pos, si.val, sk_pos,
+				sk.val, acc + 1, rs.nnz, rs.sum, rs.hash);
 			SPS_LAUNCH_CHECK();
 		}
 		unsigned long long *h = (unsigned long long *)c->host_staging(4 * sizeof(unsigned long long));
@@ -605,12 +541,9 @@ void multiply_masked(spsamd_ctx *c, double C,
 		res->hash = h[2];
 		std::memcpy(&res->sum, &h[3], sizeof(double));
 	}
-	SPS_HIP(hipEventRecord(c->ev[7], st));
-	SPS_HIP(hipEventSynchronize(c->ev[7]));
+	finish_call(c, res);
 	SPS_HIP(hipEventElapsedTime(&res->ms_consolidate, c->ev[0], c->ev[1]));
 	SPS_HIP(hipEventElapsedTime(&res->ms_numeric, c->ev[2], c->ev[3]));
-	SPS_HIP(hipEventElapsedTime(&res->ms_total, c->ev[0], c->ev[7]));
-	res->workspace_bytes = c->arena.call_used;
 }
 
 } // namespace spsamd

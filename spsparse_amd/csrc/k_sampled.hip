@@ -34,8 +34,6 @@ struct SampledArgs {
 	double *out;
 };
 
-static unsigned grid_of(size_t n, unsigned bs = 256) { return (unsigned)((n + bs - 1) / bs); }
-
 // o = alpha * d, then + beta * v; the tuple's v is read before its slot is written (out may be M's value array)
 __device__ __forceinline__ void finish(const SampledArgs &a, double d, uint32_t t)
 {
@@ -167,7 +165,7 @@ static bool auto_slab(spsamd_ctx *c, const SampledArgs &a, uint64_t ncol)
 	const uint32_t groups = (a.nnz + 63) / 64, S = std::min(groups, PROBE_GROUPS);
 	uint32_t *counts = c->arena.get<uint32_t>(2);
 	fill_zero(c, counts, 2 * sizeof(uint32_t));
-	k_sampled_probe<<<dim3(grid_of(S)), dim3(256), 0, c->stream>>>(a.row, a.col, a.nnz, S, ncol, counts);
+	k_sampled_probe<<<dim3(grid_for(S)), dim3(256), 0, c->stream>>>(a.row, a.col, a.nnz, S, ncol, counts);
 	SPS_LAUNCH_CHECK();
 	const uint64_t both = read_back(c, (const uint64_t *)counts);
 	const uint32_t local = (uint32_t)both, descending = (uint32_t)(both >> 32);
@@ -186,7 +184,7 @@ static void launch_sampled(spsamd_ctx *c, const SampledArgs &a, uint64_t ncol)
 		if (vec2) k_sampled_slab<2><<<dim3(grid), dim3(64), 0, c->stream>>>(a);
 		else k_sampled_slab<1><<<dim3(grid), dim3(64), 0, c->stream>>>(a);
 	} else {
-		const unsigned grid = std::min<unsigned>(grid_of(a.nnz), (unsigned)c->num_cu * 32);
+		const unsigned grid = std::min<unsigned>(grid_for(a.nnz), (unsigned)c->num_cu * 32);
 		if (vec2) k_sampled_lane<2><<<dim3(grid), dim3(256), 0, c->stream>>>(a);
 		else k_sampled_lane<1><<<dim3(grid), dim3(256), 0, c->stream>>>(a);
 	}
@@ -201,15 +199,6 @@ static bool overlaps(const void *a, uint64_t na, const void *b, uint64_t nb)
 	return a && b && na && nb && (const char *)a < (const char *)b + nb && (const char *)b < (const char *)a + na;
 }
 
-template <class T>
-static const T *to_device(spsamd_ctx *c, const T *p, size_t n, int mem)
-{
-	if (mem != SPSAMD_MEM_HOST || n == 0) return p;
-	T *d = c->arena.get<T>(n);
-	SPS_HIP(hipMemcpyAsync(d, p, n * sizeof(T), hipMemcpyHostToDevice, c->stream));
-	return d;
-}
-
 void multiply_sampled(spsamd_ctx *c, const spsamd_coo *M, char transpose, const double *P, size_t ldp, const double *Q,
 	size_t ldq, size_t k, double alpha, double beta, double *out, int mem)
 {
@@ -222,29 +211,17 @@ void multiply_sampled(spsamd_ctx *c, const spsamd_coo *M, char transpose, const 
 	// (the kernels count r in 32 bits and step it by up to SLAB: k < 2^31 keeps r + SLAB from wrapping)
 	if (k >= (size_t(1) << 31)) throw Error{SPSAMD_EINVAL, "k is 2^31 or more"};
 	// the tuples: a prepared operand's consolidated ones (its lead's order), else M's arrays as stored
-	const Prepared *prep = nullptr;
-	const int32_t *i0 = M->idx0, *i1 = M->idx1;
-	const double *v = M->val;
-	size_t n = M->nnz;
-	int mmem = M->mem;
-	if (M->mem == SPSAMD_MEM_PREPARED) {
-		prep = (const Prepared *)M->idx0;
-		if (!prep || prep->ctx != c) throw Error{SPSAMD_EINVAL, "a prepared operand belongs to the context that prepared it"};
-		i0 = prep->lead == 0 ? prep->m.row : prep->m.col;
-		i1 = prep->lead == 0 ? prep->m.col : prep->m.row;
-		v = prep->m.val; n = prep->m.nnz; mmem = SPSAMD_MEM_DEVICE;
-	} else if (M->mem != SPSAMD_MEM_HOST && M->mem != SPSAMD_MEM_DEVICE) {
-		throw Error{SPSAMD_EINVAL, "bad mem of M"};
-	}
+	const OperandView view = operand_view(c, M);
+	const Prepared *prep = view.prep;
+	const int32_t *i0 = view.coo.idx0, *i1 = view.coo.idx1;
+	const double *v = view.coo.val;
+	const size_t n = view.coo.nnz;
+	const int mmem = view.coo.mem;
+	check_operand(view.coo, OPERAND_PLAIN_MEM);                        // a bad mem is refused even where M is empty; val: below
 	if (n == 0) return;
-	if (n >= (size_t(1) << 31))
-		throw Error{SPSAMD_EINVAL, "operand has 2^31 or more tuples (the reference's int positions cap it too, algorithm.hpp:419)"};
-	if (!i0 || !i1) throw Error{SPSAMD_EINVAL, "operand with nnz > 0 has a null index array"};
 	if (k && (!P || !Q)) throw Error{SPSAMD_EINVAL, "null P or Q"};
 	if (!out) throw Error{SPSAMD_EINVAL, "null out"};
 	if (beta != 0 && !v) throw Error{SPSAMD_EINVAL, "beta != 0 reads M's values, and M->val is null"};
-	if (shape[0] > (uint64_t(1) << 31) || shape[1] > (uint64_t(1) << 31))
-		throw Error{SPSAMD_EINVAL, "shape exceeds the int32 index range"};
 	// the bytes each array spans: rows - 1 full leading dimensions and k values
 	const uint64_t obytes = n * sizeof(double);
 	const uint64_t pbytes = nrow && k ? ((nrow - 1) * ldp + k) * sizeof(double) : 0;
@@ -256,11 +233,7 @@ void multiply_sampled(spsamd_ctx *c, const spsamd_coo *M, char transpose, const 
 	SPS_HIP(hipSetDevice(c->device));
 	c->arena.reset();
 	// a SINK_COO result of this context handed back in: valid indices
-	bool own_result = prep != nullptr;
-	if (M->mem == SPSAMD_MEM_DEVICE)
-		for (const auto &o : c->own)
-			if (o.sort0 >= 0 && o.sort0 == M->sort0 && o.d0 == M->idx0 && o.d1 == M->idx1 && o.v == M->val && o.nnz == n &&
-				o.shape0 == M->shape0 && o.shape1 == M->shape1) own_result = true;
+	const bool own_result = prep || is_own_result(c, *M);
 	const int32_t *d0 = to_device(c, i0, n, mmem), *d1 = to_device(c, i1, n, mmem);
 	const double *dv = beta != 0 ? to_device(c, v, n, mmem) : nullptr;
 	SampledArgs a;

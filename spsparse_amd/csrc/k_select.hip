@@ -32,8 +32,6 @@ constexpr int SEL_ROUNDS = 8;
 constexpr int SEL_TILE = 64 * SEL_ROUNDS;      // tuples per wave of the flag / count / compact kernels
 constexpr uint64_t SEL_INF = 0x7FF0000000000000ull;
 
-static unsigned grid_sel(size_t n, unsigned bs = 256) { return (unsigned)((n + bs - 1) / bs); }
-
 __device__ __forceinline__ uint64_t mag_of(double v) { return (uint64_t)__double_as_longlong(v) & 0x7FFFFFFFFFFFFFFFull; }
 
 struct SelArgs {
@@ -310,26 +308,10 @@ __global__ void __launch_bounds__(SEL_HEAVY_NT) k_sel_topk_heavy(const uint32_t 
 	sel_row<SEL_HEAVY_NT>([&](uint32_t i) { return mag_of(v[i]); }, n, k, flip, keep + beg, s);
 }
 
-// DIGEST sink over the stored tuples: index hash, sum (and the per-row statistics under ROWSTATS)
-__global__ void __launch_bounds__(256) k_sel_digest(const int32_t *__restrict__ row, const int32_t *__restrict__ col,
-	const double *__restrict__ val, uint32_t n, unsigned long long *hash, double *sum,
-	long long *row_nnz, double *row_sum, unsigned long long *row_hash)
-{
-	unsigned long long h = 0;
-	double s = 0;
-	for (uint32_t t = blockIdx.x * blockDim.x + threadIdx.x; t < n; t += gridDim.x * blockDim.x) {
-		const unsigned long long x = mix64((uint32_t)row[t], (uint32_t)col[t]);
-		h += x; s += val[t];
-		if (row_nnz) { atomicAdd((unsigned long long *)&row_nnz[row[t]], 1ull); atomicAdd(&row_sum[row[t]], val[t]); atomicAdd(&row_hash[row[t]], x); }
-	}
-	h = wave_reduce_sum(h); s = wave_reduce_sum(s);
-	if (lane_id() == 0) { atomicAdd(hash, h); atomicAdd(sum, s); }
-}
-
 template <int PRED>
 static void launch_flag(spsamd_ctx *c, const SelArgs &a, uint32_t ntiles, uint8_t *keep, uint32_t *tile_count)
 {
-	k_sel_flag<PRED><<<dim3(grid_sel(ntiles, 4)), dim3(256), 0, c->stream>>>(a, keep, tile_count);
+	k_sel_flag<PRED><<<dim3(grid_for(ntiles, 4)), dim3(256), 0, c->stream>>>(a, keep, tile_count);
 	SPS_LAUNCH_CHECK();
 }
 
@@ -380,7 +362,7 @@ void select_tuples(spsamd_ctx *c, const spsamd_coo *A, char transpose, int predi
 	case SPSAMD_SELECT_ROW_REL: {
 		unsigned long long *rowmax = c->arena.get<unsigned long long>(nrow ? nrow : 1);
 		fill_zero(c, rowmax, nrow * sizeof(unsigned long long));
-		k_sel_rowmax<<<dim3(grid_sel(n)), dim3(256), 0, st>>>(S.row, S.val, n, rowmax);
+		k_sel_rowmax<<<dim3(grid_for(n)), dim3(256), 0, st>>>(S.row, S.val, n, rowmax);
 		SPS_LAUNCH_CHECK();
 		a.rowmax = rowmax;
 		launch_flag<SPSAMD_SELECT_ROW_REL>(c, a, ntiles, keep, tile_count);
@@ -394,7 +376,7 @@ void select_tuples(spsamd_ctx *c, const spsamd_coo *A, char transpose, int predi
 		const size_t cap = (size_t)std::min<uint64_t>(nrow, n);
 		uint32_t *cnt = c->arena.get<uint32_t>(8), *mid_list = c->arena.get<uint32_t>(cap + 1), *heavy_list = c->arena.get<uint32_t>(cap + 1);
 		fill_zero(c, cnt, 8 * sizeof(uint32_t));
-		k_sel_classify<<<dim3(grid_sel(nrow)), dim3(256), 0, st>>>(ptr, nrow, k, path, cnt, mid_list, heavy_list);
+		k_sel_classify<<<dim3(grid_for(nrow)), dim3(256), 0, st>>>(ptr, nrow, k, path, cnt, mid_list, heavy_list);
 		SPS_LAUNCH_CHECK();
 		uint32_t *h = (uint32_t *)c->host_staging(8 * sizeof(uint32_t));
 		SPS_HIP(hipMemcpyAsync(h, cnt, 8 * sizeof(uint32_t), hipMemcpyDeviceToHost, st));
@@ -402,10 +384,10 @@ void select_tuples(spsamd_ctx *c, const spsamd_coo *A, char transpose, int predi
 		const uint32_t nl = h[0], nm = h[1], nh = h[2];
 		res->rows_light = nl; res->rows_mid = nm; res->rows_heavy = nh;
 		res->tuples_light = h[3]; res->tuples_mid = h[4]; res->tuples_heavy = h[5];
-		if (nl) { k_sel_topk_light<<<dim3(grid_sel(nrow)), dim3(256), 0, st>>>(ptr, nrow, S.val, k, path, flip, keep); SPS_LAUNCH_CHECK(); }
+		if (nl) { k_sel_topk_light<<<dim3(grid_for(nrow)), dim3(256), 0, st>>>(ptr, nrow, S.val, k, path, flip, keep); SPS_LAUNCH_CHECK(); }
 		if (nm) { k_sel_topk_mid<<<dim3(nm), dim3(SEL_MID_NT), 0, st>>>(mid_list, ptr, S.val, k, flip, keep); SPS_LAUNCH_CHECK(); }
 		if (nh) { k_sel_topk_heavy<<<dim3(nh), dim3(SEL_HEAVY_NT), 0, st>>>(heavy_list, ptr, S.val, k, flip, keep); SPS_LAUNCH_CHECK(); }
-		k_sel_count<<<dim3(grid_sel(ntiles, 4)), dim3(256), 0, st>>>(keep, n, tile_count);
+		k_sel_count<<<dim3(grid_for(ntiles, 4)), dim3(256), 0, st>>>(keep, n, tile_count);
 		SPS_LAUNCH_CHECK();
 		break;
 	}
@@ -413,60 +395,18 @@ void select_tuples(spsamd_ctx *c, const spsamd_coo *A, char transpose, int predi
 	scan_exclusive_u32_u32(c, tile_count, tile_off, ntiles);
 	const uint32_t total = read_back(c, tile_off + ntiles);
 
-	int32_t *orow, *ocol;
-	double *oval;
-	if (coo) {
-		OutSet &o = c->out[c->cur_out];
-		c->own[c->cur_out].sort0 = -1;                                 // that set is about to be overwritten
-		o.i.ensure((size_t)total * 4 + 4); o.j.ensure((size_t)total * 4 + 4); o.v.ensure((size_t)total * 8 + 8);
-		orow = (int32_t *)o.i.p; ocol = (int32_t *)o.j.p; oval = (double *)o.v.p;
-	} else {
-		orow = c->arena.get<int32_t>((size_t)total + 1); ocol = c->arena.get<int32_t>((size_t)total + 1);
-		oval = c->arena.get<double>((size_t)total + 1);
-	}
+	const CooOut o = coo ? coo_output(c, total) : scratch_output(c, total);
 	if (total) {
-		k_sel_compact<<<dim3(grid_sel(ntiles, 4)), dim3(256), 0, st>>>(S.row, S.col, S.val, n, keep, tile_off, orow, ocol, oval);
+		k_sel_compact<<<dim3(grid_for(ntiles, 4)), dim3(256), 0, st>>>(S.row, S.col, S.val, n, keep, tile_off, o.row, o.col, o.val);
 		SPS_LAUNCH_CHECK();
 	}
 	res->nnz = total;
-
-	if (coo) {
-		res->idx0 = orow; res->idx1 = ocol; res->val = oval;
-		// a subsequence of S: in op(A)'s row order (read permuted: sorted by {1, 0}), indices checked
-		auto &w = c->own[c->cur_out];
-		w.d0 = permute ? ocol : orow; w.d1 = permute ? orow : ocol; w.v = oval; w.nnz = total;
-		w.shape0 = res->shape0; w.shape1 = res->shape1; w.sort0 = permute ? 1 : 0;
-		if (permute) std::swap(res->idx0, res->idx1);
-	} else {
-		unsigned long long *hs = c->arena.get<unsigned long long>(2);
-		fill_zero(c, hs, 2 * sizeof(unsigned long long));
-		long long *rn = nullptr; double *rs = nullptr; unsigned long long *rh = nullptr;
-		if (sink_flags & SPSAMD_SINK_ROWSTATS) {
-			c->rowstat_n.ensure(nrow * sizeof(long long) + 8);
-			c->rowstat_s.ensure(nrow * sizeof(double) + 8);
-			c->rowstat_h.ensure(nrow * sizeof(unsigned long long) + 8);
-			fill_zero(c, c->rowstat_n.p, nrow * sizeof(long long));
-			fill_zero(c, c->rowstat_s.p, nrow * sizeof(double));
-			fill_zero(c, c->rowstat_h.p, nrow * sizeof(unsigned long long));
-			rn = (long long *)c->rowstat_n.p; rs = (double *)c->rowstat_s.p; rh = (unsigned long long *)c->rowstat_h.p;
-			res->row_nnz = (const int64_t *)rn; res->row_sum = rs; res->row_hash = (const uint64_t *)rh;
-		}
-		if (total) {
-			k_sel_digest<<<dim3(std::min(grid_sel(total), 2048u)), dim3(256), 0, st>>>(orow, ocol, oval, total, hs, (double *)(hs + 1), rn, rs, rh);
-			SPS_LAUNCH_CHECK();
-		}
-		unsigned long long *h = (unsigned long long *)c->host_staging(2 * sizeof(unsigned long long));
-		SPS_HIP(hipMemcpyAsync(h, hs, 2 * sizeof(unsigned long long), hipMemcpyDeviceToHost, st));
-		SPS_HIP(hipStreamSynchronize(st));
-		res->hash = h[0];
-		std::memcpy(&res->sum, &h[1], sizeof(double));
-	}
-	SPS_HIP(hipEventRecord(c->ev[7], st));
-	SPS_HIP(hipEventSynchronize(c->ev[7]));
+	// a subsequence of S: in op(A)'s row order (read permuted: sorted by {1, 0}), indices checked
+	if (coo) publish_coo(c, res, o.row, o.col, o.val, total, permute);
+	else digest_stored(c, res, o.row, o.col, o.val, total, nrow, sink_flags);
+	finish_call(c, res);
 	SPS_HIP(hipEventElapsedTime(&res->ms_consolidate, c->ev[0], c->ev[1]));
 	SPS_HIP(hipEventElapsedTime(&res->ms_numeric, c->ev[1], c->ev[7]));
-	SPS_HIP(hipEventElapsedTime(&res->ms_total, c->ev[0], c->ev[7]));
-	res->workspace_bytes = c->arena.call_used;
 }
 
 } // namespace spsamd

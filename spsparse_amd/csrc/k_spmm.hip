@@ -21,8 +21,6 @@
 
 namespace spsamd {
 
-static unsigned grid_of(size_t n, unsigned bs = 256) { return (unsigned)((n + bs - 1) / bs); }
-
 // One step of DenseAccum::add (accum.hpp:124-135) on the entry y with the product p.
 template <int POLICY, bool HNAN>
 __device__ __forceinline__ void accum(double &y, double p)
@@ -152,14 +150,14 @@ static void launch_spmm(spsamd_ctx *c, const DenseOperand &m, const double *X, u
 	const uint32_t long_min = path == 1 ? 0xFFFFFFFFu : path >= 2 ? 0u : c->tune.spmm_long_min > 0 ? (uint32_t)c->tune.spmm_long_min : 64u;
 	if (path != 2 && path != 3) {
 		const uint64_t total = m.nrow * nrhs;
-		const unsigned grid = (unsigned)std::min<uint64_t>(grid_of(total), (uint64_t)c->num_cu * 64);
+		const unsigned grid = (unsigned)std::min<uint64_t>(grid_for(total), (uint64_t)c->num_cu * 64);
 		k_spmm_serial<POLICY, HNAN><<<dim3(grid), dim3(256), 0, st>>>(m.rowptr, m.tup, m.nrow, X, ldx, Y, ldy, nrhs, long_min);
 		SPS_LAUNCH_CHECK();
 	}
 	if (path == 1) return;
 	uint32_t *count = c->arena.get<uint32_t>(1), *list = c->arena.get<uint32_t>(m.nrow ? m.nrow : 1);
 	fill_zero(c, count, sizeof(uint32_t));
-	k_spmm_long_rows<<<dim3(grid_of(m.nrow)), dim3(256), 0, st>>>(m.rowptr, m.nrow, long_min, list, count);
+	k_spmm_long_rows<<<dim3(grid_for(m.nrow)), dim3(256), 0, st>>>(m.rowptr, m.nrow, long_min, list, count);
 	SPS_LAUNCH_CHECK();
 	// persistent waves over the list (its length stays on the device)
 	const unsigned waves = (unsigned)c->num_cu * 8;
@@ -216,62 +214,32 @@ __global__ void k_gather_rows(const uint64_t *__restrict__ keys, const uint32_t 
 	row[i] = (int32_t)keys[i];
 }
 
-static int bits_of(uint64_t dim)
-{
-	int b = 0;
-	while (b < 63 && (uint64_t(1) << b) < dim) ++b;
-	return b;
-}
-
-template <class T>
-static const T *on_device(spsamd_ctx *c, const T *p, size_t n, int mem)
-{
-	if (mem != SPSAMD_MEM_HOST || n == 0) return p;
-	T *d = c->arena.get<T>(n);
-	SPS_HIP(hipMemcpyAsync(d, p, n * sizeof(T), hipMemcpyHostToDevice, c->stream));
-	return d;
-}
-
 void dense_operand(spsamd_ctx *c, const spsamd_coo *M, int lead, DenseOperand *out)
 {
 	const uint64_t shape[2] = {M->shape0, M->shape1};
 	out->nrow = shape[lead]; out->ncol = shape[1 - lead];
 	out->nnz = 0; out->rowptr = nullptr; out->tup = nullptr; out->sorted = false;
-	if (M->mem == SPSAMD_MEM_PREPARED) {
-		Prepared *p = (Prepared *)const_cast<int32_t *>(M->idx0);
-		if (!p || p->ctx != c) throw Error{SPSAMD_EINVAL, "a prepared operand belongs to the context that prepared it"};
-		if (p->lead == lead) {
-			// consolidated by the output row already: its packed tuples and dense row pointer (both kept in the handle)
-			out->nnz = p->m.nnz;
-			if (!out->nnz) return;
-			prepared_row_structure(c, p);
-			out->rowptr = p->rowptr;
-			out->tup = prepared_btup(c, p);
-			return;
-		}
-		spsamd_coo Y;                                                  // prepared the other way round: its tuples as stored
-		Y.idx0 = p->lead == 0 ? p->m.row : p->m.col; Y.idx1 = p->lead == 0 ? p->m.col : p->m.row; Y.val = p->m.val;
-		Y.nnz = p->m.nnz; Y.shape0 = M->shape0; Y.shape1 = M->shape1; Y.sort0 = p->lead; Y.mem = SPSAMD_MEM_DEVICE;
-		dense_operand(c, &Y, lead, out);
+	const OperandView view = operand_view(c, M);
+	if (view.prep && view.prep->lead == lead) {
+		// consolidated by the output row already: its packed tuples and dense row pointer (both kept in the handle)
+		Prepared *p = view.prep;
+		out->nnz = p->m.nnz;
+		if (!out->nnz) return;
+		prepared_row_structure(c, p);
+		out->rowptr = p->rowptr;
+		out->tup = prepared_btup(c, p);
 		return;
 	}
+	M = &view.coo;                                                     // (prepared the other way round: its tuples as stored)
 	const size_t n = M->nnz;
 	if (n == 0) return;
-	if (n >= (size_t(1) << 31))
-		throw Error{SPSAMD_EINVAL, "operand has 2^31 or more tuples (the reference's int positions cap it too, algorithm.hpp:419)"};
-	if (!M->idx0 || !M->idx1 || !M->val) throw Error{SPSAMD_EINVAL, "operand with nnz > 0 has a null array"};
-	if (shape[0] > (uint64_t(1) << 31) || shape[1] > (uint64_t(1) << 31))
-		throw Error{SPSAMD_EINVAL, "shape exceeds the int32 index range"};
+	check_operand(*M, OPERAND_VALUES);                                 // (mem was never checked here: whatever is not HOST is read as device memory)
 	out->nnz = (uint32_t)n;
 	// a SINK_COO result of this context handed back in: valid indices, ascending rows (by sort0)
-	bool own_result = false;
-	if (M->mem == SPSAMD_MEM_DEVICE)
-		for (const auto &o : c->own)
-			if (o.sort0 >= 0 && o.sort0 == M->sort0 && o.d0 == M->idx0 && o.d1 == M->idx1 && o.v == M->val && o.nnz == n &&
-				o.shape0 == M->shape0 && o.shape1 == M->shape1) own_result = true;
-	const int32_t *d0 = on_device(c, M->idx0, n, M->mem);
-	const int32_t *d1 = on_device(c, M->idx1, n, M->mem);
-	const double *dv = on_device(c, M->val, n, M->mem);
+	const bool own_result = is_own_result(c, *M);
+	const int32_t *d0 = to_device(c, M->idx0, n, M->mem);
+	const int32_t *d1 = to_device(c, M->idx1, n, M->mem);
+	const double *dv = to_device(c, M->val, n, M->mem);
 	const int32_t *major = lead == 0 ? d0 : d1, *minor = lead == 0 ? d1 : d0;
 	bool ordered = own_result && M->sort0 == lead;
 	if (!own_result) {
@@ -283,18 +251,18 @@ void dense_operand(spsamd_ctx *c, const spsamd_coo *M, int lead, DenseOperand *o
 	ConMat rows;
 	rows.nnz = (uint32_t)n; rows.nrow = out->nrow; rows.ncol = out->ncol;
 	if (ordered) {
-		k_pack_rows<<<dim3(grid_of(n)), dim3(256), 0, c->stream>>>(minor, dv, (uint32_t)n, tup);
+		k_pack_rows<<<dim3(grid_for(n)), dim3(256), 0, c->stream>>>(minor, dv, (uint32_t)n, tup);
 		SPS_LAUNCH_CHECK();
 		rows.row = const_cast<int32_t *>(major);
 	} else {
 		// one stable radix pass set keyed on the output row alone, storage position as payload
 		uint64_t *keys0 = c->arena.get<uint64_t>(n), *keys1 = c->arena.get<uint64_t>(n);
 		uint32_t *pay0 = c->arena.get<uint32_t>(n), *pay1 = c->arena.get<uint32_t>(n);
-		k_row_keys<<<dim3(grid_of(n)), dim3(256), 0, c->stream>>>(major, (uint32_t)n, keys0);
+		k_row_keys<<<dim3(grid_for(n)), dim3(256), 0, c->stream>>>(major, (uint32_t)n, keys0);
 		SPS_LAUNCH_CHECK();
 		const int where = radix_sort_pairs(c, keys0, pay0, keys1, pay1, n, bits_of(out->nrow));
 		int32_t *srow = c->arena.get<int32_t>(n);
-		k_gather_rows<<<dim3(grid_of(n)), dim3(256), 0, c->stream>>>(where ? keys1 : keys0, where ? pay1 : pay0, minor, dv, (uint32_t)n, srow, tup);
+		k_gather_rows<<<dim3(grid_for(n)), dim3(256), 0, c->stream>>>(where ? keys1 : keys0, where ? pay1 : pay0, minor, dv, (uint32_t)n, srow, tup);
 		SPS_LAUNCH_CHECK();
 		rows.row = srow;
 		out->sorted = true;

@@ -217,21 +217,13 @@ int multiply_stream(spsamd_ctx *c, double C,
 	if (stats) *stats = st;
 	const unsigned long long budget = st.block_tuples;
 	// shape, inner dimension and short-circuits exactly as spsamd_multiply (multiply_sparse.hpp:167-184)
-	const int a0 = transpose_A == 'T' ? 1 : 0, a1 = 1 - a0;
-	const int bk = transpose_B == 'T' ? 1 : 0, bj = 1 - bk;
-	const size_t ashape[2] = {A->shape0, A->shape1}, bshape[2] = {B->shape0, B->shape1};
 	const bool permute = (sink_flags & SPSAMD_SINK_PERMUTE) != 0;
-	res->shape0 = permute ? bshape[bj] : ashape[a0];
-	res->shape1 = permute ? ashape[a0] : bshape[bj];
-	if (ashape[a1] != bshape[bk]) {
-		char buf[160];
-		std::snprintf(buf, sizeof buf, "Inner dimensions for A (%ld) and B (%ld) must match!", (long)ashape[a1], (long)bshape[bk]);
-		throw Error{SPSAMD_EDIM, buf};
-	}
+	const ProductFrame f(A, transpose_A, B, transpose_B, permute);
+	const int a0 = f.a0, bk = f.bk, bj = f.bj;
+	res->shape0 = f.shape0; res->shape1 = f.shape1;
+	f.check_inner("B");
 	auto finish = [&](int rc) { st.ms_wall = ms_since(t_call); if (stats) *stats = st; return rc; };
-	if (C == 0 || (scalei && scalei->nnz == 0) || A->nnz == 0 || (scalej && scalej->nnz == 0) ||
-		B->nnz == 0 || (scalek && scalek->nnz == 0))
-		return finish(SPSAMD_OK);
+	if (product_is_empty(C, scalei, A, scalej, B, scalek)) return finish(SPSAMD_OK);
 	// the same refusal as spsamd_multiply's, although this call writes neither output set
 	const spsamd_coo *ops[2] = {A, B};
 	if (output_set_aliased(c, 0, ops, 2) && output_set_aliased(c, 1, ops, 2))
@@ -247,9 +239,9 @@ int multiply_stream(spsamd_ctx *c, double C,
 	consolidate_operand(c, A, a0, a0, duplicate_policy, zero_nan, &a.A, &hpa);
 	if (a0 == bk && same_operand(A, B) && (!zero_nan || hpa)) { a.B = a.A; hpb = hpa; }
 	else consolidate_operand(c, B, bk, bj, duplicate_policy, zero_nan, &a.B, &hpb);
-	upload_scale(c, scalei, ashape[a0], "scalei", &a.si);
-	upload_scale(c, scalej, ashape[a1], "scalej", &a.sj);
-	upload_scale(c, scalek, bshape[bj], "scalek", &a.sk);
+	upload_scale(c, scalei, f.nrow, "scalei", &a.si);
+	upload_scale(c, scalej, f.inner, "scalej", &a.sj);
+	upload_scale(c, scalek, f.ncol, "scalek", &a.sk);
 	SPS_HIP(hipEventRecord(c->ev[1], s0));
 	const ConMat Am = a.A, Bm = a.B;
 	res->nnz_a = Am.nnz; res->nnz_b = Bm.nnz;

@@ -319,21 +319,11 @@ __global__ void k_block_place(const int32_t *i, const int32_t *j, const double *
 	oi[d] = r; oj[d] = j[t]; ov[d] = v[t];
 }
 
-// DIGEST | ROWSTATS: the context's three per-row arrays (tuple count, value sum, index hash), zeroed
+// DIGEST | ROWSTATS: the shared row statistics (sink.hip; no slack, as the multiply always asked) handed to the kernels' sink
 static void rowstats_begin(spsamd_ctx *c, uint64_t nrow, SinkParams &sk, spsamd_result *res)
 {
-	c->rowstat_n.ensure(nrow * sizeof(long long));
-	c->rowstat_s.ensure(nrow * sizeof(double));
-	c->rowstat_h.ensure(nrow * sizeof(unsigned long long));
-	fill_zero(c, c->rowstat_n.p, nrow * sizeof(long long));
-	fill_zero(c, c->rowstat_s.p, nrow * sizeof(double));
-	fill_zero(c, c->rowstat_h.p, nrow * sizeof(unsigned long long));
-	sk.row_nnz = (long long *)c->rowstat_n.p;
-	sk.row_sum = (double *)c->rowstat_s.p;
-	sk.row_hash = (unsigned long long *)c->rowstat_h.p;
-	res->row_nnz = (const int64_t *)sk.row_nnz;
-	res->row_sum = sk.row_sum;
-	res->row_hash = (const uint64_t *)sk.row_hash;
+	const RowStats rs = rowstats_begin(c, nrow, 0, res);
+	sk.row_nnz = rs.nnz; sk.row_sum = rs.sum; sk.row_hash = rs.hash;
 }
 
 static void spgemm_all_light(spsamd_ctx *c, MultiplyArgs &a, spsamd_result *res, const uint32_t *aptr, const int32_t *acol, const double *aval,

@@ -4,8 +4,6 @@
 
 namespace spsamd {
 
-static inline unsigned grid_for(size_t n, unsigned bs = 256) { return (unsigned)((n + bs - 1) / bs); }
-
 struct Bins {
 	uint32_t count[NBIN];
 	uint32_t off[NBIN + 1];
