@@ -145,7 +145,7 @@ int spsamd::multiply_body(spsamd_ctx *c, double C,
 	SPS_HIP(hipSetDevice(c->device));
 	if (!arena_ready) c->arena.reset();
 	hipStream_t st = c->stream;
-	SPS_HIP(hipEventRecord(c->ev[0], st));
+	SPS_HIP(hipEventRecord(c->ev[EV_BEGIN], st));
 	// (also for the digest sink: a product by column blocks, spgemm_column_blocks, goes through the COO buffers)
 	{ const spsamd_coo *ops[2] = {A, B}; pick_output_set(c, ops, 2); }
 	MultiplyArgs a;
@@ -169,7 +169,7 @@ int spsamd::multiply_body(spsamd_ctx *c, double C,
 	if (sink_kind == SPSAMD_SINK_COO && res->idx0 && res->idx1) publish_coo(c, res, res->idx0, res->idx1, res->val, res->nnz, permute);
 	finish_call(c, res);
 	if (res->nnz_a && res->nnz_b) {
-		SPS_HIP(hipEventElapsedTime(&res->ms_consolidate, c->ev[0], c->ev[1]));
+		SPS_HIP(hipEventElapsedTime(&res->ms_consolidate, c->ev[EV_BEGIN], c->ev[EV_CONSOLIDATED]));
 	}
 	return SPSAMD_OK;
 }
@@ -373,7 +373,7 @@ extern "C" int spsamd_result_fetch(spsamd_ctx *c, const spsamd_result *res, spsa
 		// callback consumes chunk k (the callback, one ret.add() per tuple upstream, is the slow side)
 		const size_t chunk = size_t(1) << 20;
 		char *h = (char *)c->host_staging(2 * chunk * 16);
-		hipEvent_t ev[2] = {c->ev[8], c->ev[9]};
+		hipEvent_t ev[2] = {c->ev[EV_FETCH0], c->ev[EV_FETCH1]};
 		auto issue = [&](uint64_t o, int b) {
 			size_t n = (size_t)std::min<uint64_t>(chunk, res->nnz - o);
 			char *hb = h + (size_t)b * chunk * 16;

@@ -68,9 +68,6 @@ struct OutSet {
 	void release() { i.release(); j.release(); v.release(); }
 };
 
-} // namespace spsamd
-
-namespace spsamd {
 // Developer knobs of one context.  Read from the environment ONCE, at spsamd_ctx_create (one SPSAMD_* variable per knob:
 // the `knobs` / `envs` table there, capi.hip), or set through spsamd_ctx_set_tuning; results are identical for every setting.
 struct Tuning {
@@ -116,8 +113,8 @@ struct spsamd_ctx {
 	void *pinned = nullptr;                  // host staging for small readbacks / fetch
 	size_t pinned_cap = 0;
 	std::string last_error;
-	hipEvent_t ev[10] = {};
-	hipEvent_t ev2[3] = {};                  // around the tile launches of the heavy rows
+	hipEvent_t ev[10] = {};                  // timing marks of a call, by Ev (below)
+	hipEvent_t ev2[3] = {};                  // around the tile launches of the heavy rows, by Ev2
 	hipStream_t side = nullptr;              // second stream: the window-major copy of B is built on it beside the rest of the symbolic phase
 	hipEvent_t ev_side[2] = {};              // [0] main -> side (inputs ready), [1] side -> main (copy built: waited for just before the dense cells)
 	hipStream_t side2 = nullptr;             // third stream: the cell lists are sorted on it beside the light and mid rows' kernels
@@ -132,6 +129,22 @@ struct spsamd_ctx {
 };
 
 namespace spsamd {
+
+// What each event of spsamd_ctx::ev marks for the multiply.  The stand-alone operations share 0, 1 and 7 and reuse 2 and
+// 3 for stages of their own: k_masked.hip for the begin and end of its numeric kernels, k_stream.hip 2 for its set-up done.
+enum Ev {
+	EV_NONE = -1,           // (no event: spgemm.hip's launch_pass)
+	EV_BEGIN = 0,           // the call begins
+	EV_CONSOLIDATED = 1,    // operands consolidated: the symbolic phase begins
+	EV_SYMBOLIC = 2,        // symbolic phase done: the numeric phase begins
+	EV_N0 = 3,              // numeric marks.  DIGEST: before the light rows | COO: before the COUNT pass
+	EV_N1 = 4,              //   DIGEST: light rows done | COO: output grown, before the STORE pass | all rows light: kernels done
+	EV_N2 = 5,              //   DIGEST: mid rows done | COO: light and mid rows stored
+	EV_N3 = 6,              //   the heavy rows' hash cells done (COO: stored)
+	EV_END = 7,             // the call ends (finish_call)
+	EV_N4 = 8,              //   the heavy rows' dense cells done (COO: stored)
+	EV_FETCH0 = EV_N4, EV_FETCH1 = 9 };     // spsamd_result_fetch, between calls: its two chunks in flight
+enum Ev2 { EV2_TILES_BEGIN = 0, EV2_TILES_END = 1, EV2_DIRECT_END = 2 };   // the tiles, then the direct tiles
 
 // ---------------------------------------------------------------- primitives (prims.hip)
 
@@ -163,6 +176,7 @@ int radix_sort_pairs(spsamd_ctx *c, uint64_t *keys0, uint32_t *pay0, uint64_t *k
 
 void fill_u32(spsamd_ctx *c, uint32_t *p, uint32_t v, size_t n);
 void fill_zero(spsamd_ctx *c, void *p, size_t bytes);
+template <class T> T *get_zeroed(spsamd_ctx *c, size_t n) { T *p = c->arena.get<T>(n); fill_zero(c, p, n * sizeof(T)); return p; }   // workspace memory
 
 template <class T>
 T read_back(spsamd_ctx *c, const T *dev)
@@ -425,7 +439,9 @@ void pick_output_set(spsamd_ctx *c, const spsamd_coo *const *operands, int n);
 bool output_set_aliased(const spsamd_ctx *c, int s, const spsamd_coo *const *operands, int n);
 
 struct CooOut { int32_t *row, *col; double *val; };
-// The current output set, about to be overwritten (its entry of c->own is dropped), grown to `total` tuples.
+// An output set grown to `total` tuples: the one way its three arrays are asked for.
+CooOut grow_output(OutSet &o, size_t total);
+// The current output set, about to be overwritten (its entry of c->own is dropped), grown to `total` + 1 tuples.
 CooOut coo_output(spsamd_ctx *c, size_t total);
 // Workspace arrays for `total` tuples: where the DIGEST sink of an operation that stores its tuples first keeps them.
 CooOut scratch_output(spsamd_ctx *c, size_t total);
@@ -440,7 +456,7 @@ RowStats rowstats_begin(spsamd_ctx *c, uint64_t nrow, size_t slack, spsamd_resul
 // SINK_DIGEST over stored tuples: the row statistics if sink_flags asks, index hash and value sum into res.
 void digest_stored(spsamd_ctx *c, spsamd_result *res, const int32_t *orow, const int32_t *ocol, const double *oval, uint32_t total,
 	uint64_t nrow, int sink_flags);
-// The end of a call: ev[7] recorded and waited for, ms_total (from ev[0]) and workspace_bytes filled.
+// The end of a call: EV_END recorded and waited for, ms_total (from EV_BEGIN) and workspace_bytes filled.
 void finish_call(spsamd_ctx *c, spsamd_result *res);
 
 } // namespace spsamd

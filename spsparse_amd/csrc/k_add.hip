@@ -304,14 +304,14 @@ void add_matrices(spsamd_ctx *c, double alpha, const spsamd_coo *A, char transpo
 	SPS_HIP(hipSetDevice(c->device));
 	c->arena.reset();
 	hipStream_t st = c->stream;
-	SPS_HIP(hipEventRecord(c->ev[0], st));
+	SPS_HIP(hipEventRecord(c->ev[EV_BEGIN], st));
 	if (coo) { const spsamd_coo *ops[2] = {A, B}; pick_output_set(c, ops, 2); }
 	const bool force_sort = c->tune.add_path == 1;
 	AddStream sa, sb;
 	bool sorted_a = false, sorted_b = false;
 	add_stream(c, A, la, force_sort, &sa, &sorted_a);
 	add_stream(c, B, lb, force_sort, &sb, &sorted_b);
-	SPS_HIP(hipEventRecord(c->ev[1], st));
+	SPS_HIP(hipEventRecord(c->ev[EV_CONSOLIDATED], st));
 
 	const uint64_t n = (uint64_t)sa.n + sb.n;
 	const uint32_t ntiles = (uint32_t)((n + ADD_TILE - 1) / ADD_TILE);
@@ -343,7 +343,7 @@ void add_matrices(spsamd_ctx *c, double alpha, const spsamd_coo *A, char transpo
 	if (coo) publish_coo(c, res, o.row, o.col, o.val, total, permute);
 	else digest_stored(c, res, o.row, o.col, o.val, total, nrow, sink_flags);
 	finish_call(c, res);
-	if (sorted_a || sorted_b) SPS_HIP(hipEventElapsedTime(&res->ms_consolidate, c->ev[0], c->ev[1]));
+	if (sorted_a || sorted_b) SPS_HIP(hipEventElapsedTime(&res->ms_consolidate, c->ev[EV_BEGIN], c->ev[EV_CONSOLIDATED]));
 }
 
 } // namespace spsamd

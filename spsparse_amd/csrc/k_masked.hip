@@ -445,7 +445,7 @@ void multiply_masked(spsamd_ctx *c, double C,
 	SPS_HIP(hipSetDevice(c->device));
 	c->arena.reset();
 	hipStream_t st = c->stream;
-	SPS_HIP(hipEventRecord(c->ev[0], st));
+	SPS_HIP(hipEventRecord(c->ev[EV_BEGIN], st));
 	{ const spsamd_coo *ops[3] = {A, B, M}; pick_output_set(c, ops, 3); }
 	ConMat ca, cb;
 	consolidate_operand(c, A, f.a0, f.a0, duplicate_policy, zero_nan, &ca);       // :187
@@ -456,7 +456,7 @@ void multiply_masked(spsamd_ctx *c, double C,
 	upload_scale(c, scalei, nrow, "scalei", &si);
 	upload_scale(c, scalej, f.inner, "scalej", &sj);
 	upload_scale(c, scalek, ncol, "scalek", &sk);
-	SPS_HIP(hipEventRecord(c->ev[1], st));
+	SPS_HIP(hipEventRecord(c->ev[EV_CONSOLIDATED], st));
 	MaskKeys mk;
 	mask_keys(c, M, nrow, ncol, &mk);
 	const uint32_t nm = mk.n;
@@ -495,7 +495,7 @@ void multiply_masked(spsamd_ctx *c, double C,
 	if (n_row) { k_masked_rowlist<<<dim3(grid_for(nrow)), dim3(256), 0, st>>>(rowflag, off_row, nrow, rows); SPS_LAUNCH_CHECK(); }
 
 	// evaluation: one launch per class
-	SPS_HIP(hipEventRecord(c->ev[2], st));
+	SPS_HIP(hipEventRecord(c->ev[EV_SYMBOLIC], st));
 	MaskedArgs g;
 	g.arp = arp; g.acol = ca.col; g.aval = ca.val;
 	g.brp = brp; g.bcol = cb.col; g.bval = cb.val;
@@ -506,7 +506,7 @@ void multiply_masked(spsamd_ctx *c, double C,
 	if (n_entry) { k_masked_entry<<<dim3(std::min(grid_for(n_entry), cap)), dim3(256), 0, st>>>(g, list_entry, n_entry); SPS_LAUNCH_CHECK(); }
 	if (n_row) { k_masked_row<<<dim3(std::min(n_row, cap)), dim3(256), 0, st>>>(g, rows, n_row, mrp, cls); SPS_LAUNCH_CHECK(); }
 	if (n_wave) { k_masked_wave<<<dim3(std::min(grid_for(n_wave, 4), cap)), dim3(256), 0, st>>>(g, list_wave, n_wave); SPS_LAUNCH_CHECK(); }
-	SPS_HIP(hipEventRecord(c->ev[3], st));
+	SPS_HIP(hipEventRecord(c->ev[EV_N0], st));
 
 	// sinks
 	if (coo) {
@@ -542,8 +542,8 @@ void multiply_masked(spsamd_ctx *c, double C,
 		std::memcpy(&res->sum, &h[3], sizeof(double));
 	}
 	finish_call(c, res);
-	SPS_HIP(hipEventElapsedTime(&res->ms_consolidate, c->ev[0], c->ev[1]));
-	SPS_HIP(hipEventElapsedTime(&res->ms_numeric, c->ev[2], c->ev[3]));
+	SPS_HIP(hipEventElapsedTime(&res->ms_consolidate, c->ev[EV_BEGIN], c->ev[EV_CONSOLIDATED]));
+	SPS_HIP(hipEventElapsedTime(&res->ms_numeric, c->ev[EV_SYMBOLIC], c->ev[EV_N0]));
 }
 
 } // namespace spsamd

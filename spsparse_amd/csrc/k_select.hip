@@ -338,11 +338,11 @@ void select_tuples(spsamd_ctx *c, const spsamd_coo *A, char transpose, int predi
 	SPS_HIP(hipSetDevice(c->device));
 	c->arena.reset();
 	hipStream_t st = c->stream;
-	SPS_HIP(hipEventRecord(c->ev[0], st));
+	SPS_HIP(hipEventRecord(c->ev[EV_BEGIN], st));
 	if (coo) { const spsamd_coo *ops[1] = {A}; pick_output_set(c, ops, 1); }
 	ConMat S;
 	consolidate_operand(c, A, lead, lead, duplicate_policy, zero_nan, &S);
-	SPS_HIP(hipEventRecord(c->ev[1], st));
+	SPS_HIP(hipEventRecord(c->ev[EV_CONSOLIDATED], st));
 	const uint32_t n = S.nnz;
 	res->nnz_a = n;
 	if (n == 0) return;
@@ -405,8 +405,8 @@ void select_tuples(spsamd_ctx *c, const spsamd_coo *A, char transpose, int predi
 	if (coo) publish_coo(c, res, o.row, o.col, o.val, total, permute);
 	else digest_stored(c, res, o.row, o.col, o.val, total, nrow, sink_flags);
 	finish_call(c, res);
-	SPS_HIP(hipEventElapsedTime(&res->ms_consolidate, c->ev[0], c->ev[1]));
-	SPS_HIP(hipEventElapsedTime(&res->ms_numeric, c->ev[1], c->ev[7]));
+	SPS_HIP(hipEventElapsedTime(&res->ms_consolidate, c->ev[EV_BEGIN], c->ev[EV_CONSOLIDATED]));
+	SPS_HIP(hipEventElapsedTime(&res->ms_numeric, c->ev[EV_CONSOLIDATED], c->ev[EV_END]));
 }
 
 } // namespace spsamd

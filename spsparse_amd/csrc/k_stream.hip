@@ -1,5 +1,5 @@
 // k_stream.hip -- spsamd_multiply_stream: the product cut into blocks of whole rows of op(A), each computed by the ordinary
-// pipeline (spgemm_row_slice) into one of two device output sets while the other set's block is copied to the host and handed
+// pipeline (spgemm_once) into one of two device output sets while the other set's block is copied to the host and handed
 // to the callback.  The reference's loop makes the rows of C independent (multiply_sparse.hpp:192): a block of rows is a
 // product of its own, and their outputs, one after the other, are C's tuples in order.
 //
@@ -232,7 +232,7 @@ int multiply_stream(spsamd_ctx *c, double C,
 	SPS_HIP(hipSetDevice(c->device));
 	c->arena.reset();
 	hipStream_t s0 = c->stream;
-	SPS_HIP(hipEventRecord(c->ev[0], s0));
+	SPS_HIP(hipEventRecord(c->ev[EV_BEGIN], s0));
 	MultiplyArgs a;
 	a.C = C; a.sink_kind = SPSAMD_SINK_COO; a.sink_flags = sink_flags & (SPSAMD_SINK_ORDERED | SPSAMD_SINK_EXACT_PATTERN);
 	Prepared *hpa = nullptr, *hpb = nullptr;
@@ -242,12 +242,12 @@ int multiply_stream(spsamd_ctx *c, double C,
 	upload_scale(c, scalei, f.nrow, "scalei", &a.si);
 	upload_scale(c, scalej, f.inner, "scalej", &a.sj);
 	upload_scale(c, scalek, f.ncol, "scalek", &a.sk);
-	SPS_HIP(hipEventRecord(c->ev[1], s0));
+	SPS_HIP(hipEventRecord(c->ev[EV_CONSOLIDATED], s0));
 	const ConMat Am = a.A, Bm = a.B;
 	res->nnz_a = Am.nnz; res->nnz_b = Bm.nnz;
 	if (Am.nnz == 0 || Bm.nnz == 0) {
 		SPS_HIP(hipStreamSynchronize(s0));
-		res->ms_consolidate = res->ms_total = elapsed(c->ev[0], c->ev[1]);
+		res->ms_consolidate = res->ms_total = elapsed(c->ev[EV_BEGIN], c->ev[EV_CONSOLIDATED]);
 		return finish(SPSAMD_OK);
 	}
 
@@ -277,7 +277,7 @@ int multiply_stream(spsamd_ctx *c, double C,
 	k_stream_row_bound<<<dim3(grid_for(n)), dim3(256), 0, s0>>>(aptr, pref, n, Bm.ncol, bound, bs);
 	SPS_LAUNCH_CHECK();
 	const BoundStats hb = read_back(c, bs);
-	res->ms_consolidate = elapsed(c->ev[0], c->ev[1]);
+	res->ms_consolidate = elapsed(c->ev[EV_BEGIN], c->ev[EV_CONSOLIDATED]);
 	if (hb.max_bound > budget) {
 		char buf[200];
 		std::snprintf(buf, sizeof buf, "a row of op(A) can produce %llu tuples, more than block_tuples = %llu: the smallest budget that works is %llu",
@@ -338,9 +338,9 @@ int multiply_stream(spsamd_ctx *c, double C,
 	SPS_HIP(hipStreamCreateWithFlags(&cp.s, hipStreamNonBlocking));
 	for (auto &e : cp.ev) SPS_HIP(hipEventCreateWithFlags(&e, hipEventDisableTiming));
 	for (auto &e : cp.tb) SPS_HIP(hipEventCreate(&e));
-	SPS_HIP(hipEventRecord(c->ev[2], s0));
-	SPS_HIP(hipEventSynchronize(c->ev[2]));
-	const float ms_setup = elapsed(c->ev[0], c->ev[2]);           // consolidation, B's structures, bounds and blocks
+	SPS_HIP(hipEventRecord(c->ev[EV_SYMBOLIC], s0));
+	SPS_HIP(hipEventSynchronize(c->ev[EV_SYMBOLIC]));
+	const float ms_setup = elapsed(c->ev[EV_BEGIN], c->ev[EV_SYMBOLIC]);           // consolidation, B's structures, bounds and blocks
 
 	// ---- the worker computes the blocks; this thread delivers them
 	struct Done { uint64_t nnz = 0; const int32_t *i = nullptr, *j = nullptr; const double *v = nullptr; };
@@ -375,7 +375,7 @@ int multiply_stream(spsamd_ctx *c, double C,
 				as.A.row = Am.row + t0; as.A.col = Am.col + t0; as.A.val = Am.val + t0; as.A.nnz = t1 - t0;
 				spsamd_result rs{};
 				SPS_HIP(hipEventRecord(cp.tb[0], c->stream));
-				if (as.A.nnz) spgemm_row_slice(c, as, &rs);
+				if (as.A.nnz) spgemm_once(c, as, &rs);
 				SPS_HIP(hipEventRecord(cp.tb[1], c->stream));
 				SPS_HIP(hipEventSynchronize(cp.tb[1]));
 				ms_dev += elapsed(cp.tb[0], cp.tb[1]);

@@ -25,12 +25,16 @@ void pick_output_set(spsamd_ctx *c, const spsamd_coo *const *operands, int n)
 	c->cur_out ^= 1;
 }
 
+CooOut grow_output(OutSet &o, size_t total)
+{
+	o.i.ensure(total * 4); o.j.ensure(total * 4); o.v.ensure(total * 8);
+	return CooOut{(int32_t *)o.i.p, (int32_t *)o.j.p, (double *)o.v.p};
+}
+
 CooOut coo_output(spsamd_ctx *c, size_t total)
 {
-	OutSet &o = c->out[c->cur_out];
 	c->own[c->cur_out].sort0 = -1;                                     // that set is about to be overwritten
-	o.i.ensure(total * 4 + 4); o.j.ensure(total * 4 + 4); o.v.ensure(total * 8 + 8);
-	return CooOut{(int32_t *)o.i.p, (int32_t *)o.j.p, (double *)o.v.p};
+	return grow_output(c->out[c->cur_out], total + 1);
 }
 
 CooOut scratch_output(spsamd_ctx *c, size_t total)
@@ -98,9 +102,9 @@ void digest_stored(spsamd_ctx *c, spsamd_result *res, const int32_t *orow, const
 
 void finish_call(spsamd_ctx *c, spsamd_result *res)
 {
-	SPS_HIP(hipEventRecord(c->ev[7], c->stream));
-	SPS_HIP(hipEventSynchronize(c->ev[7]));
-	SPS_HIP(hipEventElapsedTime(&res->ms_total, c->ev[0], c->ev[7]));
+	SPS_HIP(hipEventRecord(c->ev[EV_END], c->stream));
+	SPS_HIP(hipEventSynchronize(c->ev[EV_END]));
+	SPS_HIP(hipEventElapsedTime(&res->ms_total, c->ev[EV_BEGIN], c->ev[EV_END]));
 	res->workspace_bytes = c->arena.call_used;
 }
 

@@ -1,6 +1,8 @@
-// spgemm.hip -- the hot path: C = c * Di * op(A) * Dj * op(B) * Dk on gfx950.  This file is the DRIVER (row classes,
-// segments, sinks, column-block fallback, the small symbolic kernels); the numeric kernels live in k_light.hip, k_hash.hip,
-// k_dense.hip and k_tiles.hip, the heavy rows' symbolic phase in symbolic_heavy.hip (source map: DESIGN.md section 4).
+// spgemm.hip -- the hot path: C = c * Di * op(A) * Dj * op(B) * Dk on gfx950.  This file is the DRIVER and the small symbolic
+// kernels; the numeric kernels live in k_light.hip, k_hash.hip, k_dense.hip and k_tiles.hip, the heavy rows' symbolic phase
+// in symbolic_heavy.hip (source map: DESIGN.md section 4).  One multiply is spgemm_once, a sequence of phases: spgemm_all_light,
+// or classify_rows, build_segments, then numeric_digest / numeric_coo (every pass over the numeric kernels: launch_pass).  The
+// two sinks are digest_begin / digest_end and sink_output; spgemm_column_blocks is the fallback for an op(B) too wide.
 //
 // Replaces the reference's triple loop (multiply_sparse.hpp:192-246: every
 // non-empty row of A x every non-empty column of B, a leap-frog merge join
@@ -250,13 +252,13 @@ template <int MODE>
 static void launch_heavy_hash(spsamd_ctx *c, const Heavy &hv, const RowMeta &m, const EmitParams &ep, const SinkParams &sk)
 {
 	c->join_side(hv.ntile2 != 0, true);                             // the sorted lists (and, for direct cells, the window-major copy)
-	SPS_HIP(hipEventRecord(c->ev2[0], c->stream));
+	SPS_HIP(hipEventRecord(c->ev2[EV2_TILES_BEGIN], c->stream));
 	if (hv.ntile && hv.tiles2 == 0) launch_tiles_bm<MODE>(c, hv, m, ep, sk);
 	else if (hv.ntile && hv.tiles2 == 2) launch_tiles_hash2<MODE>(c, hv, m, ep, sk);
 	else if (hv.ntile) launch_tiles_v1<MODE>(c, hv, m, ep, sk);
-	SPS_HIP(hipEventRecord(c->ev2[1], c->stream));
+	SPS_HIP(hipEventRecord(c->ev2[EV2_TILES_END], c->stream));
 	if (hv.ntile2) launch_tiles_direct<MODE>(c, hv, m, ep, sk);
-	SPS_HIP(hipEventRecord(c->ev2[2], c->stream));
+	SPS_HIP(hipEventRecord(c->ev2[EV2_DIRECT_END], c->stream));
 	launch_hash_windowed<MODE>(c, hv, m, ep, sk);
 }
 
@@ -319,57 +321,76 @@ __global__ void k_block_place(const int32_t *i, const int32_t *j, const double *
 	oi[d] = r; oj[d] = j[t]; ov[d] = v[t];
 }
 
-// DIGEST | ROWSTATS: the shared row statistics (sink.hip; no slack, as the multiply always asked) handed to the kernels' sink
-static void rowstats_begin(spsamd_ctx *c, uint64_t nrow, SinkParams &sk, spsamd_result *res)
+// ---- what every path of the driver shares: the kernels' parameters, the two sinks, the error word
+static EmitParams emit_params(spsamd_ctx *c, const MultiplyArgs &a, uint64_t ncol, int ordered, int exact)
 {
-	const RowStats rs = rowstats_begin(c, nrow, 0, res);
-	sk.row_nnz = rs.nnz; sk.row_sum = rs.sum; sk.row_hash = rs.hash;
+	return EmitParams{a.C, a.si.present ? a.si.pos : nullptr, a.si.val, a.sk.present ? a.sk.pos : nullptr, a.sk.val, c->tune.emit_path,
+#ifdef SPSAMD_ABLATIONS
+		c->tune.dbg,
+#endif
+		0u, ncol > 1 ? (uint32_t)(64 - __builtin_clzll((unsigned long long)(ncol - 1))) : 1u, ordered, exact};
 }
 
+// SINK_DIGEST as the numeric kernels feed it (not digest_stored): DIGEST_SLOTS accumulators and the slot they are reduced into; under
+// ROWSTATS the shared row statistics (sink.hip; no slack, as the multiply always asked) handed to the kernels' sink
+static DigestSlot *digest_begin(spsamd_ctx *c, const MultiplyArgs &a, uint64_t nrow, SinkParams &sk, spsamd_result *res)
+{
+	DigestSlot *slots = sk.digest = get_zeroed<DigestSlot>(c, DIGEST_SLOTS + 1);
+	if (a.sink_flags & SPSAMD_SINK_ROWSTATS) { const RowStats rs = rowstats_begin(c, nrow, 0, res); sk.row_nnz = rs.nnz; sk.row_sum = rs.sum; sk.row_hash = rs.hash; }
+	return slots;
+}
+
+// nnz / hash / sum into res; returns the kernels' error word *err, which rides along.  `reduced`: an event to record behind the reduction
+static unsigned long long digest_end(spsamd_ctx *c, DigestSlot *slots, const uint32_t *err, spsamd_result *res, hipEvent_t reduced = nullptr)
+{
+	k_digest_reduce<<<dim3(1), dim3(64), 0, c->stream>>>(slots, slots + DIGEST_SLOTS, err);
+	SPS_LAUNCH_CHECK();
+	if (reduced) SPS_HIP(hipEventRecord(reduced, c->stream));
+	const DigestSlot d = read_back(c, slots + DIGEST_SLOTS);
+	res->nnz = d.count; res->hash = d.hash; res->sum = d.sum;
+	return d.pad;
+}
+
+// SINK_COO: the segments' counts scanned into their offsets; the output set -- a.out, else the context's current one (chosen by
+// multiply_body: never the set an operand lives in) -- grown to their total, which is returned, and the kernels' sink pointed at it
+static int64_t sink_output(spsamd_ctx *c, const MultiplyArgs &a, const uint32_t *counts, int64_t *segoff, size_t n, SinkParams &sk)
+{
+	scan_exclusive_u32_i64(c, counts, segoff, n);
+	const int64_t total = read_back(c, segoff + n);
+	const CooOut o = grow_output(a.out ? *a.out : c->out[c->cur_out], (size_t)total);
+	sk.out_i = o.row; sk.out_j = o.col; sk.out_v = o.val;
+	return total;
+}
+
+static void check_kernel_error(unsigned long long err) { if (err) throw Error{SPSAMD_EINVAL, "internal error: a numeric kernel met a cell larger than its class allows"}; }
+
+// ---- all rows light: the direct kernel, no symbolic phase
 static void spgemm_all_light(spsamd_ctx *c, MultiplyArgs &a, spsamd_result *res, const uint32_t *aptr, const int32_t *acol, const double *aval,
 	const uint32_t *bptr, uint32_t maxp)
 {
 	hipStream_t st = c->stream;
 	const ConMat &A = a.A, &B = a.B;
 	const uint32_t nrow = (uint32_t)A.nrow;
-	EmitParams ep{a.C, a.si.present ? a.si.pos : nullptr, a.si.val, a.sk.present ? a.sk.pos : nullptr, a.sk.val, c->tune.emit_path,
-#ifdef SPSAMD_ABLATIONS
-		c->tune.dbg,
-#endif
-		0u, B.ncol > 1 ? (uint32_t)(64 - __builtin_clzll((unsigned long long)(B.ncol - 1))) : 1u, 0, 0};
+	const EmitParams ep = emit_params(c, a, B.ncol, 0, 0);
 	// wide variant: (column << log2 S | A position) does not fit 32 bits, or an operand array reaches 4 GB
 	const bool k64 = ep.ncolbits + 6u > 32u || A.nnz >= (1u << 29) || B.nnz >= (1u << 29) || A.nrow + 2 >= (uint64_t(1) << 30) || B.nrow + 3 >= (uint64_t(1) << 30);
 	SinkParams sk{};
-	sk.err = c->arena.get<uint32_t>(1);
-	fill_zero(c, sk.err, sizeof(uint32_t));
-	unsigned long long *pc = c->arena.get<unsigned long long>(1);
-	fill_zero(c, pc, sizeof(unsigned long long));
-	SPS_HIP(hipEventRecord(c->ev[2], st));
-	SPS_HIP(hipEventRecord(c->ev[3], st));
+	sk.err = get_zeroed<uint32_t>(c, 1);
+	unsigned long long *pc = get_zeroed<unsigned long long>(c, 1);
+	SPS_HIP(hipEventRecord(c->ev[EV_SYMBOLIC], st)); SPS_HIP(hipEventRecord(c->ev[EV_N0], st));
 	if (a.sink_kind != SPSAMD_SINK_COO) {
-		DigestSlot *slots = c->arena.get<DigestSlot>(DIGEST_SLOTS + 1);
-		fill_zero(c, slots, (DIGEST_SLOTS + 1) * sizeof(DigestSlot));
-		sk.digest = slots;
-		if (a.sink_flags & SPSAMD_SINK_ROWSTATS) {
-			rowstats_begin(c, A.nrow, sk, res);
-		}
+		DigestSlot *slots = digest_begin(c, a, A.nrow, sk, res);
 		launch_light_direct_s<MODE_DIGEST>(c, maxp, nrow, aptr, acol, aval, bptr, B, k64, ep, sk, pc);
-		k_digest_reduce<<<dim3(1), dim3(64), 0, st>>>(slots, slots + DIGEST_SLOTS, sk.err);
-		SPS_LAUNCH_CHECK();
-		SPS_HIP(hipEventRecord(c->ev[4], st));
-		DigestSlot d = read_back(c, slots + DIGEST_SLOTS);
-		res->nnz = d.count; res->hash = d.hash; res->sum = d.sum;
+		// (checked like every digest, though it cannot fire here: no kernel of k_light.hip writes the error word)
+		check_kernel_error(digest_end(c, slots, sk.err, res, c->ev[EV_N1]));
 	} else {
 		// COO: one segment per row of op(A) (empty rows included) -- or, in one pass, per wave round of the kernel
-		const uint32_t S = maxp <= 8 ? 8u : (maxp <= 16 ? 16u : (maxp <= 32 ? 32u : 64u));
-		const uint32_t G = 64u / S;
+		const uint32_t S = maxp <= 8 ? 8u : (maxp <= 16 ? 16u : (maxp <= 32 ? 32u : 64u)), G = 64u / S;
 		const size_t nround = ((size_t)nrow + 4u * G - 1u) / (4u * G) * 4u;      // wave rounds: G rows each, four waves per workgroup round
 		const size_t nsegs = std::max<size_t>(nrow, nround);
-		uint32_t *segcount = c->arena.get<uint32_t>(nsegs + 1);
-		uint32_t *segactual = c->arena.get<uint32_t>(nsegs + 1);
+		sk.segcount = c->arena.get<uint32_t>(nsegs + 1);
+		sk.segactual = c->arena.get<uint32_t>(nsegs + 1);
 		int64_t *segoff = c->arena.get<int64_t>(nsegs + 1);
-		sk.segcount = segcount; sk.segactual = segactual;
-		OutSet &os = a.out ? *a.out : c->out[c->cur_out];
 		// ONE compute pass where the memory is there: every wave round writes the tuples of its G rows, packed, to its own 64
 		// slots of a sparse buffer and says how many; scan; a gather packs the rounds.  The other way -- count, scan, store
 		// -- evaluates every product twice: Poisson 4096^2 8.1 ms against 3.8 for the digest.
@@ -383,50 +404,39 @@ static void spgemm_all_light(spsamd_ctx *c, MultiplyArgs &a, spsamd_result *res,
 				if (slots * 16 > (freeb + room) / 3) one_pass = false;
 			}
 		}
-		int64_t total;
 		if (one_pass) {
 			int32_t *si = c->arena.get<int32_t>(slots), *sj = c->arena.get<int32_t>(slots);
 			double *sv = c->arena.get<double>(slots);
 			sk.segoff = nullptr; sk.out_i = si; sk.out_j = sj; sk.out_v = sv;
 			launch_light_direct_s<MODE_STORE>(c, maxp, nrow, aptr, acol, aval, bptr, B, k64, ep, sk, pc);
-			scan_exclusive_u32_i64(c, segactual, segoff, nround);
-			total = read_back(c, segoff + nround);
-			os.i.ensure((size_t)total * sizeof(int32_t));
-			os.j.ensure((size_t)total * sizeof(int32_t));
-			os.v.ensure((size_t)total * sizeof(double));
-			sk.out_i = (int32_t *)os.i.p; sk.out_j = (int32_t *)os.j.p; sk.out_v = (double *)os.v.p;
-			launch_light_gather(c, (uint32_t)nround, 64u, segactual, segoff, si, sj, sv, sk.out_i, sk.out_j, sk.out_v);
+			res->nnz = (uint64_t)sink_output(c, a, sk.segactual, segoff, nround, sk);
+			launch_light_gather(c, (uint32_t)nround, 64u, sk.segactual, segoff, si, sj, sv, sk.out_i, sk.out_j, sk.out_v);
 		} else {
 			sk.segoff = segoff;
 			launch_light_direct_s<MODE_COUNT>(c, maxp, nrow, aptr, acol, aval, bptr, B, k64, ep, sk, pc);
-			scan_exclusive_u32_i64(c, segcount, segoff, nrow);
-			total = read_back(c, segoff + nrow);
-			os.i.ensure((size_t)total * sizeof(int32_t));
-			os.j.ensure((size_t)total * sizeof(int32_t));
-			os.v.ensure((size_t)total * sizeof(double));
-			sk.out_i = (int32_t *)os.i.p; sk.out_j = (int32_t *)os.j.p; sk.out_v = (double *)os.v.p;
+			// the counting launch evaluates the same sums as the storing one (ascending k, deterministic): the counts are exact, no holes
+			res->nnz = (uint64_t)sink_output(c, a, sk.segcount, segoff, nrow, sk);
 			fill_zero(c, pc, sizeof(unsigned long long));
 			launch_light_direct_s<MODE_STORE>(c, maxp, nrow, aptr, acol, aval, bptr, B, k64, ep, sk, pc);
 		}
-		SPS_HIP(hipEventRecord(c->ev[4], st));
-		// the counting launch evaluated the same sums (ascending k, deterministic): the counts are exact, no holes
-		res->nnz = (uint64_t)total;
+		SPS_HIP(hipEventRecord(c->ev[EV_N1], st));
 		res->idx0 = sk.out_i; res->idx1 = sk.out_j; res->val = sk.out_v;
 	}
 	res->products = read_back(c, pc);
 	res->rows_light = nrow; res->products_light = res->products; res->tuples_light = A.nnz;
-	SPS_HIP(hipEventRecord(c->ev[7], st));
-	SPS_HIP(hipEventSynchronize(c->ev[7]));
-	res->ms_symbolic = elapsed(c->ev[1], c->ev[2]);
-	res->ms_numeric = elapsed(c->ev[2], c->ev[7]);
-	res->ms_light = elapsed(c->ev[3], c->ev[4]);
+	SPS_HIP(hipEventRecord(c->ev[EV_END], st));
+	SPS_HIP(hipEventSynchronize(c->ev[EV_END]));
+	res->ms_symbolic = elapsed(c->ev[EV_CONSOLIDATED], c->ev[EV_SYMBOLIC]);
+	res->ms_numeric = elapsed(c->ev[EV_SYMBOLIC], c->ev[EV_END]);
+	res->ms_light = elapsed(c->ev[EV_N0], c->ev[EV_N1]);
 }
 
 // ---- derived structures of an operand: taken from its Prepared record where they exist, built (and kept there) otherwise
+constexpr uint32_t SENTINEL_ROWS = 1u;  // one empty row after the last: it receives the A tuples whose k is absent from scalej
+
 static uint32_t *ensure_rowptr(spsamd_ctx *c, Prepared *p)
 {
-	// one empty sentinel row after the last: it receives the A tuples whose k is absent from scalej
-	if (!p->rowptr) p->rowptr = dense_rowptr(c, p->m, 1u, p->get<uint32_t>(p->m.nrow + 2));
+	if (!p->rowptr) p->rowptr = dense_rowptr(c, p->m, SENTINEL_ROWS, p->get<uint32_t>(p->m.nrow + 1 + SENTINEL_ROWS));
 	return p->rowptr;
 }
 
@@ -437,8 +447,7 @@ static void ensure_maxlen(spsamd_ctx *c, Prepared *pa, Prepared *pb)
 	if (!pa->have_maxlen) need[n++] = pa;
 	if (pb != pa && !pb->have_maxlen) need[n++] = pb;
 	if (!n) return;
-	uint32_t *mx = c->arena.get<uint32_t>(2);
-	fill_zero(c, mx, 2 * sizeof(uint32_t));
+	uint32_t *mx = get_zeroed<uint32_t>(c, 2);
 	for (int q = 0; q < n; ++q) {
 		k_max_rowlen<<<dim3(std::min(grid_for(need[q]->m.nrow, 1024), 1024u)), dim3(256), 0, st>>>(need[q]->rowptr, need[q]->m.nrow, mx + q);
 		SPS_LAUNCH_CHECK();
@@ -494,26 +503,186 @@ BTup *prepared_btup(spsamd_ctx *c, Prepared *p)
 	return ensure_btup(c, a, p);
 }
 
-static void spgemm_once(spsamd_ctx *c, MultiplyArgs &a, spsamd_result *res)
+// ---- the phases of one multiply, in the order spgemm_once calls them.  Symbolic phase over all rows: per A tuple the B row it
+// selects (elo, elen), per non-empty row of A its products (rprod), the rows listed by bin and the bins' totals on the host
+struct RowClasses { Bins bins; uint32_t *rprod, *elo, *elen; BinCounters hbc; };
+
+static RowClasses classify_rows(spsamd_ctx *c, const MultiplyArgs &a, const RowList &rl, const int32_t *acol, const uint32_t *bptr)
+{
+	hipStream_t st = c->stream;
+	const uint32_t nnz = a.A.nnz;
+	RowClasses rc;
+	rc.elen = c->arena.get<uint32_t>(nnz);
+	rc.elo = c->arena.get<uint32_t>(nnz);
+	int64_t *pref = c->arena.get<int64_t>((size_t)nnz + 1);
+	k_elem_len<<<dim3(grid_for(nnz)), dim3(256), 0, st>>>(acol, bptr, nnz, rc.elo, rc.elen);
+	SPS_LAUNCH_CHECK();
+	scan_exclusive_u32_i64(c, rc.elen, pref, nnz);
+	rc.rprod = c->arena.get<uint32_t>(rl.nrows);
+	uint8_t *rbin = c->arena.get<uint8_t>(rl.nrows);
+	BinCounters *bc = get_zeroed<BinCounters>(c, 1);
+	k_classify<<<dim3(grid_for(rl.nrows, 256 * CLS_ITEMS)), dim3(256), 0, st>>>(rl.beg, rl.id, rl.nrows, pref, rc.elen,
+		a.si.present ? a.si.pos : nullptr, a.si.val, rc.rprod, rbin, bc);
+	SPS_LAUNCH_CHECK();
+	rc.hbc = read_back(c, bc);
+	if (rc.hbc.too_big) throw Error{SPSAMD_EINVAL, "an output row with more than 2^32-1 scalar products is not supported"};
+	Bins &bins = rc.bins;
+	BinOffsets bo; uint32_t run = 0;
+	for (int b = 0; b < NBIN; ++b) {
+		bins.count[b] = b == 0 ? 0 : (uint32_t)rc.hbc.rows[b];
+		bins.off[b] = bo.off[b] = run;
+		run += bins.count[b];
+	}
+	bins.off[NBIN] = bo.off[NBIN] = run;
+	int whole_bin = 0;                               // a light bin that holds every row needs no list
+	for (int b = 1; b <= 4; ++b) if (bins.count[b] == rl.nrows) whole_bin = b;
+	bins.rows = nullptr;
+	if (!whole_bin) {
+		bins.rows = c->arena.get<uint32_t>(run ? run : 1);
+		uint32_t *cursor = get_zeroed<uint32_t>(c, NBIN);
+		k_bin_scatter<<<dim3(grid_for(rl.nrows, 256 * CLS_ITEMS)), dim3(256), 0, st>>>(rbin, rl.nrows, bo, cursor, bins.rows);
+		SPS_LAUNCH_CHECK();
+	}
+	return rc;
+}
+
+// rows, products and A tuples of the light (bins 1-4), mid (5-7) and heavy (8) rows
+static void fill_class_counters(spsamd_result *res, const BinCounters &h)
+{
+	const struct { int first, last; uint64_t *rows, *prods, *tuples; } cls[3] = {{1, 4, &res->rows_light, &res->products_light, &res->tuples_light},
+		{5, 7, &res->rows_mid, &res->products_mid, &res->tuples_mid}, {8, 8, &res->rows_heavy, &res->products_heavy, &res->tuples_heavy}};
+	res->products = 0;
+	for (auto &k : cls) {
+		*k.rows = *k.prods = *k.tuples = 0;
+		for (int b = k.first; b <= k.last; ++b) { *k.rows += h.rows[b]; *k.prods += h.prods[b]; *k.tuples += h.tuples[b]; }
+		res->products += *k.prods;
+	}
+}
+
+// Segments (the COO sink's: one per light / mid row, one per cell of a heavy row; sk.segbase, their number returned) and the heavy and mid rows' cells
+static int64_t build_segments(spsamd_ctx *c, const MultiplyArgs &a, const RowList &rl, const RowClasses &rc, const RowMeta &m, Prepared *pb,
+	Heavy &hv, MidCells &mc, SinkParams &sk, spsamd_result *res)
+{
+	const Bins &bins = rc.bins;
+	uint32_t *nseg = c->arena.get<uint32_t>(rl.nrows);
+	fill_u32(c, nseg, 1u, rl.nrows);
+	hv.n = bins.count[8]; hv.tuples = rc.hbc.tuples[8]; hv.coo = a.sink_kind == SPSAMD_SINK_COO;
+	if (hv.n) heavy_prepare(c, hv, bins, m, a.B, m.bptr, SENTINEL_ROWS, nseg, (a.sink_flags & SPSAMD_SINK_ORDERED) != 0, (a.sink_flags & SPSAMD_SINK_EXACT_PATTERN) != 0, pb);
+	uint32_t *segbase = nullptr; int64_t nsegs = 0;
+	if (hv.coo) {
+		int64_t *segbase64 = c->arena.get<int64_t>((size_t)rl.nrows + 1);
+		scan_exclusive_u32_i64(c, nseg, segbase64, rl.nrows);
+		nsegs = read_back(c, segbase64 + rl.nrows);
+		if (nsegs >= (int64_t(1) << 32)) throw Error{SPSAMD_EINVAL, "too many output segments"};
+		segbase = c->arena.get<uint32_t>((size_t)rl.nrows + 1);
+		scan_exclusive_u32_u32(c, nseg, segbase, rl.nrows);
+	}
+	if (hv.n) heavy_cells(c, hv, m, segbase);
+	for (int k = 0; k < 3; ++k) {
+		uint32_t nb = bins.count[5 + k];
+		if (!nb) continue;
+		mc.cells[k] = c->arena.get<Cell>(nb);
+		k_row_cells<<<dim3(grid_for(nb)), dim3(256), 0, c->stream>>>(bins.rows + bins.off[5 + k], nb, rl.beg, rl.id, rc.rprod, segbase, mc.cells[k]);
+		SPS_LAUNCH_CHECK();
+	}
+	res->cells_hash = (uint64_t)hv.ncell[0] + hv.ncell[1] + hv.ncell[2] + hv.ncell[3] + hv.ntcell + hv.ntcell2;
+	res->cells_dense = hv.ncell[CLS_DENSE]; res->window = hv.n ? (uint32_t)hv.W : 0u;
+	res->products_dense = hv.clsprod[CLS_DENSE]; res->products_tiles = hv.clsprod[NCLS]; res->products_direct = hv.clsprod[NCLS + 1];
+	sk.segbase = segbase;
+	return nsegs;
+}
+
+struct Work { const Bins &bins; const MidCells &mc; Heavy &hv; const RowMeta &m; const EmitParams &ep; };   // what the numeric kernels of a call work on
+
+// One pass of the numeric kernels in the one order there is: light rows, mid rows, the heavy rows' hash cells (their lists are sorted beside
+// the first two, ahead of a call's first pass only), their dense cells.  mark[0]: the event recorded before the pass, mark[1..4]: after each group.
+template <int MODE>
+static void launch_pass(spsamd_ctx *c, const Work &w, const SinkParams &sk, const int (&mark)[5])
+{
+	auto record = [&](int e) { if (e != EV_NONE) SPS_HIP(hipEventRecord(c->ev[e], c->stream)); };
+	record(mark[0]);
+	launch_light<MODE>(c, w.bins, w.m, w.ep, sk);
+	record(mark[1]);
+	launch_mid<MODE>(c, w.bins, w.mc, w.m, w.ep, sk);
+	record(mark[2]);
+	if (MODE != MODE_STORE && w.hv.n) heavy_sort_lists(c, w.hv);
+	launch_heavy_hash<MODE>(c, w.hv, w.m, w.ep, sk);
+	record(mark[3]);
+	c->join_side(true, true);                                       // (nothing is left to wait for in a second pass)
+	launch_heavy_dense<MODE>(c, w.hv, w.m, w.ep, sk);
+	record(mark[4]);
+}
+
+static void numeric_digest(spsamd_ctx *c, const MultiplyArgs &a, const Work &w, SinkParams &sk, spsamd_result *res)
+{
+	DigestSlot *slots = digest_begin(c, a, a.A.nrow, sk, res);
+	launch_pass<MODE_DIGEST>(c, w, sk, {EV_N0, EV_N1, EV_N2, EV_N3, EV_N4});
+	check_kernel_error(digest_end(c, slots, sk.err, res));
+	res->ms_light = elapsed(c->ev[EV_N0], c->ev[EV_N1]); res->ms_mid = elapsed(c->ev[EV_N1], c->ev[EV_N2]);
+	res->ms_heavy = elapsed(c->ev[EV_N2], c->ev[EV_N4]); res->ms_dense = elapsed(c->ev[EV_N3], c->ev[EV_N4]);
+}
+
+// STORE left gaps where a sum cancelled to exactly 0 (COUNT reserved its tuple): close them.  Returns the tuples that remain.
+static uint64_t close_holes(spsamd_ctx *c, const SinkParams &sk, int64_t nsegs, int64_t reserved)
+{
+	hipStream_t st = c->stream;
+	struct HolesErr { unsigned long long holes, err; };
+	unsigned long long *holes = get_zeroed<unsigned long long>(c, 2);
+	k_seg_holes<<<dim3(grid_for((size_t)nsegs)), dim3(256), 0, st>>>(sk.segcount, sk.segactual, (uint32_t)nsegs, holes, sk.err);
+	SPS_LAUNCH_CHECK();
+	const HolesErr he = read_back(c, (const HolesErr *)holes);
+	check_kernel_error(he.err);
+	const uint64_t nnz = (uint64_t)reserved - he.holes;
+	if (he.holes) {                                                 // (rare path)
+		int64_t *newoff = c->arena.get<int64_t>((size_t)nsegs + 1);
+		scan_exclusive_u32_i64(c, sk.segactual, newoff, (size_t)nsegs);
+		int32_t *ti = c->arena.get<int32_t>(nnz ? nnz : 1), *tj = c->arena.get<int32_t>(nnz ? nnz : 1);
+		double *tv = c->arena.get<double>(nnz ? nnz : 1);
+		k_seg_gather<<<dim3(grid_for((size_t)nsegs)), dim3(256), 0, st>>>(sk.segoff, newoff, sk.segactual, (uint32_t)nsegs,
+			sk.out_i, sk.out_j, sk.out_v, ti, tj, tv);
+		SPS_LAUNCH_CHECK();
+		SPS_HIP(hipMemcpyAsync(sk.out_i, ti, nnz * sizeof(int32_t), hipMemcpyDeviceToDevice, st));
+		SPS_HIP(hipMemcpyAsync(sk.out_j, tj, nnz * sizeof(int32_t), hipMemcpyDeviceToDevice, st));
+		SPS_HIP(hipMemcpyAsync(sk.out_v, tv, nnz * sizeof(double), hipMemcpyDeviceToDevice, st));
+		SPS_HIP(hipStreamSynchronize(st));
+	}
+	return nnz;
+}
+
+// COUNT every segment's tuples, scan, grow the output, STORE, close the holes
+static void numeric_coo(spsamd_ctx *c, const MultiplyArgs &a, const Work &w, int64_t nsegs, SinkParams &sk, spsamd_result *res)
+{
+	const size_t n = (size_t)nsegs + 1;
+	sk.segcount = get_zeroed<uint32_t>(c, n);
+	sk.segactual = get_zeroed<uint32_t>(c, n);
+	int64_t *segoff = c->arena.get<int64_t>(n);
+	sk.segoff = segoff;
+	launch_pass<MODE_COUNT>(c, w, sk, {EV_N0, EV_NONE, EV_NONE, EV_NONE, EV_NONE});
+	const int64_t reserved = sink_output(c, a, sk.segcount, segoff, (size_t)nsegs, sk);
+	launch_pass<MODE_STORE>(c, w, sk, {EV_N1, EV_NONE, EV_N2, EV_N3, EV_N4});
+	res->nnz = close_holes(c, sk, nsegs, reserved);
+	res->idx0 = sk.out_i; res->idx1 = sk.out_j; res->val = sk.out_v;
+	// of the STORE pass, which has no mark between the light and the mid rows: both are in ms_light, ms_mid is 0
+	res->ms_light = elapsed(c->ev[EV_N1], c->ev[EV_N2]); res->ms_mid = 0;
+	res->ms_heavy = elapsed(c->ev[EV_N2], c->ev[EV_N4]); res->ms_dense = elapsed(c->ev[EV_N3], c->ev[EV_N4]);
+}
+
+void spgemm_once(spsamd_ctx *c, MultiplyArgs &a, spsamd_result *res)
 {
 	hipStream_t st = c->stream;
 	const ConMat &A = a.A, &B = a.B;
 	res->nnz_a = A.nnz; res->nnz_b = B.nnz;
 	if (A.nnz == 0 || B.nnz == 0) return;           // empty product (also SURVEY Appendix A.3)
-
-	SPS_HIP(hipEventRecord(c->ev[1], st));
+	SPS_HIP(hipEventRecord(c->ev[EV_CONSOLIDATED], st));
 	// views for operands that come without a record of their own (pieces in this call's arena)
 	Prepared viewA, viewB;
-	viewA.ctx = viewB.ctx = c;
-	viewA.m = A; viewB.m = B;
+	viewA.ctx = viewB.ctx = c; viewA.m = A; viewB.m = B;
 	const bool same = (a.pa && a.pa == a.pb) || (A.row == B.row && A.col == B.col && A.nnz == B.nnz && A.nrow == B.nrow);
 	Prepared *pa = a.pa ? a.pa : &viewA;
 	Prepared *pb = a.pb ? a.pb : (same ? pa : &viewB);
 	if (same && a.pb && !a.pa) pa = pb;
-	const uint32_t extra = 1u;                       // (the sentinel row: ensure_rowptr)
 	uint32_t *bptr = ensure_rowptr(c, pb);
-	const int32_t *acol = A.col;
-	const double *aval = A.val;
+	const int32_t *acol = A.col; const double *aval = A.val;
 	if (a.sj.present) {
 		int32_t *acol2 = c->arena.get<int32_t>(A.nnz);
 		double *aval2 = c->arena.get<double>(A.nnz);
@@ -531,343 +700,156 @@ static void spgemm_once(spsamd_ctx *c, MultiplyArgs &a, spsamd_result *res)
 			return;
 		}
 	}
-	// ---- row structure of A (dim_beginnings)
+	// ---- symbolic: the row structure of A (dim_beginnings); products per A tuple and per row, bins; segments and cells
 	const RowList rl = ensure_rowlist(c, pa);
-
-	// ---- symbolic: products per A tuple, per row, bins
-	uint32_t *elen = c->arena.get<uint32_t>(A.nnz);
-	uint32_t *elo = c->arena.get<uint32_t>(A.nnz);
-	int64_t *pref = c->arena.get<int64_t>((size_t)A.nnz + 1);
-	k_elem_len<<<dim3(grid_for(A.nnz)), dim3(256), 0, st>>>(acol, bptr, A.nnz, elo, elen);
-	SPS_LAUNCH_CHECK();
-	scan_exclusive_u32_i64(c, elen, pref, A.nnz);
-	uint32_t *rprod = c->arena.get<uint32_t>(rl.nrows);
-	uint8_t *rbin = c->arena.get<uint8_t>(rl.nrows);
-	BinCounters *bc = c->arena.get<BinCounters>(1);
-	fill_zero(c, bc, sizeof(BinCounters));
-	k_classify<<<dim3(grid_for(rl.nrows, 256 * CLS_ITEMS)), dim3(256), 0, st>>>(rl.beg, rl.id, rl.nrows, pref, elen,
-		a.si.present ? a.si.pos : nullptr, a.si.val, rprod, rbin, bc);
-	SPS_LAUNCH_CHECK();
-	BinCounters hbc = read_back(c, bc);
-	if (hbc.too_big) throw Error{SPSAMD_EINVAL, "an output row with more than 2^32-1 scalar products is not supported"};
-
-	Bins bins;
-	BinOffsets bo;
-	uint32_t run = 0;
-	for (int b = 0; b < NBIN; ++b) {
-		bins.count[b] = b == 0 ? 0 : (uint32_t)hbc.rows[b];
-		bins.off[b] = bo.off[b] = run;
-		run += bins.count[b];
-	}
-	bins.off[NBIN] = bo.off[NBIN] = run;
-	int whole_bin = 0;                               // a light bin that holds every row needs no list
-	for (int b = 1; b <= 4; ++b) if (bins.count[b] == rl.nrows) whole_bin = b;
-	bins.rows = nullptr;
-	if (!whole_bin) {
-		bins.rows = c->arena.get<uint32_t>(run ? run : 1);
-		uint32_t *cursor = c->arena.get<uint32_t>(NBIN);
-		fill_zero(c, cursor, NBIN * sizeof(uint32_t));
-		k_bin_scatter<<<dim3(grid_for(rl.nrows, 256 * CLS_ITEMS)), dim3(256), 0, st>>>(rbin, rl.nrows, bo, cursor, bins.rows);
-		SPS_LAUNCH_CHECK();
-	}
-
-	uint64_t P = 0;
-	for (int b = 1; b < NBIN; ++b) P += hbc.prods[b];
-	res->products = P;
-	res->rows_light = hbc.rows[1] + hbc.rows[2] + hbc.rows[3] + hbc.rows[4];
-	res->rows_mid = hbc.rows[5] + hbc.rows[6] + hbc.rows[7];
-	res->rows_heavy = hbc.rows[8];
-	res->products_light = hbc.prods[1] + hbc.prods[2] + hbc.prods[3] + hbc.prods[4];
-	res->products_mid = hbc.prods[5] + hbc.prods[6] + hbc.prods[7];
-	res->products_heavy = hbc.prods[8];
-	res->tuples_light = hbc.tuples[1] + hbc.tuples[2] + hbc.tuples[3] + hbc.tuples[4];
-	res->tuples_mid = hbc.tuples[5] + hbc.tuples[6] + hbc.tuples[7];
-	res->tuples_heavy = hbc.tuples[8];
-
+	const RowClasses rc = classify_rows(c, a, rl, acol, bptr);
+	fill_class_counters(res, rc.hbc);
 	BTup *btup = ensure_btup(c, a, pb);
-	RowMeta m{rl.beg, rl.id, acol, aval, bptr, btup, btup, elo, elen};
+	const RowMeta m{rl.beg, rl.id, acol, aval, bptr, btup, btup, rc.elo, rc.elen};
 #ifdef SPSAMD_ABLATIONS
 	set_ablation_word(c, c->tune.dbg);
 #endif
-	EmitParams ep{a.C, a.si.present ? a.si.pos : nullptr, a.si.val, a.sk.present ? a.sk.pos : nullptr, a.sk.val,
-		c->tune.emit_path,
-#ifdef SPSAMD_ABLATIONS
-		c->tune.dbg,
-#endif
-		0u,
-		B.ncol > 1 ? (uint32_t)(64 - __builtin_clzll((unsigned long long)(B.ncol - 1))) : 1u,
-		(a.sink_flags & SPSAMD_SINK_ORDERED) ? 1 : 0,
-		((a.sink_flags & SPSAMD_SINK_EXACT_PATTERN) && !(a.sink_flags & SPSAMD_SINK_ORDERED)) ? 1 : 0};
-
-	// ---- segments (one per light/mid row, one per cell of a heavy row) and the heavy rows' cells
-	const bool coo = a.sink_kind == SPSAMD_SINK_COO;
-	uint32_t *nseg = c->arena.get<uint32_t>(rl.nrows);
-	fill_u32(c, nseg, 1u, rl.nrows);
+	EmitParams ep = emit_params(c, a, B.ncol, (a.sink_flags & SPSAMD_SINK_ORDERED) ? 1 : 0,
+		((a.sink_flags & SPSAMD_SINK_EXACT_PATTERN) && !(a.sink_flags & SPSAMD_SINK_ORDERED)) ? 1 : 0);
 	// work this call puts on the context's other streams is waited for by the main stream before the first kernel that needs
 	// it -- and before the call ends, whatever happens (its buffers are this call's workspace)
 	struct SideGuard { spsamd_ctx *c; ~SideGuard() { c->join_side(true, true); } } side_guard{c};
-	Heavy hv;
-	hv.n = bins.count[8];
-	hv.tuples = hbc.tuples[8];
-	hv.coo = coo;
-	if (hv.n) heavy_prepare(c, hv, bins, m, B, bptr, extra, nseg, (a.sink_flags & SPSAMD_SINK_ORDERED) != 0, (a.sink_flags & SPSAMD_SINK_EXACT_PATTERN) != 0, pb);
+	Heavy hv; MidCells mc; SinkParams sk{};
+	const int64_t nsegs = build_segments(c, a, rl, rc, m, pb, hv, mc, sk, res);
 	ep.wshift = hv.W == 8192 ? 13u : 14u;
-	uint32_t *segbase = nullptr;
-	int64_t nsegs = 0;
-	if (coo) {
-		int64_t *segbase64 = c->arena.get<int64_t>((size_t)rl.nrows + 1);
-		scan_exclusive_u32_i64(c, nseg, segbase64, rl.nrows);
-		nsegs = read_back(c, segbase64 + rl.nrows);
-		if (nsegs >= (int64_t(1) << 32)) throw Error{SPSAMD_EINVAL, "too many output segments"};
-		segbase = c->arena.get<uint32_t>((size_t)rl.nrows + 1);
-		scan_exclusive_u32_u32(c, nseg, segbase, rl.nrows);
-	}
-	if (hv.n) heavy_cells(c, hv, m, segbase);
-	MidCells mc;
-	for (int k = 0; k < 3; ++k) {
-		uint32_t nb = bins.count[5 + k];
-		if (!nb) continue;
-		mc.cells[k] = c->arena.get<Cell>(nb);
-		k_row_cells<<<dim3(grid_for(nb)), dim3(256), 0, st>>>(bins.rows + bins.off[5 + k], nb, rl.beg, rl.id, rprod, segbase, mc.cells[k]);
-		SPS_LAUNCH_CHECK();
-	}
-	res->cells_hash = (uint64_t)hv.ncell[0] + hv.ncell[1] + hv.ncell[2] + hv.ncell[3] + hv.ntcell + hv.ntcell2;
-	res->cells_dense = hv.ncell[CLS_DENSE];
-	res->window = hv.n ? (uint32_t)hv.W : 0u;
-	res->products_dense = hv.clsprod[CLS_DENSE];
-	res->products_tiles = hv.clsprod[NCLS];
-	res->products_direct = hv.clsprod[NCLS + 1];
-	SPS_HIP(hipEventRecord(c->ev[2], st));
+	SPS_HIP(hipEventRecord(c->ev[EV_SYMBOLIC], st));
 
 	// ---- numeric
-	SinkParams sk{};
-	sk.segbase = segbase;
-	sk.err = c->arena.get<uint32_t>(1);
-	fill_zero(c, sk.err, sizeof(uint32_t));
-	float ms_light = 0, ms_mid = 0, ms_heavy = 0, ms_dense = 0;
-	if (!coo) {
-		DigestSlot *slots = c->arena.get<DigestSlot>(DIGEST_SLOTS + 1);
-		fill_zero(c, slots, (DIGEST_SLOTS + 1) * sizeof(DigestSlot));
-		sk.digest = slots;
-		if (a.sink_flags & SPSAMD_SINK_ROWSTATS) {
-			rowstats_begin(c, A.nrow, sk, res);
-		}
-		SPS_HIP(hipEventRecord(c->ev[3], st));
-		launch_light<MODE_DIGEST>(c, bins, m, ep, sk);
-		SPS_HIP(hipEventRecord(c->ev[4], st));
-		launch_mid<MODE_DIGEST>(c, bins, mc, m, ep, sk);
-		SPS_HIP(hipEventRecord(c->ev[5], st));
-		if (hv.n) heavy_sort_lists(c, hv);
-		launch_heavy_hash<MODE_DIGEST>(c, hv, m, ep, sk);
-		SPS_HIP(hipEventRecord(c->ev[6], st));
-		c->join_side(true, true);
-		launch_heavy_dense<MODE_DIGEST>(c, hv, m, ep, sk);
-		SPS_HIP(hipEventRecord(c->ev[8], st));
-		k_digest_reduce<<<dim3(1), dim3(64), 0, st>>>(slots, slots + DIGEST_SLOTS, sk.err);
-		SPS_LAUNCH_CHECK();
-		DigestSlot d = read_back(c, slots + DIGEST_SLOTS);
-		if (d.pad) throw Error{SPSAMD_EINVAL, "internal error: a numeric kernel met a cell larger than its class allows"};
-		res->nnz = d.count; res->hash = d.hash; res->sum = d.sum;
-		ms_light = elapsed(c->ev[3], c->ev[4]); ms_mid = elapsed(c->ev[4], c->ev[5]);
-		ms_heavy = elapsed(c->ev[5], c->ev[8]); ms_dense = elapsed(c->ev[6], c->ev[8]);
-	} else {
-		uint32_t *segcount = c->arena.get<uint32_t>((size_t)nsegs + 1);
-		uint32_t *segactual = c->arena.get<uint32_t>((size_t)nsegs + 1);
-		int64_t *segoff = c->arena.get<int64_t>((size_t)nsegs + 1);
-		fill_zero(c, segcount, ((size_t)nsegs + 1) * sizeof(uint32_t));
-		fill_zero(c, segactual, ((size_t)nsegs + 1) * sizeof(uint32_t));
-		sk.segcount = segcount; sk.segoff = segoff; sk.segactual = segactual;
+	sk.err = get_zeroed<uint32_t>(c, 1);
+	const Work w{rc.bins, mc, hv, m, ep};
+	if (hv.coo) numeric_coo(c, a, w, nsegs, sk, res);
+	else numeric_digest(c, a, w, sk, res);
+	SPS_HIP(hipEventRecord(c->ev[EV_END], st));
+	SPS_HIP(hipEventSynchronize(c->ev[EV_END]));
+	res->ms_symbolic = elapsed(c->ev[EV_CONSOLIDATED], c->ev[EV_SYMBOLIC]);
+	res->ms_numeric = elapsed(c->ev[EV_SYMBOLIC], c->ev[EV_END]);
+	if (hv.n) { res->ms_tiles = elapsed(c->ev2[EV2_TILES_BEGIN], c->ev2[EV2_TILES_END]); res->ms_direct = elapsed(c->ev2[EV2_TILES_END], c->ev2[EV2_DIRECT_END]); }    // (COO: of the STORE launches)
+}
 
-		SPS_HIP(hipEventRecord(c->ev[3], st));
-		launch_light<MODE_COUNT>(c, bins, m, ep, sk);
-		launch_mid<MODE_COUNT>(c, bins, mc, m, ep, sk);
-		if (hv.n) heavy_sort_lists(c, hv);
-		launch_heavy_hash<MODE_COUNT>(c, hv, m, ep, sk);
-		c->join_side(true, true);
-		launch_heavy_dense<MODE_COUNT>(c, hv, m, ep, sk);
-		scan_exclusive_u32_i64(c, segcount, segoff, (size_t)nsegs);
-		int64_t reserved = read_back(c, segoff + nsegs);
-		OutSet &os = a.out ? *a.out : c->out[c->cur_out];   // chosen by multiply_body: never the set an operand lives in
-		os.i.ensure((size_t)reserved * sizeof(int32_t));
-		os.j.ensure((size_t)reserved * sizeof(int32_t));
-		os.v.ensure((size_t)reserved * sizeof(double));
-		sk.out_i = (int32_t *)os.i.p; sk.out_j = (int32_t *)os.j.p; sk.out_v = (double *)os.v.p;
-		SPS_HIP(hipEventRecord(c->ev[4], st));
-		launch_light<MODE_STORE>(c, bins, m, ep, sk);
-		launch_mid<MODE_STORE>(c, bins, mc, m, ep, sk);
-		SPS_HIP(hipEventRecord(c->ev[5], st));
-		launch_heavy_hash<MODE_STORE>(c, hv, m, ep, sk);
-		SPS_HIP(hipEventRecord(c->ev[6], st));
-		launch_heavy_dense<MODE_STORE>(c, hv, m, ep, sk);
-		SPS_HIP(hipEventRecord(c->ev[8], st));
-		struct HolesErr { unsigned long long holes, err; };
-		unsigned long long *holes = c->arena.get<unsigned long long>(2);
-		fill_zero(c, holes, 2 * sizeof(unsigned long long));
-		k_seg_holes<<<dim3(grid_for((size_t)nsegs)), dim3(256), 0, st>>>(segcount, segactual, (uint32_t)nsegs, holes, sk.err);
+// ---- by column blocks of op(B) (their kernels, and why: above)
+struct BlockOut { int32_t *i = nullptr, *j = nullptr; double *v = nullptr; uint64_t n = 0; };
+struct Blocks {                                                     // the blocks' COO outputs until they are interleaved
+	std::vector<BlockOut> b;
+	~Blocks() { for (auto &x : b) { (void)hipFree(x.i); (void)hipFree(x.j); (void)hipFree(x.v); } }
+};
+
+static void accumulate_block(spsamd_result &acc, const spsamd_result &rs)
+{
+	acc.products += rs.products; acc.products_light += rs.products_light; acc.products_mid += rs.products_mid;
+	acc.products_heavy += rs.products_heavy; acc.products_dense += rs.products_dense; acc.products_tiles += rs.products_tiles;
+	acc.cells_hash += rs.cells_hash; acc.cells_dense += rs.cells_dense; acc.window = std::max(acc.window, rs.window);
+	acc.rows_light = std::max(acc.rows_light, rs.rows_light); acc.rows_mid = std::max(acc.rows_mid, rs.rows_mid);
+	acc.rows_heavy = std::max(acc.rows_heavy, rs.rows_heavy);
+	acc.ms_symbolic += rs.ms_symbolic; acc.ms_numeric += rs.ms_numeric; acc.ms_light += rs.ms_light; acc.ms_mid += rs.ms_mid;
+	acc.ms_heavy += rs.ms_heavy; acc.ms_dense += rs.ms_dense; acc.ms_tiles += rs.ms_tiles;
+}
+
+// One block: B restricted to columns [c0, c1), rebased, through the ordinary path into the COO sink; its tuples then feed the digest `dsk` or are kept in `blocks`
+static void multiply_block(spsamd_ctx *c, const MultiplyArgs &a, uint64_t c0, uint64_t c1, const SinkParams &dsk, spsamd_result &acc, Blocks &blocks)
+{
+	hipStream_t st = c->stream;
+	const ConMat &B = a.B;
+	uint8_t *flag = c->arena.get<uint8_t>(B.nnz);
+	uint32_t *off = c->arena.get<uint32_t>((size_t)B.nnz + 1);
+	k_col_flag<<<dim3(grid_for(B.nnz)), dim3(256), 0, st>>>(B.col, B.nnz, (uint32_t)c0, (uint32_t)c1, flag);
+	SPS_LAUNCH_CHECK();
+	scan_exclusive_u8_u32(c, flag, off, B.nnz);
+	const uint32_t nb = read_back(c, off + B.nnz);
+	if (!nb) return;
+	MultiplyArgs as = a;
+	as.pb = nullptr; as.b_ready = nullptr;                          // (B restricted to the block: nothing of B's record applies)
+	as.B.row = c->arena.get<int32_t>(nb); as.B.col = c->arena.get<int32_t>(nb); as.B.val = c->arena.get<double>(nb);
+	as.B.nnz = nb; as.B.nrow = B.nrow; as.B.ncol = c1 - c0;
+	k_col_compact<<<dim3(grid_for(B.nnz)), dim3(256), 0, st>>>(B.row, B.col, B.val, flag, off, B.nnz, (uint32_t)c0, as.B.row, as.B.col, as.B.val);
+	SPS_LAUNCH_CHECK();
+	if (as.sk.present) { as.sk.pos += c0; as.sk.dim = c1 - c0; }
+	as.sink_kind = SPSAMD_SINK_COO;
+	as.sink_flags = a.sink_flags & (SPSAMD_SINK_ORDERED | SPSAMD_SINK_EXACT_PATTERN);
+	spsamd_result rs{};
+	try { spgemm_once(c, as, &rs); }
+	catch (const TooWide &) { throw Error{SPSAMD_ENOMEM, "the window indices of a column block of op(B) do not fit the device"}; }
+	accumulate_block(acc, rs);
+	if (!rs.nnz) return;
+	if (a.sink_kind != SPSAMD_SINK_COO) {
+		k_block_digest<<<dim3(std::min<unsigned>(grid_for((size_t)rs.nnz), 4096u)), dim3(256), 0, st>>>(rs.idx0, rs.idx1, rs.val, rs.nnz, (uint32_t)c0, dsk.digest, dsk.row_nnz, dsk.row_sum, dsk.row_hash);
 		SPS_LAUNCH_CHECK();
-		const HolesErr he = read_back(c, (const HolesErr *)holes);
-		if (he.err) throw Error{SPSAMD_EINVAL, "internal error: a numeric kernel met a cell larger than its class allows"};
-		unsigned long long nholes = he.holes;
-		uint64_t nnz = (uint64_t)reserved - nholes;
-		if (nholes) {
-			// sums that cancelled to exactly 0 left gaps: close them (rare path)
-			int64_t *newoff = c->arena.get<int64_t>((size_t)nsegs + 1);
-			scan_exclusive_u32_i64(c, segactual, newoff, (size_t)nsegs);
-			int32_t *ti = c->arena.get<int32_t>(nnz ? nnz : 1), *tj = c->arena.get<int32_t>(nnz ? nnz : 1);
-			double *tv = c->arena.get<double>(nnz ? nnz : 1);
-			k_seg_gather<<<dim3(grid_for((size_t)nsegs)), dim3(256), 0, st>>>(segoff, newoff, segactual, (uint32_t)nsegs,
-				sk.out_i, sk.out_j, sk.out_v, ti, tj, tv);
-			SPS_LAUNCH_CHECK();
-			SPS_HIP(hipMemcpyAsync(sk.out_i, ti, nnz * sizeof(int32_t), hipMemcpyDeviceToDevice, st));
-			SPS_HIP(hipMemcpyAsync(sk.out_j, tj, nnz * sizeof(int32_t), hipMemcpyDeviceToDevice, st));
-			SPS_HIP(hipMemcpyAsync(sk.out_v, tv, nnz * sizeof(double), hipMemcpyDeviceToDevice, st));
-			SPS_HIP(hipStreamSynchronize(st));
-		}
-		res->nnz = nnz;
-		res->idx0 = sk.out_i; res->idx1 = sk.out_j; res->val = sk.out_v;
-		ms_light = elapsed(c->ev[4], c->ev[5]);
-		ms_heavy = elapsed(c->ev[5], c->ev[8]); ms_dense = elapsed(c->ev[6], c->ev[8]);
+		return;
 	}
-	SPS_HIP(hipEventRecord(c->ev[7], st));
-	SPS_HIP(hipEventSynchronize(c->ev[7]));
-	res->ms_symbolic = elapsed(c->ev[1], c->ev[2]);
-	res->ms_numeric = elapsed(c->ev[2], c->ev[7]);
-	res->ms_light = ms_light; res->ms_mid = ms_mid; res->ms_heavy = ms_heavy; res->ms_dense = ms_dense;
-	if (hv.n) { res->ms_tiles = elapsed(c->ev2[0], c->ev2[1]); res->ms_direct = elapsed(c->ev2[1], c->ev2[2]); }    // (COO: of the STORE launches)
+	blocks.b.push_back(BlockOut{});                                 // (first, so that what was allocated is freed if the rest fails)
+	BlockOut &bo = blocks.b.back();
+	bo.n = rs.nnz;
+	if (hipMalloc((void **)&bo.i, rs.nnz * sizeof(int32_t)) != hipSuccess || hipMalloc((void **)&bo.j, rs.nnz * sizeof(int32_t)) != hipSuccess ||
+		hipMalloc((void **)&bo.v, rs.nnz * sizeof(double)) != hipSuccess) {
+		(void)hipGetLastError();
+		throw Error{SPSAMD_ENOMEM, "hipMalloc of a column block's output failed"};
+	}
+	SPS_HIP(hipMemcpyAsync(bo.i, rs.idx0, rs.nnz * sizeof(int32_t), hipMemcpyDeviceToDevice, st));
+	SPS_HIP(hipMemcpyAsync(bo.j, rs.idx1, rs.nnz * sizeof(int32_t), hipMemcpyDeviceToDevice, st));
+	SPS_HIP(hipMemcpyAsync(bo.v, rs.val, rs.nnz * sizeof(double), hipMemcpyDeviceToDevice, st));
+	k_add_col<<<dim3(grid_for((size_t)rs.nnz)), dim3(256), 0, st>>>(bo.j, rs.nnz, (uint32_t)c0);
+	SPS_LAUNCH_CHECK();
+}
+
+// The COO result: the blocks' outputs -- each row-major -- interleaved row by row into the context's current output set
+static void interleave_blocks(spsamd_ctx *c, uint64_t nrow, const Blocks &blocks, spsamd_result *res)
+{
+	hipStream_t st = c->stream;
+	uint64_t total = 0;
+	for (auto &x : blocks.b) total += x.n;
+	const CooOut o = grow_output(c->out[c->cur_out], (size_t)total);
+	uint32_t *cnt = c->arena.get<uint32_t>(nrow ? nrow : 1), *cur = c->arena.get<uint32_t>(nrow ? nrow : 1);
+	int64_t *rowoff = c->arena.get<int64_t>((size_t)nrow + 1);
+	fill_zero(c, cnt, nrow * sizeof(uint32_t));
+	fill_zero(c, cur, nrow * sizeof(uint32_t));
+	// a block's row pointer lives in the workspace for one step: place its tuples (second round), then add its rows' counts to `into`
+	auto add_counts = [&](const BlockOut &x, bool place, uint32_t *into) {
+		const Arena::Mark mk = c->arena.mark();
+		ConMat t; t.row = x.i; t.nnz = (uint32_t)x.n; t.nrow = nrow;
+		const uint32_t *rp = dense_rowptr(c, t, 0);
+		if (place) { k_block_place<<<dim3(grid_for((size_t)x.n)), dim3(256), 0, st>>>(x.i, x.j, x.v, x.n, rp, rowoff, cur, o.row, o.col, o.val); SPS_LAUNCH_CHECK(); }
+		k_row_add_counts<<<dim3(grid_for(nrow)), dim3(256), 0, st>>>(rp, nrow, into);
+		SPS_LAUNCH_CHECK();
+		SPS_HIP(hipStreamSynchronize(st));
+		c->arena.rewind(mk);
+	};
+	for (auto &x : blocks.b) {
+		if (x.n >= (uint64_t(1) << 32)) throw Error{SPSAMD_EINVAL, "a column block of the product has 2^32 tuples or more"};
+		add_counts(x, false, cnt);
+	}
+	scan_exclusive_u32_i64(c, cnt, rowoff, nrow);
+	for (auto &x : blocks.b) add_counts(x, true, cur);
+	res->nnz = total;
+	res->idx0 = o.row; res->idx1 = o.col; res->val = o.val;
 }
 
 static void spgemm_column_blocks(spsamd_ctx *c, MultiplyArgs &a, spsamd_result *res, uint64_t colblk)
 {
-	hipStream_t st = c->stream;
 	const ConMat &A = a.A, &B = a.B;
 	const bool coo = a.sink_kind == SPSAMD_SINK_COO;
-	const uint32_t nblk = (uint32_t)((B.ncol + colblk - 1) / colblk);
 	wait_b_tuples(c, a);
 	c->own[c->cur_out].sort0 = -1;                                  // (the blocks go through that output set, whatever the sink)
-	struct BlockOut { int32_t *i = nullptr, *j = nullptr; double *v = nullptr; uint64_t n = 0; };
-	struct Blocks {                                                 // the blocks' COO outputs until they are interleaved
-		std::vector<BlockOut> b;
-		~Blocks() { for (auto &x : b) { (void)hipFree(x.i); (void)hipFree(x.j); (void)hipFree(x.v); } }
-	} blocks;
-	DigestSlot *slots = nullptr;
-	SinkParams rsk{};
-	spsamd_result rres{};
-	if (!coo) {
-		slots = c->arena.get<DigestSlot>(DIGEST_SLOTS + 1);
-		fill_zero(c, slots, (DIGEST_SLOTS + 1) * sizeof(DigestSlot));
-		if (a.sink_flags & SPSAMD_SINK_ROWSTATS) rowstats_begin(c, A.nrow, rsk, &rres);
-	}
-	long long *const row_nnz = rsk.row_nnz; double *const row_sum = rsk.row_sum; unsigned long long *const row_hash = rsk.row_hash;
+	Blocks blocks; DigestSlot *slots = nullptr; SinkParams dsk{};
+	spsamd_result rstats{};                                         // (the row statistics: attached to res at the end only, res being the blocks' sum)
+	if (!coo) slots = digest_begin(c, a, A.nrow, dsk, &rstats);
 	spsamd_result acc{};
-	for (uint32_t s = 0; s < nblk; ++s) {
-		const uint64_t c0 = (uint64_t)s * colblk, c1 = std::min<uint64_t>(B.ncol, c0 + colblk);
+	acc.shape0 = res->shape0; acc.shape1 = res->shape1;
+	for (uint64_t c0 = 0; c0 < B.ncol; c0 += colblk) {
 		const Arena::Mark mk = c->arena.mark();
-		// B restricted to columns [c0, c1), rebased; the tuples keep their (row, column) order
-		uint8_t *flag = c->arena.get<uint8_t>(B.nnz);
-		uint32_t *off = c->arena.get<uint32_t>((size_t)B.nnz + 1);
-		k_col_flag<<<dim3(grid_for(B.nnz)), dim3(256), 0, st>>>(B.col, B.nnz, (uint32_t)c0, (uint32_t)c1, flag);
-		SPS_LAUNCH_CHECK();
-		scan_exclusive_u8_u32(c, flag, off, B.nnz);
-		const uint32_t nb = read_back(c, off + B.nnz);
-		if (nb) {
-			MultiplyArgs as = a;
-			as.pb = nullptr;                                            // (B restricted to the block: nothing of B's record applies)
-			as.b_ready = nullptr;
-			as.B.row = c->arena.get<int32_t>(nb); as.B.col = c->arena.get<int32_t>(nb); as.B.val = c->arena.get<double>(nb);
-			as.B.nnz = nb; as.B.nrow = B.nrow; as.B.ncol = c1 - c0;
-			k_col_compact<<<dim3(grid_for(B.nnz)), dim3(256), 0, st>>>(B.row, B.col, B.val, flag, off, B.nnz, (uint32_t)c0, as.B.row, as.B.col, as.B.val);
-			SPS_LAUNCH_CHECK();
-			if (as.sk.present) { as.sk.pos += c0; as.sk.dim = c1 - c0; }
-			as.sink_kind = SPSAMD_SINK_COO;
-			as.sink_flags = a.sink_flags & (SPSAMD_SINK_ORDERED | SPSAMD_SINK_EXACT_PATTERN);
-			spsamd_result rs{};
-			try { spgemm_once(c, as, &rs); }
-			catch (const TooWide &) { throw Error{SPSAMD_ENOMEM, "the window indices of a column block of op(B) do not fit the device"}; }
-			acc.products += rs.products; acc.products_light += rs.products_light; acc.products_mid += rs.products_mid;
-			acc.products_heavy += rs.products_heavy; acc.products_dense += rs.products_dense; acc.products_tiles += rs.products_tiles;
-			acc.cells_hash += rs.cells_hash; acc.cells_dense += rs.cells_dense; acc.window = std::max(acc.window, rs.window);
-			acc.rows_light = std::max(acc.rows_light, rs.rows_light); acc.rows_mid = std::max(acc.rows_mid, rs.rows_mid);
-			acc.rows_heavy = std::max(acc.rows_heavy, rs.rows_heavy);
-			acc.ms_symbolic += rs.ms_symbolic; acc.ms_numeric += rs.ms_numeric; acc.ms_light += rs.ms_light; acc.ms_mid += rs.ms_mid;
-			acc.ms_heavy += rs.ms_heavy; acc.ms_dense += rs.ms_dense; acc.ms_tiles += rs.ms_tiles;
-			if (rs.nnz) {
-				if (!coo) {
-					k_block_digest<<<dim3(std::min<unsigned>(grid_for((size_t)rs.nnz), 4096u)), dim3(256), 0, st>>>(rs.idx0, rs.idx1, rs.val, rs.nnz, (uint32_t)c0, slots, row_nnz, row_sum, row_hash);
-					SPS_LAUNCH_CHECK();
-				} else {
-					BlockOut bo;
-					bo.n = rs.nnz;
-					if (hipMalloc((void **)&bo.i, rs.nnz * sizeof(int32_t)) != hipSuccess || hipMalloc((void **)&bo.j, rs.nnz * sizeof(int32_t)) != hipSuccess ||
-						hipMalloc((void **)&bo.v, rs.nnz * sizeof(double)) != hipSuccess) {
-						(void)hipGetLastError();
-						(void)hipFree(bo.i); (void)hipFree(bo.j); (void)hipFree(bo.v);
-						throw Error{SPSAMD_ENOMEM, "hipMalloc of a column block's output failed"};
-					}
-					blocks.b.push_back(bo);
-					SPS_HIP(hipMemcpyAsync(bo.i, rs.idx0, rs.nnz * sizeof(int32_t), hipMemcpyDeviceToDevice, st));
-					SPS_HIP(hipMemcpyAsync(bo.j, rs.idx1, rs.nnz * sizeof(int32_t), hipMemcpyDeviceToDevice, st));
-					SPS_HIP(hipMemcpyAsync(bo.v, rs.val, rs.nnz * sizeof(double), hipMemcpyDeviceToDevice, st));
-					k_add_col<<<dim3(grid_for((size_t)rs.nnz)), dim3(256), 0, st>>>(bo.j, rs.nnz, (uint32_t)c0);
-					SPS_LAUNCH_CHECK();
-				}
-			}
-		}
-		SPS_HIP(hipStreamSynchronize(st));                          // (the block's workspace is handed back)
+		multiply_block(c, a, c0, std::min<uint64_t>(B.ncol, c0 + colblk), dsk, acc, blocks);
+		SPS_HIP(hipStreamSynchronize(c->stream));                   // (the block's workspace is handed back)
 		c->arena.rewind(mk);
 	}
 	*res = acc;
 	res->nnz_a = A.nnz; res->nnz_b = B.nnz;
-	if (!coo) {
-		uint32_t *noerr = c->arena.get<uint32_t>(1);
-		fill_zero(c, noerr, sizeof(uint32_t));
-		k_digest_reduce<<<dim3(1), dim3(64), 0, st>>>(slots, slots + DIGEST_SLOTS, noerr);
-		SPS_LAUNCH_CHECK();
-		const DigestSlot d = read_back(c, slots + DIGEST_SLOTS);
-		res->nnz = d.count; res->hash = d.hash; res->sum = d.sum;
-		if (row_nnz) { res->row_nnz = (const int64_t *)row_nnz; res->row_sum = row_sum; res->row_hash = (const uint64_t *)row_hash; }
-		return;
-	}
-	// ---- interleave the blocks row by row
-	uint64_t total = 0;
-	for (auto &x : blocks.b) total += x.n;
-	OutSet &os = c->out[c->cur_out];
-	os.i.ensure((size_t)total * sizeof(int32_t)); os.j.ensure((size_t)total * sizeof(int32_t)); os.v.ensure((size_t)total * sizeof(double));
-	int32_t *oi = (int32_t *)os.i.p, *oj = (int32_t *)os.j.p; double *ov = (double *)os.v.p;
-	uint32_t *cnt = c->arena.get<uint32_t>(A.nrow ? A.nrow : 1), *cur = c->arena.get<uint32_t>(A.nrow ? A.nrow : 1);
-	int64_t *rowoff = c->arena.get<int64_t>((size_t)A.nrow + 1);
-	fill_zero(c, cnt, A.nrow * sizeof(uint32_t));
-	fill_zero(c, cur, A.nrow * sizeof(uint32_t));
-	auto block_rowptr = [&](const BlockOut &x) {
-		ConMat t; t.row = x.i; t.nnz = (uint32_t)x.n; t.nrow = A.nrow;
-		return dense_rowptr(c, t, 0);
-	};
-	for (auto &x : blocks.b) {
-		if (x.n >= (uint64_t(1) << 32)) throw Error{SPSAMD_EINVAL, "a column block of the product has 2^32 tuples or more"};
-		const Arena::Mark mk = c->arena.mark();
-		const uint32_t *rp = block_rowptr(x);
-		k_row_add_counts<<<dim3(grid_for(A.nrow)), dim3(256), 0, st>>>(rp, A.nrow, cnt);
-		SPS_LAUNCH_CHECK();
-		SPS_HIP(hipStreamSynchronize(st));
-		c->arena.rewind(mk);
-	}
-	scan_exclusive_u32_i64(c, cnt, rowoff, A.nrow);
-	for (auto &x : blocks.b) {
-		const Arena::Mark mk = c->arena.mark();
-		const uint32_t *rp = block_rowptr(x);
-		k_block_place<<<dim3(grid_for((size_t)x.n)), dim3(256), 0, st>>>(x.i, x.j, x.v, x.n, rp, rowoff, cur, oi, oj, ov);
-		SPS_LAUNCH_CHECK();
-		k_row_add_counts<<<dim3(grid_for(A.nrow)), dim3(256), 0, st>>>(rp, A.nrow, cur);
-		SPS_LAUNCH_CHECK();
-		SPS_HIP(hipStreamSynchronize(st));
-		c->arena.rewind(mk);
-	}
-	res->nnz = total;
-	res->idx0 = oi; res->idx1 = oj; res->val = ov;
-}
-
-void spgemm_row_slice(spsamd_ctx *c, MultiplyArgs &a, spsamd_result *res)
-{
-	spgemm_once(c, a, res);
+	if (coo) { interleave_blocks(c, A.nrow, blocks, res); return; }
+	// the blocks' kernels had error words of their own, checked block by block and gone with the blocks' workspace: a fresh zero
+	digest_end(c, slots, get_zeroed<uint32_t>(c, 1), res);
+	res->row_nnz = rstats.row_nnz; res->row_sum = rstats.row_sum; res->row_hash = rstats.row_hash;
 }
 
 void spgemm(spsamd_ctx *c, MultiplyArgs &a, spsamd_result *res)
@@ -882,11 +864,7 @@ void spgemm(spsamd_ctx *c, MultiplyArgs &a, spsamd_result *res)
 	}
 	SPS_HIP(hipStreamSynchronize(c->stream));
 	c->arena.rewind(mk);
-	const spsamd_result keep = *res;
-	*res = spsamd_result{};
-	res->shape0 = keep.shape0; res->shape1 = keep.shape1;
-	spgemm_column_blocks(c, a, res, colblk);
-	res->shape0 = keep.shape0; res->shape1 = keep.shape1;
+	spgemm_column_blocks(c, a, res, colblk);                        // (keeps res's shape, replaces whatever else the first attempt left there)
 }
 
 } // namespace spsamd

@@ -83,9 +83,9 @@ void heavy_prepare(spsamd_ctx *c, Heavy &hv, const Bins &bins, const RowMeta &m,
 void heavy_cells(spsamd_ctx *c, Heavy &hv, const RowMeta &m, const uint32_t *segbase);
 void heavy_sort_lists(spsamd_ctx *c, Heavy &hv);
 
-// ---- the streamed product's row slice (spgemm.hip): a.A holds a run of whole rows of op(A) (its tuple arrays offset, nrow
-// unchanged); the COO result goes to a.out.  Never by column blocks: a product that would need them throws TooWide.
-void spgemm_row_slice(spsamd_ctx *c, MultiplyArgs &a, spsamd_result *res);
+// ---- one multiply in one pass (spgemm.hip).  Also the streamed product's row slice: a.A holds a run of whole rows of op(A) (its tuple
+// arrays offset, nrow unchanged); the COO result goes to a.out.  Never by column blocks: a product that would need them throws TooWide.
+void spgemm_once(spsamd_ctx *c, MultiplyArgs &a, spsamd_result *res);
 
 #ifdef SPSAMD_ABLATIONS
 void set_ablation_word(spsamd_ctx *c, int word);          // k_hash.hip (the only unit that reads it through ABLG)
