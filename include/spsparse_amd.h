@@ -209,6 +209,13 @@ const char *spsamd_version(void);
  *                                     heavy (a workgroup per row, keys re-read from memory) kernel wherever that kernel can
  *                                     hold the row; a row too long for the forced class falls to the next one (default: by
  *                                     row length)
+ *   extract_path    1 | 2 | 3 | 4     extract: 1 every output row through the permuted path (emit, then order), even where the
+ *                                     in-order path applies; 2 | 3 | 4 the same, with every output row of two or more tuples
+ *                                     through the light (a wave per row, at most 64 tuples) | mid (a workgroup per row, keys
+ *                                     in LDS, at most 4096 tuples) | heavy (one radix sort over all such rows) ordering kernel
+ *                                     wherever that kernel can hold the row; a row too long for the forced class falls to the
+ *                                     next one (default: in order where J ascends and S is column-ordered, else by row
+ *                                     length)
  * The environment variables of the same purpose (SPSAMD_W ...) are read once, inside spsamd_ctx_create; nothing reads
  * the environment later.  Unknown names: SPSAMD_EINVAL. */
 int spsamd_ctx_set_tuning(spsamd_ctx *ctx, const char *name, long value);
@@ -414,6 +421,47 @@ int spsamd_add(spsamd_ctx *ctx,
 
 int spsamd_select(spsamd_ctx *ctx, const spsamd_coo *A, char transpose,
 	int predicate, int64_t iparam, double dparam, int select_flags,
+	int duplicate_policy, int zero_nan,
+	int sink_kind, int sink_flags, spsamd_result *result);
+
+/*
+ * ret = op(A)(I, J), the submatrix (or reordering) of op(A) by a row list I and a column list J  -- GraphBLAS GrB_extract:
+ * A_FC / A_CC of a C/F splitting, a Schwarz subdomain A(I, I), an induced subgraph, P*A*P^T for a permutation, a row block.
+ * No value is computed.
+ *   - Operand.  op(A) is taken exactly as spsamd_select takes it (above), with duplicate_policy and zero_nan: a raw operand
+ *     is consolidated by op()'s rows; an operand whose sort0 names op()'s row order is trusted as stored and rejected
+ *     (SPSAMD_EINVAL) if its leading index descends; a SINK_COO result of this context and a prepared handle of the same
+ *     transpose are read in place.  Host and device operands.  Call the resulting sequence S.
+ *   - Lists.  rows holds nrows indices into rows(op(A)), cols holds ncols indices into cols(op(A)); both live where
+ *     index_mem says (SPSAMD_MEM_HOST or SPSAMD_MEM_DEVICE).  SPSAMD_EXTRACT_ALL (NULL) stands for every index of that
+ *     dimension, ascending (GrB_ALL); its count is ignored.  A list may be in any order and may name an index more than
+ *     once: a row named twice is delivered twice, a column named m times multiplies that column's tuples by m.
+ *   - Result.  Shape nrows x ncols.  For every output row r, output column c and tuple (I[r], J[c], v) of S at position p it
+ *     holds one tuple (r, c, v), and no other; the order is (r, c, p) ascending.  v keeps its bits (NaN payloads,
+ *     signalling NaNs, -0.0, the explicit zeros of a trusted operand): no value is computed, no floating-point comparison
+ *     is made.  For a consolidated S the result has every key once, row-major; for a trusted S with duplicate keys or
+ *     unordered rows the duplicates of a key follow each other in storage order.
+ * Sinks as for spsamd_select: SINK_COO (fetchable, usable with spsamd_result_scatter_dense, chainable as a MEM_DEVICE
+ * sort0 = 0 operand -- sort0 = 1 with SINK_PERMUTE, which swaps the index arrays and the shape), SINK_DIGEST (+ ROWSTATS
+ * over the nrows output rows); SINK_ORDERED and SINK_EXACT_PATTERN are accepted and change nothing.  The operand may live
+ * in the context's current output set: the result goes to the other set.
+ * result: shape, nnz, nnz_a (= |S|), ms_consolidate, ms_symbolic (list checks, column map, count, scan), ms_numeric (emit and
+ * ordering), ms_total, workspace_bytes; rows_light / rows_mid / rows_heavy and tuples_light / tuples_mid / tuples_heavy: the
+ * output rows of two or more tuples, and their tuples, by the ordering kernel class that served them -- all 0 on the in-order
+ * path (J ALL or strictly ascending and S column-ordered inside its rows), where nothing needs ordering.  Everything else
+ * 0 / NULL.
+ * SPSAMD_EINVAL, with a message and nothing written: A or result NULL; index_mem neither HOST nor DEVICE, or a list
+ * pointer that is not of that kind; an entry of rows outside [0, rows(op(A))) or of cols outside [0, cols(op(A))) (the
+ * message names the first such position); nrows or ncols >= 2^31; a policy outside 0..2; an unknown sink; an index of A out
+ * of bounds; a result of 2^31 or more tuples (possible only with repeated indices; the message names the count); a device
+ * list that lies in the output set about to be written.  nrows == 0, ncols == 0 or an empty S: an empty result of shape
+ * nrows x ncols.  Returns when the result is complete.
+ */
+#define SPSAMD_EXTRACT_ALL NULL   /* rows / cols == NULL: every index of that dimension, ascending (GrB_ALL) */
+int spsamd_extract(spsamd_ctx *ctx, const spsamd_coo *A, char transpose,
+	const int32_t *rows, size_t nrows,      /* I: nrows indices into rows(op(A)); NULL: all rows (nrows ignored) */
+	const int32_t *cols, size_t ncols,      /* J: ncols indices into cols(op(A)); NULL: all columns (ncols ignored) */
+	int index_mem,                          /* SPSAMD_MEM_HOST or SPSAMD_MEM_DEVICE, for rows and cols together */
 	int duplicate_policy, int zero_nan,
 	int sink_kind, int sink_flags, spsamd_result *result);
 

@@ -527,6 +527,52 @@ void select(AccumulatorT &ret, MatT const &A, char transpose, int predicate, int
 	if (rc != 0) (*spsparse_error)(-1, "%s", spsamd_last_error(ctx));
 }
 
+// ---- submatrix by index lists ---------------------------------------------------------------------------------------
+// ret receives op(A)(rows, cols) (spsamd_extract): for every output row r, output column c and tuple (rows[r], cols[c], v) of
+// op(A) one tuple (r, c, v), in (r, c, storage position) order, values bit for bit as stored.  A list may be in any order and
+// may repeat indices; `all` in place of a list (or a null pointer) stands for every index of that dimension, ascending.
+// op(A) is taken like multiply's left operand: consolidated with duplicate_policy and zero_nan unless it carries op()'s sort
+// order.
+struct all_t {};
+constexpr all_t all{};
+
+template <class MatT, class AccumulatorT>
+void extract(AccumulatorT &ret, MatT const &A, char transpose, std::vector<int> const *rows, std::vector<int> const *cols,
+	DuplicatePolicy duplicate_policy = DuplicatePolicy::ADD, bool zero_nan = false)
+{
+	static_assert(sizeof(int) == sizeof(int32_t), "index lists are int32");
+	std::array<int, 2> const &a_sort_order(transpose == 'T' ? COL_MAJOR : ROW_MAJOR);
+	ret.set_shape({rows ? rows->size() : (size_t)A.shape[a_sort_order[0]], cols ? cols->size() : (size_t)A.shape[a_sort_order[1]]});
+	spsamd_coo a = detail::as_coo(A);
+	spsamd_ctx *ctx = default_context().get();
+	if (!ctx) return;
+	static const int32_t none = 0;                 // what an empty list points at (a null pointer means every index)
+	const int32_t *pr = rows ? (rows->empty() ? &none : rows->data()) : nullptr;
+	const int32_t *pc = cols ? (cols->empty() ? &none : cols->data()) : nullptr;
+	spsamd_result res;
+	int rc = spsamd_extract(ctx, &a, transpose, pr, rows ? rows->size() : 0, pc, cols ? cols->size() : 0, SPSAMD_MEM_HOST,
+		(int)duplicate_policy, zero_nan ? 1 : 0, SPSAMD_SINK_COO, 0, &res);
+	if (rc != 0) { (*spsparse_error)(-1, "%s", spsamd_last_error(ctx)); return; }
+	rc = spsamd_result_fetch(ctx, &res, &detail::add_chunk<AccumulatorT>, &ret);
+	if (rc != 0) (*spsparse_error)(-1, "%s", spsamd_last_error(ctx));
+}
+template <class MatT, class AccumulatorT>
+void extract(AccumulatorT &ret, MatT const &A, char transpose, std::vector<int> const &rows, std::vector<int> const &cols,
+	DuplicatePolicy duplicate_policy = DuplicatePolicy::ADD, bool zero_nan = false)
+{ extract(ret, A, transpose, &rows, &cols, duplicate_policy, zero_nan); }
+template <class MatT, class AccumulatorT>
+void extract(AccumulatorT &ret, MatT const &A, char transpose, all_t, std::vector<int> const &cols,
+	DuplicatePolicy duplicate_policy = DuplicatePolicy::ADD, bool zero_nan = false)
+{ extract(ret, A, transpose, (std::vector<int> const *)nullptr, &cols, duplicate_policy, zero_nan); }
+template <class MatT, class AccumulatorT>
+void extract(AccumulatorT &ret, MatT const &A, char transpose, std::vector<int> const &rows, all_t,
+	DuplicatePolicy duplicate_policy = DuplicatePolicy::ADD, bool zero_nan = false)
+{ extract(ret, A, transpose, &rows, (std::vector<int> const *)nullptr, duplicate_policy, zero_nan); }
+template <class MatT, class AccumulatorT>
+void extract(AccumulatorT &ret, MatT const &A, char transpose, all_t, all_t,
+	DuplicatePolicy duplicate_policy = DuplicatePolicy::ADD, bool zero_nan = false)
+{ extract(ret, A, transpose, (std::vector<int> const *)nullptr, (std::vector<int> const *)nullptr, duplicate_policy, zero_nan); }
+
 // ---- VectorCooArray::consolidate on the device ---------------------------
 template <class IndexT, class ValT, int RANK>
 void VectorCooArray<IndexT, ValT, RANK>::consolidate(std::array<int, RANK> const &_sort_order,

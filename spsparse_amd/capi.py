@@ -25,6 +25,8 @@ SELECT_TRIL, SELECT_TRIU, SELECT_DIAG, SELECT_OFFDIAG, SELECT_ABS_GE, SELECT_ROW
 SELECT_COMPLEMENT = 1
 # ROW_TOPK: the longest row of the light (a wave per row) and of the mid (a workgroup per row, keys in LDS) kernel class
 select_light_max, select_mid_max = 64, 4096
+# extract: the longest output row of the light and of the mid ordering kernel class
+extract_light_max, extract_mid_max = 64, 4096
 
 ERRORS = {-1: "EDIM", -2: "EINVAL", -3: "EHIP", -4: "ENOMEM", -5: "ECAPACITY", -6: "ENODEVICE", -7: "EPEER"}
 
@@ -88,7 +90,7 @@ SYMBOLS = ["spsamd_ctx_create", "spsamd_ctx_destroy", "spsamd_last_error", "spsa
            "spsamd_dist_unique_id", "spsamd_dist_create", "spsamd_dist_destroy", "spsamd_dist_multiply",
            "spsamd_operand_prepare", "spsamd_operand_as_coo", "spsamd_operand_bytes", "spsamd_operand_destroy",
            "spsamd_multiply_dense", "spsamd_add", "spsamd_multiply_stream", "spsamd_multiply_masked",
-           "spsamd_multiply_sampled", "spsamd_select"]
+           "spsamd_multiply_sampled", "spsamd_select", "spsamd_extract"]
 
 _lib = None
 
@@ -139,6 +141,8 @@ def load():
                                           C.c_size_t, C.c_double, C.c_double, C.c_void_p, C.c_int]
     L.spsamd_select.argtypes = [C.c_void_p, P(Coo), C.c_char, C.c_int, C.c_int64, C.c_double, C.c_int, C.c_int, C.c_int,
                                 C.c_int, C.c_int, P(Result)]
+    L.spsamd_extract.argtypes = [C.c_void_p, P(Coo), C.c_char, C.c_void_p, C.c_size_t, C.c_void_p, C.c_size_t, C.c_int,
+                                 C.c_int, C.c_int, C.c_int, C.c_int, P(Result)]
     L.spsamd_memcpy.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_size_t]
     L.spsamd_consolidate.argtypes = [C.c_void_p, P(Coo), C.c_int, C.c_int, C.c_int, P(Result)]
     L.spsamd_sorted_permutation.argtypes = [C.c_void_p, P(Coo), C.c_int, C.c_void_p]
@@ -308,6 +312,21 @@ class Context:
         self._check(rc)
         return res
 
+    def extract(self, A, rows=None, cols=None, transpose='.', duplicate_policy=ADD, zero_nan=False, sink=SINK_COO, flags=0):
+        """spsamd_extract: the submatrix op(A)(rows, cols), values untouched, in (r, c, storage position) order.  rows, cols:
+        None for every index of that dimension, or int32 index lists -- numpy arrays (host lists) or torch CUDA tensors
+        (device lists), both of one kind; a list may be unordered and may repeat indices.  A: a Coo struct."""
+        args = [_index_list(rows, "rows"), _index_list(cols, "cols")]
+        mems = {m for _p, _n, m, _k in args if m is not None}
+        if len(mems) > 1:
+            raise ValueError("rows and cols must both be host (numpy) or both device (torch) lists")
+        res = Result()
+        rc = self.L.spsamd_extract(self.h, C.byref(A), transpose.encode(), args[0][0], args[0][1], args[1][0], args[1][1],
+                                   mems.pop() if mems else MEM_HOST, duplicate_policy, int(zero_nan), sink, flags, C.byref(res))
+        del args
+        self._check(rc)
+        return res
+
     def consolidate(self, A, so0, duplicate_policy=ADD, zero_nan=False):
         res = Result()
         self._check(self.L.spsamd_consolidate(self.h, C.byref(A), so0, duplicate_policy, int(zero_nan), C.byref(res)))
@@ -420,6 +439,33 @@ class Context:
 
     def gen_aggregation3d(self, N, p0, p1, pv):
         self._check(self.L.spsamd_gen_aggregation3d(self.h, N, p0, p1, pv))
+
+
+_EMPTY_LIST = np.zeros(1, np.int32)        # what an empty host list points at (NULL means every index)
+
+
+def _index_list(L, name):
+    """(pointer, count, mem, keepalive) of an index list argument of extract; (None, 0, None, None) for every index."""
+    if L is None:
+        return None, 0, None, None
+    if isinstance(L, np.ndarray) or isinstance(L, (list, tuple, range)):
+        a = np.asarray(L)
+        if a.size and a.dtype != np.int32:
+            if not np.issubdtype(a.dtype, np.integer) or isinstance(L, np.ndarray):
+                raise TypeError("%s must be int32" % name)
+        a = np.ascontiguousarray(a, dtype=np.int32)
+        if a.ndim != 1:
+            raise ValueError("%s must be 1-D" % name)
+        return (a if a.size else _EMPTY_LIST).ctypes.data, int(a.size), MEM_HOST, a
+    import torch
+    if not isinstance(L, torch.Tensor):
+        raise TypeError("%s must be None, a numpy int32 array or a torch CUDA int32 tensor" % name)
+    if L.dtype != torch.int32 or L.ndim != 1 or not L.is_contiguous():
+        raise TypeError("%s must be a contiguous 1-D int32 tensor" % name)
+    if L.device.type != "cuda":
+        raise ValueError("%s must be a device tensor (or a numpy array for a host list)" % name)
+    n = int(L.shape[0])
+    return (L.data_ptr() if n else _EMPTY_LIST.ctypes.data), n, (MEM_DEVICE if n else None), L
 
 
 def _rows(A):

@@ -92,6 +92,7 @@ struct Tuning {
 	int masked_path = 0;         // multiply_masked: 0 auto | 1 entry kernel for every key | 2 row kernel wherever A_i fits LDS | 3 wave kernel for every key
 	int sampled_path = 0;        // multiply_sampled: 0 auto | 1 lane kernel for every tuple | 2 slab kernel for every tuple (auto: by k and a probe of M's order)
 	int select_path = 0;         // select, ROW_TOPK: 0 by row length | 1 light | 2 mid | 3 heavy kernel for every row it can hold
+	int extract_path = 0;        // extract: 0 auto | 1 every row through the permuted path | 2 light | 3 mid | 4 heavy ordering kernel for every row it can hold
 #ifdef SPSAMD_ABLATIONS
 	int dbg = 0;
 #endif
@@ -426,6 +427,12 @@ void multiply_sampled(spsamd_ctx *c, const spsamd_coo *M, char transpose, const 
 // the tuples of op(A) a predicate keeps, into the sink: spsamd_select after its null checks
 void select_tuples(spsamd_ctx *c, const spsamd_coo *A, char transpose, int predicate, int64_t iparam, double dparam,
 	int select_flags, int duplicate_policy, int zero_nan, int sink_kind, int sink_flags, spsamd_result *res);
+
+// ---------------------------------------------------------------- submatrix by index lists (k_extract.hip)
+
+// op(A)(I, J) into the sink: spsamd_extract after its null checks (rows / cols null: every index of that dimension)
+void extract_tuples(spsamd_ctx *c, const spsamd_coo *A, char transpose, const int32_t *rows, size_t nrows, const int32_t *cols,
+	size_t ncols, int index_mem, int duplicate_policy, int zero_nan, int sink_kind, int sink_flags, spsamd_result *res);
 
 // The same operand struct twice (A * A): one consolidation can serve both sides (capi.hip).
 bool same_operand(const spsamd_coo *a, const spsamd_coo *b);
