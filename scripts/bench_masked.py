@@ -17,44 +17,10 @@ Byte model of the masked call: per evaluated key its two lists (12 B per tuple o
 the key itself (8 B), against 8 TB/s -- an upper bound of the traffic (lists shared by neighbouring keys hit in cache).
 One JSON line per measurement.
 """
-import argparse
-import json
-import os
-import sys
+import torch
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-if ROOT not in sys.path:
-    sys.path.insert(0, ROOT)
-
-import numpy as np  # noqa: E402
-import torch  # noqa: E402
-
-from spsparse_amd import capi  # noqa: E402
-
-PEAK = 8.0e12
-
-
-def dev_arrays(m, dev):
-    return (torch.empty(m, dtype=torch.int32, device=dev), torch.empty(m, dtype=torch.int32, device=dev),
-            torch.empty(m, dtype=torch.float64, device=dev))
-
-
-def ptrs(t):
-    return [x.data_ptr() for x in t]
-
-
-def time_call(stream, fn, reps, warmup):
-    for _ in range(warmup):
-        fn()
-    ms = []
-    for _ in range(reps):
-        e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-        e0.record(stream)
-        fn()
-        e1.record(stream)
-        e1.synchronize()
-        ms.append(e0.elapsed_time(e1))
-    return float(np.median(ms)), ms
+import opbench as ob
+from opbench import capi
 
 
 def coo_filter(ctx, stream, A, B, mkeys, ncol):
@@ -82,10 +48,7 @@ def coo_filter(ctx, stream, A, B, mkeys, ncol):
 
 
 def record(rows, name, impl, med, ms, **extra):
-    r = {"workload": name, "impl": impl, "ms": round(med, 4), "ms_all": [round(x, 4) for x in ms]}
-    r.update(extra)
-    print(json.dumps(r), flush=True)
-    rows.append(r)
+    ob.record(rows, {"workload": name, "impl": impl, **ob.times(med, ms), **extra})
 
 
 def bytes_model(la, lb):
@@ -100,26 +63,26 @@ def list_lengths(i, j, rowptr_a, colptr_b):
     return la[ok], lb[ok]
 
 
-def run(ctx, stream, rows, name, A, B, M, mi, mj, n, ncol, sink, a, paths, bytes_):
-    med, ms = time_call(stream, lambda: ctx.multiply_masked(A, B, M, sink=sink), a.reps, a.warmup)
+def run(ctx, stream, rows, name, A, B, M, mi, mj, ncol, sink, a, bytes_):
+    med, ms = ob.time_call(stream, lambda: ctx.multiply_masked(A, B, M, sink=sink), a.reps, a.warmup)
     res = ctx.multiply_masked(A, B, M, sink=sink)
     out = dict(nnz=int(res.nnz), products=int(res.products), keys=int(mi.numel()), algo_bytes=bytes_,
                tbps=round(bytes_ / med / 1e9, 3), ms_numeric=round(res.ms_numeric, 4))
     if sink == capi.SINK_DIGEST:
         out["sum"] = res.sum
     record(rows, name, "masked", med, ms, **out)
-    if paths:
+    if a.paths:
         for p in (1, 2, 3):
             ctx.set_tuning("masked_path", p)
-            med, ms = time_call(stream, lambda: ctx.multiply_masked(A, B, M, sink=sink), a.reps, a.warmup)
+            med, ms = ob.time_call(stream, lambda: ctx.multiply_masked(A, B, M, sink=sink), a.reps, a.warmup)
             record(rows, name, "masked_path=%d" % p, med, ms, tbps=round(bytes_ / med / 1e9, 3))
         ctx.set_tuning("masked_path", 0)
     mkeys = mi.to(torch.int64) * ncol + mj.to(torch.int64)
     res_f = []
-    med, ms = time_call(stream, lambda: res_f.append(coo_filter(ctx, stream, A, B, mkeys, ncol)), a.reps, a.warmup)
+    med, ms = ob.time_call(stream, lambda: res_f.append(coo_filter(ctx, stream, A, B, mkeys, ncol)), a.reps, a.warmup)
     cnt, tot, nfull = res_f[-1]
     record(rows, name, "coo+filter", med, ms, nnz=cnt, sum=tot, nnz_full=nfull, coo_bytes=16 * nfull)
-    med, ms = time_call(stream, lambda: ctx.multiply(A, B, sink=capi.SINK_DIGEST), a.reps, a.warmup)
+    med, ms = ob.time_call(stream, lambda: ctx.multiply(A, B, sink=capi.SINK_DIGEST), a.reps, a.warmup)
     d = ctx.multiply(A, B, sink=capi.SINK_DIGEST)
     record(rows, name, "unmasked digest", med, ms, nnz=int(d.nnz), products=int(d.products))
 
@@ -129,24 +92,15 @@ def rowptr(idx, n):
 
 
 def main():
-    ap = argparse.ArgumentParser()
-    ap.add_argument("--only", default="tri,poisson")
-    ap.add_argument("--reps", type=int, default=5)
-    ap.add_argument("--warmup", type=int, default=1)
+    ap = ob.parser("tri,poisson", reps=5, warmup=1)
     ap.add_argument("--paths", action="store_true")
     a = ap.parse_args()
-    dev = torch.device("cuda", 0)
-    stream = torch.cuda.Stream(dev)
-    ctx = capi.Context(0, stream.cuda_stream)
+    dev, stream, ctx = ob.open_context()
     rows = []
-    only = a.only.split(",")
-    if "tri" in only:
-        scale = 20
-        ne = 16 << scale
-        n = 1 << scale
-        t = dev_arrays(ne, dev)
-        ctx.gen_rmat(scale, 1, 0, ne, *ptrs(t))
-        torch.cuda.synchronize()
+
+    def tri():
+        R, t = ob.rmat(ctx, dev, 20)
+        n = int(R.shape0)
         u, v = t[0].long(), t[1].long()
         hi, lo = torch.maximum(u, v), torch.minimum(u, v)
         off = hi != lo
@@ -154,29 +108,24 @@ def main():
         del off
         li, lj = (k // n).to(torch.int32), (k % n).to(torch.int32)
         lv = torch.ones(li.numel(), dtype=torch.float64, device=dev)
-        del t, u, v, hi, lo, k
+        del R, t, u, v, hi, lo, k
         torch.cuda.synchronize()
         L = capi.device_coo(li.data_ptr(), lj.data_ptr(), lv.data_ptr(), li.numel(), (n, n), 0)
         rp = rowptr(li, n)
         cp = rowptr(lj, n)                                         # columns of L (op(B) = L)
         la, lb = list_lengths(li, lj, rp, cp)
-        run(ctx, stream, rows, "rmat_tri", L, L, L, li, lj, n, n, capi.SINK_DIGEST, a, a.paths, bytes_model(la, lb))
-        del L, li, lj, lv
-        torch.cuda.empty_cache()
-    if "poisson" in only:
-        N = 4096
-        n = N * N
-        t = dev_arrays(5 * N * N - 4 * N, dev)
-        ctx.gen_poisson2d(N, *ptrs(t))
-        torch.cuda.synchronize()
-        A = capi.device_coo(*ptrs(t), t[2].numel(), (n, n), 0)
+        run(ctx, stream, rows, "rmat_tri", L, L, L, li, lj, n, capi.SINK_DIGEST, a, bytes_model(la, lb))
+
+    def poisson():
+        A, t = ob.poisson2d(ctx, dev)
+        n = int(A.shape0)
         rp = rowptr(t[0], n)
         cp = rowptr(t[1], n)
         la, lb = list_lengths(t[0], t[1], rp, cp)
-        run(ctx, stream, rows, "poisson_AA_A", A, A, A, t[0], t[1], n, n, capi.SINK_COO, a, a.paths, bytes_model(la, lb))
-    print("%-14s %-18s %10s" % ("workload", "impl", "ms"))
-    for r in rows:
-        print("%-14s %-18s %10.3f" % (r["workload"], r["impl"], r["ms"]))
+        run(ctx, stream, rows, "poisson_AA_A", A, A, A, t[0], t[1], n, capi.SINK_COO, a, bytes_model(la, lb))
+
+    ob.run(a.only.split(","), [("tri", tri), ("poisson", poisson)])
+    ob.table(rows, [("workload", -14, "%s", "workload"), ("impl", -18, "%s", "impl"), ("ms", 10, "%.3f", "ms")])
     ctx.close()
 
 

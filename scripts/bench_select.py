@@ -17,41 +17,12 @@ Byte model: 16 B per tuple of S for every pass that reads it (tuple-wise: flag +
 compact = 3; ROW_TOPK: row pointer, selection, compact = 3) + 16 B per kept tuple, against 8 TB/s: reported, not gated.
 One JSON line per measurement, then a table with the ratio select / baseline (the gate: < 1 everywhere).
 """
-import argparse
-import json
-import os
-import sys
+import torch
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-if ROOT not in sys.path:
-    sys.path.insert(0, ROOT)
+import opbench as ob
+from opbench import capi
 
-import numpy as np  # noqa: E402
-import torch  # noqa: E402
-
-from spsparse_amd import capi  # noqa: E402
-
-PEAK = 8.0e12
 PASSES = {capi.SELECT_TRIL: 2, capi.SELECT_ABS_GE: 2, capi.SELECT_ROW_REL: 3, capi.SELECT_ROW_TOPK: 3}
-
-
-def dev_arrays(m, dev):
-    return (torch.empty(m, dtype=torch.int32, device=dev), torch.empty(m, dtype=torch.int32, device=dev),
-            torch.empty(m, dtype=torch.float64, device=dev))
-
-
-def ptrs(t):
-    return [x.data_ptr() for x in t]
-
-
-def copy_out(ctx, res, dev):
-    """A SINK_COO result in torch tensors of its own."""
-    n = int(res.nnz)
-    t = dev_arrays(n, dev)
-    for x, src, sz in zip(t, (res.idx0, res.idx1, res.val), (4, 4, 8)):
-        if n:
-            ctx.memcpy(x.data_ptr(), src, n * sz)
-    return t
 
 
 def torch_select(t, nrow, pred, ip, dp):
@@ -79,75 +50,42 @@ def torch_select(t, nrow, pred, ip, dp):
     return r[keep], c[keep], v[keep]
 
 
-def timed(stream, fn):
-    e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-    e0.record(stream)
-    out = fn()
-    e1.record(stream)
-    e1.synchronize()
-    return e0.elapsed_time(e1), out
-
-
 def main():
-    ap = argparse.ArgumentParser()
-    ap.add_argument("--only", default="poisson,rmat,raw,galerkin,square")
-    ap.add_argument("--reps", type=int, default=7)
-    ap.add_argument("--warmup", type=int, default=2)
-    a = ap.parse_args()
-    dev = torch.device("cuda", 0)
-    stream = torch.cuda.Stream(dev)
-    ctx = capi.Context(0, stream.cuda_stream)
+    a = ob.parser("poisson,rmat,raw,galerkin,square").parse_args()
+    dev, stream, ctx = ob.open_context()
     rows = []
     only = a.only.split(",")
 
     def measure(name, A, t, nrow, pred, ip=0, dp=0.0, baseline=None):
         """A: the operand of spsamd_select; t: the same tuples as torch tensors for the baseline."""
-        sel = lambda: ctx.select(A, pred, iparam=ip, dparam=dp)            # noqa: E731
+        def sel():
+            return ctx.select(A, pred, iparam=ip, dparam=dp)
 
         def base():
             with torch.cuda.stream(stream):
                 return baseline() if baseline else torch_select(t, nrow, pred, ip, dp)
-        ms_s, ms_b = [], []
-        for rep in range(a.warmup + a.reps):
-            m1, res = timed(stream, sel)
-            m2, out = timed(stream, base)
-            if rep >= a.warmup:
-                ms_s.append(m1); ms_b.append(m2)
-        got = copy_out(ctx, sel(), dev)              # (a baseline that consolidates writes the output set: select once more)
-        same = all(x.numel() == y.numel() for x, y in zip(got, out)) and torch.equal(got[0], out[0]) and \
-            torch.equal(got[1], out[1]) and torch.equal(got[2].view(torch.int64), out[2].view(torch.int64))
+        (s, ms_s), (b, ms_b), res, out = ob.time_pair(stream, sel, base, a.reps, a.warmup)
+        got = ob.copy_out(ctx, sel(), dev)           # (a baseline that consolidates writes the output set: select once more)
+        same = ob.same(got, out)
         nin, nout = int(res.nnz_a), int(res.nnz)
         by = 16.0 * nin * PASSES[pred] + 16.0 * nout
-        s, b = float(np.median(ms_s)), float(np.median(ms_b))
         for impl, med, ms in (("spsamd_select", s, ms_s), ("torch", b, ms_b)):
-            r = {"workload": name, "impl": impl, "ms": round(med, 4), "ms_all": [round(x, 4) for x in ms], "tuples_in": nin,
+            r = {"workload": name, "impl": impl, **ob.times(med, ms), "tuples_in": nin,
                  "tuples_out": nout, "same_tuples": bool(same)}
             if impl == "spsamd_select":
-                r.update({"passes": PASSES[pred], "model_bytes": by, "model_ms_at_8TBps": round(by / PEAK * 1e3, 4),
-                          "of_model": round(by / PEAK * 1e3 / med, 4), "ratio_to_torch": round(s / b, 4),
+                r.update({"passes": PASSES[pred], "model_bytes": by, "model_ms_at_8TBps": round(by / ob.PEAK * 1e3, 4),
+                          "of_model": round(by / ob.PEAK * 1e3 / med, 4), "ratio_to_torch": round(s / b, 4),
                           "rows_light": int(res.rows_light), "rows_mid": int(res.rows_mid), "rows_heavy": int(res.rows_heavy)})
-            print(json.dumps(r), flush=True)
-            rows.append(r)
+            ob.record(rows, r)
 
-    if "poisson" in only:
-        N = 4096
-        n = N * N
-        t = dev_arrays(5 * N * N - 4 * N, dev)
-        ctx.gen_poisson2d(N, *ptrs(t))
-        torch.cuda.synchronize()
-        A = capi.device_coo(*ptrs(t), t[2].numel(), (n, n), 0)
-        measure("poisson_tril", A, t, n, capi.SELECT_TRIL, ip=-1)
-        del t
-        torch.cuda.empty_cache()
-    if "rmat" in only or "raw" in only:
-        scale = 20
-        ne, n = 16 << scale, 1 << scale
-        raw = dev_arrays(ne, dev)
-        ctx.gen_rmat(scale, 1, 0, ne, *ptrs(raw))
-        torch.cuda.synchronize()
-        R = capi.device_coo(*ptrs(raw), ne, (n, n), -1)
-        t = copy_out(ctx, ctx.consolidate(R, 0), dev)
-        A = capi.device_coo(*ptrs(t), t[2].numel(), (n, n), 0)
+    def poisson():
+        A, t = ob.poisson2d(ctx, dev)
+        measure("poisson_tril", A, t, int(A.shape0), capi.SELECT_TRIL, ip=-1)
+
+    def rmat20():
+        R, raw = ob.rmat(ctx, dev, 20)
+        A, t = ob.consolidated(ctx, dev, R)
+        n = int(A.shape0)
         if "rmat" in only:
             med = float(t[2].abs().median().item())
             measure("rmat20_tril", A, t, n, capi.SELECT_TRIL, ip=-1)
@@ -157,48 +95,28 @@ def main():
             measure("rmat20_topk32", A, t, n, capi.SELECT_ROW_TOPK, ip=32)
         if "raw" in only:
             def raw_base():
-                c = copy_out(ctx, ctx.consolidate(R, 0), dev)
+                c = ob.copy_out(ctx, ctx.consolidate(R, 0), dev)
                 return torch_select(c, n, capi.SELECT_TRIL, -1, 0.0)
             measure("rmat20_raw_tril", R, None, n, capi.SELECT_TRIL, ip=-1, baseline=raw_base)
-        del raw, t
-        torch.cuda.empty_cache()
-    if "galerkin" in only:
-        g = 256
-        nf, nc = g ** 3, (g // 2) ** 3
-        ta, tr = dev_arrays(7 * g ** 3 - 6 * g * g, dev), dev_arrays(nf, dev)
-        ctx.gen_laplace3d(g, *ptrs(ta))
-        ctx.gen_aggregation3d(g, *ptrs(tr))
-        torch.cuda.synchronize()
-        A = capi.device_coo(*ptrs(ta), ta[2].numel(), (nf, nf), 0)
-        R = capi.device_coo(*ptrs(tr), nf, (nc, nf), 0)
-        T = ctx.multiply(R, A)
-        G = ctx.multiply(capi.result_operand(T), R, tB='T')
-        t = copy_out(ctx, G, dev)
-        measure("galerkin_rowrel", capi.result_operand(G), t, nc, capi.SELECT_ROW_REL, dp=0.25)
-        del ta, tr, t
-        torch.cuda.empty_cache()
-    if "square" in only:
-        scale = 16
-        ne, n = 16 << scale, 1 << scale
-        raw = dev_arrays(ne, dev)
-        ctx.gen_rmat(scale, 1, 0, ne, *ptrs(raw))
-        torch.cuda.synchronize()
-        R = capi.device_coo(*ptrs(raw), ne, (n, n), -1)
-        P = ctx.multiply(R, R)
-        t = copy_out(ctx, P, dev)
-        measure("square_topk32", capi.result_operand(P), t, n, capi.SELECT_ROW_TOPK, ip=32)
-        del raw, t
-        torch.cuda.empty_cache()
 
-    print("%-16s %-14s %10s %10s %9s %8s %6s" % ("workload", "impl", "ms", "model ms", "of model", "ratio", "same"))
-    for r in rows:
-        if r["impl"] == "spsamd_select":
-            print("%-16s %-14s %10.3f %10.3f %8.1f%% %8.3f %6s" % (r["workload"], r["impl"], r["ms"], r["model_ms_at_8TBps"],
-                                                                   100 * r["of_model"], r["ratio_to_torch"], r["same_tuples"]))
-        else:
-            print("%-16s %-14s %10.3f" % (r["workload"], r["impl"], r["ms"]))
-    bad = [r["workload"] for r in rows if r["impl"] == "spsamd_select" and (r["ratio_to_torch"] >= 1 or not r["same_tuples"])]
-    print("gate (select faster than torch, same tuples):", "holds" if not bad else "MISSED by " + ", ".join(bad))
+    def galerkin():
+        (A, ta), (R, tr) = ob.laplace3d(ctx, dev), ob.aggregation3d(ctx, dev)
+        G = ob.galerkin(ctx, A, R)
+        t = ob.copy_out(ctx, G, dev)
+        measure("galerkin_rowrel", capi.result_operand(G), t, int(R.shape0), capi.SELECT_ROW_REL, dp=0.25)
+
+    def square():
+        R, raw = ob.rmat(ctx, dev, 16)
+        P = ob.square(ctx, R)
+        t = ob.copy_out(ctx, P, dev)
+        measure("square_topk32", capi.result_operand(P), t, int(R.shape0), capi.SELECT_ROW_TOPK, ip=32)
+
+    ob.run(only, [("poisson", poisson), ("rmat raw", rmat20), ("galerkin", galerkin), ("square", square)])
+    ob.table(rows, [("workload", -16, "%s", "workload"), ("impl", -14, "%s", "impl"), ("ms", 10, "%.3f", "ms"),
+                    ("model ms", 10, "%.3f", "model_ms_at_8TBps"), ("of model", 9, "%.1f%%", ob.pct("of_model")),
+                    ("ratio", 8, "%.3f", "ratio_to_torch"), ("same", 6, "%s", lambda r: r["same_tuples"] if "passes" in r else None)])
+    ob.gate("select faster than torch, same tuples",
+            [r["workload"] for r in rows if r["impl"] == "spsamd_select" and (r["ratio_to_torch"] >= 1 or not r["same_tuples"])])
     ctx.close()
 
 

@@ -11,31 +11,16 @@ Workloads (R-MAT A*A, device generator, operands resident in HBM):
 Times: host wall clock around each call, median of --reps.  Rate: 16 B per tuple delivered / wall time.
 One JSON line per measurement.
 """
-import argparse
 import json
-import os
-import sys
 import time
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-if ROOT not in sys.path:
-    sys.path.insert(0, ROOT)
+import numpy as np
+import torch
 
-import numpy as np  # noqa: E402
-import torch  # noqa: E402
-
-from spsparse_amd import capi  # noqa: E402
+import opbench as ob
+from opbench import capi
 
 SCALES = {"s17": 17, "cfg2": 20, "over": 21}
-
-
-def rmat_operand(ctx, scale, dev):
-    m = 16 << scale
-    t = (torch.empty(m, dtype=torch.int32, device=dev), torch.empty(m, dtype=torch.int32, device=dev),
-         torch.empty(m, dtype=torch.float64, device=dev))
-    ctx.gen_rmat(scale, 1, 0, m, *[x.data_ptr() for x in t])
-    torch.cuda.synchronize()
-    return capi.device_coo(t[0].data_ptr(), t[1].data_ptr(), t[2].data_ptr(), m, (1 << scale, 1 << scale)), t
 
 
 class Counter:
@@ -71,27 +56,23 @@ def streamed(ctx, A, budget):
 
 
 def main():
-    ap = argparse.ArgumentParser()
-    ap.add_argument("--only", default="s17,cfg2")
-    ap.add_argument("--reps", type=int, default=3)
+    ap = ob.parser("s17,cfg2", reps=3, warmup=None)
     ap.add_argument("--budget", type=int, default=0, help="block_tuples (0: the library's default)")
     args = ap.parse_args()
     dev = torch.device("cuda:0")
     ctx = capi.Context(0)
     for name in args.only.split(","):
-        A, keep = rmat_operand(ctx, SCALES[name], dev)
+        A, keep = ob.rmat(ctx, dev, SCALES[name])
         rows = []
         for rep in range(args.reps):
             if name != "over":
                 ms, n, ms_dev = plain(ctx, A)
-                rows.append(dict(workload=name, path="multiply+fetch", rep=rep, ms_wall=ms, nnz_c=n, ms_device=ms_dev,
-                                 host_GBps=16 * n / ms / 1e6))
-                print(json.dumps(rows[-1]), flush=True)
+                ob.record(rows, dict(workload=name, path="multiply+fetch", rep=rep, ms_wall=ms, nnz_c=n, ms_device=ms_dev,
+                                     host_GBps=16 * n / ms / 1e6))
             ms, n, st = streamed(ctx, A, args.budget)
-            rows.append(dict(workload=name, path="stream", rep=rep, ms_wall=ms, nnz_c=n, ms_device=st.ms_device,
-                             ms_callback=st.ms_callback, blocks=st.blocks, block_tuples=st.block_tuples,
-                             device_output_bytes=st.device_output_bytes, host_GBps=16 * n / ms / 1e6))
-            print(json.dumps(rows[-1]), flush=True)
+            ob.record(rows, dict(workload=name, path="stream", rep=rep, ms_wall=ms, nnz_c=n, ms_device=st.ms_device,
+                                 ms_callback=st.ms_callback, blocks=st.blocks, block_tuples=st.block_tuples,
+                                 device_output_bytes=st.device_output_bytes, host_GBps=16 * n / ms / 1e6))
         for path in ("multiply+fetch", "stream"):
             r = [x for x in rows if x["path"] == path]
             if r:

@@ -11,6 +11,8 @@ import subprocess
 
 import pytest
 
+from tests.gpu_util import build_cpp_test
+
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 HEADER = os.path.join(ROOT, "include", "spsparse_amd.h")
 
@@ -53,16 +55,6 @@ def test_product_path_has_no_oracle_or_cpu_fallback():
             assert "import orc" not in src and "from oracle" not in src and "oracle/" not in src, f
 
 
-def _build_shim_test(tmp_path):
-    exe = os.path.join(str(tmp_path), "test_shim")
-    libdir = os.path.dirname(_lib())
-    cmd = ["g++", "-std=c++17", "-O1", "-Wall", "-I" + os.path.join(ROOT, "include"),
-           os.path.join(ROOT, "tests", "cpp", "test_shim.cpp"), "-o", exe, "-L" + libdir, "-lspsparse_amd",
-           "-Wl,-rpath," + libdir, "-Wl,-rpath,/opt/rocm/lib"]
-    subprocess.check_call(cmd)
-    return exe
-
-
 def _gpu_present():
     try:
         out = subprocess.run(["/opt/rocm/bin/rocminfo"], capture_output=True, text=True, timeout=60).stdout
@@ -77,7 +69,7 @@ def test_fails_loudly_without_gpu(tmp_path):
     with pytest.raises(capi.SpsamdError) as e:
         capi.Context()
     assert e.value.code == -6
-    exe = _build_shim_test(tmp_path)
+    exe = build_cpp_test("shim", tmp_path)
     out = subprocess.run([exe, "--abi-only"], capture_output=True, text=True, timeout=120)
     assert out.returncode == 0 and "fails loudly" in out.stdout
 
@@ -86,7 +78,7 @@ def test_fails_loudly_without_gpu(tmp_path):
 def test_cpp_shim_restates_reference_tests(tmp_path):
     """tests/test_multiply_sparse.cpp:45-78,84-136; tests/test_array.cpp:50-56,135-168 through
     spsparse_amd::multiply / VectorCooArray on the device."""
-    exe = _build_shim_test(tmp_path)
+    exe = build_cpp_test("shim", tmp_path)
     out = subprocess.run([exe], capture_output=True, text=True, timeout=600)
     print(out.stdout[-2000:], out.stderr[-2000:])
     assert out.returncode == 0 and out.stdout.strip().endswith("OK")

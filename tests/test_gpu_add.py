@@ -7,6 +7,7 @@ import pytest
 from oracle import binding as orc
 from spsparse_amd import workloads as wl
 from tests import add_ref as ar
+from tests.gpu_util import check_tuples as _check, coo as _coo, ctx, forced  # noqa: F401
 
 pytestmark = pytest.mark.gpu
 
@@ -14,53 +15,15 @@ PATHS = (0, 1)
 SCALES = (1.0, -0.75, 0.0, np.inf)
 
 
-@pytest.fixture(scope="module")
-def ctx():
-    from spsparse_amd import capi
-    c = capi.Context(0)
-    yield c
-    c.close()
-
-
-def _coo(X, shape, sort0=-1, device=False, keep=None):
-    """Coo struct of (idx0, idx1, val): host numpy arrays, or torch device copies (kept alive in `keep`)."""
-    from spsparse_amd import capi
-    if not device:
-        s, k = capi.host_coo(X[0], X[1], X[2], shape, sort0)
-        keep.append(k)
-        return s
-    import torch
-    t = [torch.from_numpy(np.ascontiguousarray(a)).cuda() for a in (np.asarray(X[0], np.int32), np.asarray(X[1], np.int32), np.asarray(X[2], np.float64))]
-    torch.cuda.synchronize()
-    keep.append(t)
-    return capi.device_coo(t[0].data_ptr(), t[1].data_ptr(), t[2].data_ptr(), len(X[2]), shape, sort0)
-
-
 def _add(ctx, A, B, path=0, **kw):
-    ctx.set_tuning("add_path", path)
-    try:
+    with forced(ctx, "add_path", path):
         return ctx.add(A, B, **kw)
-    finally:
-        ctx.set_tuning("add_path", 0)
 
 
 def _want(A, B, alpha=1.0, beta=1.0, tA='.', tB='.', pol=ar.ADD, zn=False):
     r, c, v = ar.scaled_cat(A, B, alpha, beta, tA, tB)
     i, j, w = orc.consolidate(r, c, v, 0, pol, zn)
     return i, j, w
-
-
-def _check(got, want, what):
-    if ar.same_tuples(got, want):
-        return
-    gi, gj, gv = got
-    wi, wj, wv = want
-    if gi.shape != wi.shape:
-        raise AssertionError("%s: %d tuples, want %d" % (what, gi.size, wi.size))
-    bad = np.flatnonzero((gi != wi) | (gj != wj) | (gv.view(np.int64) != wv.view(np.int64)))
-    k = bad[0]
-    raise AssertionError("%s: %d tuples differ, first at %d: (%d, %d, %r) vs (%d, %d, %r)" % (
-        what, bad.size, k, gi[k], gj[k], gv[k], wi[k], wj[k], wv[k]))
 
 
 def _case(rng, big=False):

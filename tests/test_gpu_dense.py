@@ -6,19 +6,12 @@ import numpy as np
 import pytest
 
 from tests import dense_ref as dr
+from tests.gpu_util import ctx  # noqa: F401
 
 pytestmark = pytest.mark.gpu
 
 NAN, INF = np.nan, np.inf
 PATHS = (0, 1, 2, 3)          # spmm_path: auto | serial | lanes | fold
-
-
-@pytest.fixture(scope="module")
-def ctx():
-    from spsparse_amd import capi
-    c = capi.Context(0)
-    yield c
-    c.close()
 
 
 def _sprinkle(rng, A, frac=0.03):
@@ -52,6 +45,7 @@ def _apply(ctx, i0, i1, v, shape, X, Y, t='.', pol=dr.ADD, hn=False, sort0=-1, p
         ctx.set_tuning("spmm_path", 0)
 
 
+# (its own: compares dense Y arrays entry by entry, not tuple sets as gpu_util.check_tuples does)
 def _check(got, i0, i1, v, X, Y, t, pol, hn, what="", want=None):
     if want is None:
         want = dr.apply_fast(i0, i1, v, X, Y, t, pol, hn)
@@ -60,6 +54,7 @@ def _check(got, i0, i1, v, X, Y, t, pol, hn, what="", want=None):
         raise AssertionError("%s: %d entries differ, first at %d: %r vs %r" % (what, bad.size, bad[0], got.reshape(-1)[bad[0]], want.reshape(-1)[bad[0]]))
 
 
+# (its own: test_gpu_sampled.py's maker of the same name draws a different random stream for the same seed)
 def _random_matrix(rng, nrow, ncol, nnz, storage):
     """Duplicates, explicit zeros, empty rows and columns; storage: 'raw', 'row' (sort0 0) or 'col' (sort0 1)."""
     rows = rng.choice(nrow, max(1, nrow * 2 // 3), replace=False)
@@ -132,6 +127,7 @@ def test_nrhs_and_leading_dimensions(ctx, nrhs):
                 assert dr.same_bits(out[:, nrhs:], Yw[:, nrhs:]), "padding after the nrhs values was written"
 
 
+# (its own: host only, returns capi.host_coo's (struct, keepalive) pair; gpu_util.coo appends to a keep list)
 def _coo(ctx, i0, i1, v, shape, sort0=-1):
     from spsparse_amd import capi
     return capi.host_coo(i0, i1, v, shape, sort0)

@@ -11,43 +11,12 @@ from oracle import binding as orc
 from spsparse_amd import workloads as wl
 from tests import add_ref as ar
 from tests import masked_ref as mr
+from tests.gpu_util import check_tuples, coo as _coo, ctx, forced  # noqa: F401
 
 pytestmark = pytest.mark.gpu
 
 PATHS = (0, 1, 2, 3)
 CS = (1.0, -0.75, np.inf)
-
-
-@pytest.fixture(scope="module")
-def ctx():
-    from spsparse_amd import capi
-    c = capi.Context(0)
-    yield c
-    c.close()
-
-
-def _dev(arrs, keep):
-    import torch
-    t = [torch.from_numpy(np.ascontiguousarray(a)).cuda() for a in arrs]
-    torch.cuda.synchronize()
-    keep.append(t)
-    return t
-
-
-def _coo(X, shape, sort0=-1, device=False, keep=None, no_val=False):
-    """Coo struct of (idx0, idx1, val): host numpy arrays or torch device copies (kept alive in `keep`); no_val: val NULL."""
-    from spsparse_amd import capi
-    arrs = [np.asarray(X[0], np.int32), np.asarray(X[1], np.int32), np.asarray(X[2], np.float64)]
-    if device:
-        t = _dev(arrs, keep)
-        p = [x.data_ptr() for x in t]
-        mem = capi.MEM_DEVICE
-    else:
-        arrs = [np.ascontiguousarray(a) for a in arrs]
-        keep.append(arrs)
-        p = [a.ctypes.data for a in arrs]
-        mem = capi.MEM_HOST
-    return capi.Coo(p[0], p[1], None if no_val else p[2], len(arrs[2]), int(shape[0]), int(shape[1]), sort0, mem)
 
 
 def _vec(s, dim, keep):
@@ -60,24 +29,17 @@ def _vec(s, dim, keep):
 
 
 def _masked(ctx, *args, path=0, **kw):
-    ctx.set_tuning("masked_path", path)
-    try:
+    with forced(ctx, "masked_path", path):
         return ctx.multiply_masked(*args, **kw)
-    finally:
-        ctx.set_tuning("masked_path", 0)
+
+
+def _nan_aware(gv, wv):
+    return (gv.view(np.int64) != wv.view(np.int64)) & ~(np.isnan(gv) & np.isnan(wv))
 
 
 def _check(got, want, what, payloads=False):
-    if mr.same_tuples(got, want, payloads):
-        return
-    gi, gj, gv = got
-    wi, wj, wv = want
-    if gi.shape != wi.shape:
-        raise AssertionError("%s: %d tuples, want %d" % (what, gi.size, wi.size))
-    bad = np.flatnonzero((gi != wi) | (gj != wj) | ((gv.view(np.int64) != wv.view(np.int64)) & ~(np.isnan(gv) & np.isnan(wv))))
-    k = bad[0]
-    raise AssertionError("%s: %d tuples differ, first at %d: (%d, %d, %r) vs (%d, %d, %r)" % (
-        what, bad.size, k, gi[k], gj[k], gv[k], wi[k], wj[k], wv[k]))
+    # its own: masked_ref.same_tuples (two NaNs agree unless payloads), and a mismatch mask that knows it
+    check_tuples(got, want, what, lambda g, w: mr.same_tuples(g, w, payloads), _nan_aware)
 
 
 def _operand(ctx, X, shape, form, t, role, pol, zn, keep, ops):

@@ -16,6 +16,7 @@ import pytest
 import projection as pj
 from oracle import binding as orc
 from spsparse_amd import workloads as wl
+from tests.gpu_util import device_operand as _device_operand
 
 pytestmark = pytest.mark.gpu
 
@@ -57,6 +58,7 @@ def _dev(ctx, A, B, **kw):
     return None, None, None, res
 
 
+# (its own: a relative bound or exact equality plus the (i, j) order, not the bit-for-bit gpu_util.check_tuples)
 def _check(got, want, exact=False, scale=None):
     gi, gj, gv = got[:3]
     wi, wj, wv = want[:3]
@@ -162,6 +164,7 @@ def test_mv_flags_scales(ctx):
         _dev_mv(ctx, orc.Mat([0], [1], [2.], (2, 3)), orc.Vec([0], [1.], 4))
 
 
+# (the two makers below stay here: test_gpu_stream.py's _rand_vec draws other numbers from the same seed)
 def _rand_mat(rng, shape, nnz, zeros=False, positive=True):
     i0 = rng.integers(0, shape[0], nnz)
     i1 = rng.integers(0, shape[1], nnz)
@@ -1263,17 +1266,6 @@ def test_device_resident_operands_rmat15(ctx):
 # BASELINE.json's full sizes: too large for a tuple-by-tuple oracle, checked through
 # size-independent properties (linearity: C 1 = A (B 1); closed-form sizes of the stencils;
 # agreement of the two sinks).
-
-def _device_operand(ctx, gen, n_tuples, shape, sort0=-1):
-    import torch
-    from spsparse_amd import capi
-    dev = torch.device("cuda:0")
-    t = (torch.empty(n_tuples, dtype=torch.int32, device=dev), torch.empty(n_tuples, dtype=torch.int32, device=dev),
-         torch.empty(n_tuples, dtype=torch.float64, device=dev))
-    gen(*[x.data_ptr() for x in t])
-    torch.cuda.synchronize()
-    return capi.device_coo(t[0].data_ptr(), t[1].data_ptr(), t[2].data_ptr(), n_tuples, shape, sort0), t
-
 
 def test_cfg2_rmat20_full_size_properties(ctx):
     """BASELINE cfg2: R-MAT scale-20 A*A (P = 2.09e10, nnz(C) = 9.7e9) -- every row sum and the

@@ -5,8 +5,6 @@ Coverage caveat.  A digest call with scalek = w leaves the kernels' `plain` emit
 for emit_value: the accumulation, the column arithmetic and the store are the same in both branches, but at these sizes
 the plain branch's values are covered only by the unweighted row sums (test_gpu_parity) and by the whole-COO checks here
 and in test_gpu_parity's R-MAT 18 tests, which apply the weights after the multiply."""
-import os
-import threading
 import time
 
 import numpy as np
@@ -14,6 +12,7 @@ import pytest
 
 import projection as pj
 from oracle import binding as orc
+from tests.gpu_util import PeakMemory as _PeakMemory, device_operand as _device_operand, threads as _threads
 
 pytestmark = pytest.mark.gpu
 
@@ -24,21 +23,6 @@ def ctx():
     c = capi.Context()
     yield c
     c.close()
-
-
-def _threads():
-    return max(1, min(orc.host_threads(), int(os.environ.get("OMP_NUM_THREADS") or 16)))
-
-
-def _device_operand(ctx, gen, n_tuples, shape, sort0=-1):
-    import torch
-    from spsparse_amd import capi
-    dev = torch.device("cuda:0")
-    t = (torch.empty(n_tuples, dtype=torch.int32, device=dev), torch.empty(n_tuples, dtype=torch.int32, device=dev),
-         torch.empty(n_tuples, dtype=torch.float64, device=dev))
-    gen(*[x.data_ptr() for x in t])
-    torch.cuda.synchronize()
-    return capi.device_coo(t[0].data_ptr(), t[1].data_ptr(), t[2].data_ptr(), n_tuples, shape, sort0), t
 
 
 def _host(keep, shape):
@@ -86,27 +70,6 @@ def test_cfg2_rmat20_digest_weighted_rows(ctx):
         _report("cfg2 C=%g rows (A A w)" % C_, ctx.to_host(d.row_sum, n, np.float64), ref.rows(w))
     print("wall %.1f s" % (time.time() - t0))
     del keep
-
-
-class _PeakMemory:
-    """Device memory in use (hipMemGetInfo, the whole device), sampled every millisecond on a thread."""
-
-    def __enter__(self):
-        import torch
-        self.peak, self.stop = 0, False
-
-        def poll():
-            while not self.stop:
-                free, total = torch.cuda.mem_get_info(0)
-                self.peak = max(self.peak, total - free)
-                time.sleep(0.001)
-        self.t = threading.Thread(target=poll, daemon=True)
-        self.t.start()
-        return self
-
-    def __exit__(self, *exc):
-        self.stop = True
-        self.t.join()
 
 
 def test_cfg2_coo_sink_whole():

@@ -8,6 +8,7 @@ import pytest
 
 from tests import dense_ref as dr
 from tests import sampled_ref as sr
+from tests.gpu_util import ctx  # noqa: F401
 
 pytestmark = pytest.mark.gpu
 
@@ -16,14 +17,6 @@ PATHS = (0, 1, 2)             # sampled_path: auto | lane | slab
 KS = (0, 1, 2, 3, 7, 8, 15, 16, 17, 64, 65, 256, 1000)
 SCALES = ((1.0, 0.0), (-1.0, 0.0), (0.0, 1.0), (2.5, -1.0), (NAN, 0.0), (1.0, NAN))
 EINVAL = -2
-
-
-@pytest.fixture(scope="module")
-def ctx():
-    from spsparse_amd import capi
-    c = capi.Context(0)
-    yield c
-    c.close()
 
 
 def nan_with(payload):
@@ -45,6 +38,7 @@ def _sprinkle(rng, A, frac=0.02):
     flat[(u >= 2 * frac) & (u < 3 * frac)] = -INF
 
 
+# (its own: compares the out[] value arrays, not tuple sets as gpu_util.check_tuples does)
 def _check(got, want, what):
     got, want = np.asarray(got), np.asarray(want)
     if not dr.same_bits(got, want):
@@ -53,6 +47,7 @@ def _check(got, want, what):
             what, bad.size, want.size, bad[0], got.reshape(-1)[bad[0]], want.reshape(-1)[bad[0]]))
 
 
+# (its own: test_gpu_dense.py's maker of the same name draws a different random stream for the same seed)
 def _random_matrix(rng, nrow, ncol, nnz, storage):
     """Duplicates and explicit zeros; storage: 'raw', 'row' (sort0 0) or 'col' (sort0 1)."""
     i0 = rng.integers(0, nrow, nnz).astype(np.int32)

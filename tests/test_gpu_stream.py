@@ -3,7 +3,6 @@ bit under SINK_ORDERED, to the same rules otherwise), the partition is the numpy
 before the first chunk, chained and prepared operands work, and the block outputs stay within two budgets."""
 import os
 import subprocess
-import threading
 import time
 
 import numpy as np
@@ -14,18 +13,11 @@ import projection as pj
 from oracle import binding as orc
 from spsparse_amd import workloads as wl
 from tests import stream_ref as sr
+from tests.gpu_util import PeakMemory as _PeakMemory, build_cpp_test, ctx, threads as _threads  # noqa: F401
 
 pytestmark = pytest.mark.gpu
 
 UNLIMITED = 1 << 62
-
-
-@pytest.fixture(scope="module")
-def ctx():
-    from spsparse_amd import capi
-    c = capi.Context(0)
-    yield c
-    c.close()
 
 
 class Keep:
@@ -111,6 +103,7 @@ def _nan_mat(rng, shape, nnz, nan):
     return (i0.astype(np.int32), i1.astype(np.int32), v, shape)
 
 
+# (its own: test_gpu_parity.py's _rand_vec zeroes an entry and returns an orc.Vec)
 def _rand_vec(rng, n):
     idx = np.flatnonzero(rng.uniform(size=n) < 0.7)
     if idx.size == 0:
@@ -335,30 +328,6 @@ def test_column_block_products_are_refused_before_delivery(ctx):
     assert _bits_equal(got, want) and st.blocks >= 2
 
 
-class _PeakMemory:
-    """Device memory in use (hipMemGetInfo, the whole device), sampled every millisecond on a thread."""
-
-    def __enter__(self):
-        import torch
-        self.base = 0
-        free, total = torch.cuda.mem_get_info(0)
-        self.base = self.peak = total - free
-        self.total, self.stop = total, False
-
-        def poll():
-            while not self.stop:
-                free, total = torch.cuda.mem_get_info(0)
-                self.peak = max(self.peak, total - free)
-                time.sleep(0.001)
-        self.t = threading.Thread(target=poll, daemon=True)
-        self.t.start()
-        return self
-
-    def __exit__(self, *exc):
-        self.stop = True
-        self.t.join()
-
-
 def test_block_outputs_stay_within_two_budgets():
     """R-MAT 18 at a budget of 2^22: device memory sampled during the call grows by the two block output sets, the
     workspace and op(B)'s structures -- far less than the 16 B per tuple the plain path's output set takes."""
@@ -396,21 +365,8 @@ def test_block_outputs_stay_within_two_budgets():
 
 # ---- full size: the C++ consumer of tests/cpp/test_stream.cpp through the template with stream_block_tuples
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-
-
-def _threads():
-    return max(1, min(orc.host_threads(), int(os.environ.get("OMP_NUM_THREADS") or 16)))
-
-
 def _consumer(tmp_path):
-    from spsparse_amd import build
-    libdir = os.path.dirname(build.build())
-    exe = os.path.join(str(tmp_path), "test_stream_o2")
-    subprocess.check_call(["g++", "-std=c++17", "-O2", "-Wall", "-I" + os.path.join(ROOT, "include"),
-                           os.path.join(ROOT, "tests", "cpp", "test_stream.cpp"), "-o", exe, "-L" + libdir,
-                           "-lspsparse_amd", "-Wl,-rpath," + libdir, "-Wl,-rpath,/opt/rocm/lib"])
-    return exe
+    return build_cpp_test("stream", tmp_path, "-O2")
 
 
 def _write_square(path, a, n):
