@@ -216,6 +216,10 @@ const char *spsamd_version(void);
  *                                     wherever that kernel can hold the row; a row too long for the forced class falls to the
  *                                     next one (default: in order where J ascends and S is column-ordered, else by row
  *                                     length)
+ *   reduce_path     1 | 2             reduce: every row through the short rows' kernel (a wave per 64 consecutive rows, their
+ *                                     tuples staged packed through LDS; correct for any length) | the long rows' kernel (a
+ *                                     wave per 64 listed rows, a padded LDS tile of 32 values per row and step) (default:
+ *                                     rows of at most 64 tuples short, the others long)
  * The environment variables of the same purpose (SPSAMD_W ...) are read once, inside spsamd_ctx_create; nothing reads
  * the environment later.  Unknown names: SPSAMD_EINVAL. */
 int spsamd_ctx_set_tuning(spsamd_ctx *ctx, const char *name, long value);
@@ -464,6 +468,65 @@ int spsamd_extract(spsamd_ctx *ctx, const spsamd_coo *A, char transpose,
 	int index_mem,                          /* SPSAMD_MEM_HOST or SPSAMD_MEM_DEVICE, for rows and cols together */
 	int duplicate_policy, int zero_nan,
 	int sink_kind, int sink_flags, spsamd_result *result);
+
+/*
+ * v = post(reduce(op(A)))  -- a matrix reduced to a vector along its rows (GraphBLAS GrB_reduce to a vector; column
+ * reductions are transpose = 'T'): row sums, 1- and 2-norms, the largest magnitude, the tuple count and the diagonal, with an
+ * optional reciprocal / square root, straight into caller-owned memory -- device memory included, so that a chained product
+ * is scaled (spsamd_multiply's scalei / scalej / scalek with mem = SPSAMD_MEM_DEVICE) without a trip to the host.
+ *   - Operand.  op(A) is taken exactly as spsamd_select takes it (above), with duplicate_policy and zero_nan: a raw operand
+ *     is consolidated by op()'s rows; an operand whose sort0 names op()'s row order is trusted as stored (duplicates, zeros
+ *     and the order inside a row included) and rejected (SPSAMD_EINVAL) if its leading index descends; a SINK_COO result of
+ *     this context and a prepared handle of the same transpose are read in place.  Host and device operands.  Call the
+ *     resulting sequence S.
+ *   - Rows.  The contributing tuples of row i are all its tuples in S -- for SPSAMD_REDUCE_DIAG only those with column i.  A
+ *     row appears in the result if and only if it has at least one contributing tuple.
+ *   - Value.  r_i is the fold written beside each constant below over the contributing tuples IN S's ORDER, serially: every
+ *     add and multiply is rounded on its own (no FMA, no tree or split sum), and a NaN result has the bits x86-64 gives it
+ *     (the left operand's NaN, quieted, else the right one's, else 0xFFF8000000000000; the accumulator is the left operand),
+ *     as in spsamd_multiply_dense.  MAX_ABS is the largest |v| over the non-NaN tuples, compared through mag like
+ *     spsamd_select does, +0.0 when there is none: bit for bit the m_i of SPSAMD_SELECT_ROW_REL.  COUNT is exact (a row
+ *     holds fewer than 2^31 tuples).  The emitted value is post(r_i): RECIP = 1.0 / r and SQRT = sqrt(r) are the correctly
+ *     rounded IEEE operations, RSQRT is SQRT followed by RECIP (two roundings); a NaN result has x86's bits (1.0 / NaN and
+ *     sqrt(NaN): the operand quieted; sqrt(r < 0): 0xFFF8000000000000; sqrt(-0.0) = -0.0).
+ *   - No entry is dropped for its value: zeros, infinities and NaNs are emitted.  NOTE for scale vectors: spsamd_multiply
+ *     treats a zero scale entry like a missing one (isnone, multiply_sparse.hpp:195,211) and skips that row, column or k.
+ *   - Output, caller-owned; mem says where out_idx and out_val live (SPSAMD_MEM_HOST or SPSAMD_MEM_DEVICE).
+ *       sparse form (out_idx != NULL): the entries (i, post(r_i)), i strictly ascending -- a valid spsamd_vec of shape0 =
+ *         rows(op(A)), ready to be a scale vector.  *out_nnz gets their number.  capacity < that number: nothing is written,
+ *         *out_nnz gets the number needed and the call returns SPSAMD_ECAPACITY (capacity = 0 is the size query).
+ *       dense form (out_idx == NULL): out_val[i] for every row of op(A) -- what spsamd_multiply_dense and
+ *         spsamd_multiply_sampled consume; rows without a contributing tuple get +0.0 (no post-operation applied to them).
+ *         *out_nnz is still the number of rows with one.  capacity < rows(op(A)): SPSAMD_ECAPACITY, nothing written,
+ *         *out_nnz = rows(op(A)).
+ *     Neither output set of the context is written: a SINK_COO result may be A and stays valid and fetchable.
+ *   - result (may be NULL): shape0 = rows(op(A)), shape1 = 0, nnz = the count, nnz_a = |S|, ms_consolidate, ms_numeric,
+ *     ms_total, workspace_bytes; rows_light / rows_heavy and tuples_light / tuples_heavy: the non-empty rows of S, and their
+ *     tuples, by the kernel that served them (the short rows' and the long rows' kernel; all 0 for COUNT, which reads the row
+ *     pointer only).  Everything else 0 / NULL.  `Nothing written` below and above means the output
+ *     buffers: on SPSAMD_ECAPACITY result is zeroed with shape0 set, and the sparse form has filled nnz_a too (its count
+ *     is known only after the intake; the dense form is refused before it).  On another error result is unspecified.
+ * SPSAMD_EINVAL, with a message and nothing written: A, out_val or out_nnz NULL; an unknown op or post; a policy outside
+ * 0..2; a bad mem; an index of A out of bounds; a false sort0; 2^31 or more tuples; out_idx / out_val overlapping each
+ * other or A's arrays, or, for device buffers, lying in either output set of the context.  An empty S: 0 with count 0 (the
+ * dense form is then filled with +0.0).  Returns when the output is complete.
+ */
+#define SPSAMD_REDUCE_SUM      1   /* acc = +0.0;  acc = acc + v                       */
+#define SPSAMD_REDUCE_SUM_ABS  2   /* acc = +0.0;  acc = acc + |v|   (sign bit cleared) */
+#define SPSAMD_REDUCE_SUM_SQ   3   /* acc = +0.0;  acc = acc + v * v (two roundings)    */
+#define SPSAMD_REDUCE_MAX_ABS  4   /* spsamd_select ROW_REL's m_i                       */
+#define SPSAMD_REDUCE_COUNT    5   /* the number of tuples, as a double                 */
+#define SPSAMD_REDUCE_DIAG     6   /* SUM over the row's tuples with col == row only    */
+
+#define SPSAMD_POST_NONE   0
+#define SPSAMD_POST_RECIP  1       /* 1.0 / r            */
+#define SPSAMD_POST_SQRT   2       /* sqrt(r)            */
+#define SPSAMD_POST_RSQRT  3       /* 1.0 / sqrt(r): two rounded operations */
+
+int spsamd_reduce(spsamd_ctx *ctx, const spsamd_coo *A, char transpose,
+	int op, int post, int duplicate_policy, int zero_nan,
+	int32_t *out_idx, double *out_val, size_t capacity, int mem,
+	size_t *out_nnz, spsamd_result *result /* may be NULL */);
 
 /*
  * ret = (C * diag(scalei) * op(A) * diag(scalej) * op(B) * diag(scalek)) restricted to the keys of M  -- a masked product

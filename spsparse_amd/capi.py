@@ -27,6 +27,10 @@ SELECT_COMPLEMENT = 1
 select_light_max, select_mid_max = 64, 4096
 # extract: the longest output row of the light and of the mid ordering kernel class
 extract_light_max, extract_mid_max = 64, 4096
+REDUCE_SUM, REDUCE_SUM_ABS, REDUCE_SUM_SQ, REDUCE_MAX_ABS, REDUCE_COUNT, REDUCE_DIAG = 1, 2, 3, 4, 5, 6
+POST_NONE, POST_RECIP, POST_SQRT, POST_RSQRT = 0, 1, 2, 3
+# reduce: the longest row of the short rows' kernel class, and the values per row and step of the long rows' LDS tile
+reduce_light_max, reduce_chunk = 64, 32
 
 ERRORS = {-1: "EDIM", -2: "EINVAL", -3: "EHIP", -4: "ENOMEM", -5: "ECAPACITY", -6: "ENODEVICE", -7: "EPEER"}
 
@@ -90,7 +94,7 @@ SYMBOLS = ["spsamd_ctx_create", "spsamd_ctx_destroy", "spsamd_last_error", "spsa
            "spsamd_dist_unique_id", "spsamd_dist_create", "spsamd_dist_destroy", "spsamd_dist_multiply",
            "spsamd_operand_prepare", "spsamd_operand_as_coo", "spsamd_operand_bytes", "spsamd_operand_destroy",
            "spsamd_multiply_dense", "spsamd_add", "spsamd_multiply_stream", "spsamd_multiply_masked",
-           "spsamd_multiply_sampled", "spsamd_select", "spsamd_extract"]
+           "spsamd_multiply_sampled", "spsamd_select", "spsamd_extract", "spsamd_reduce"]
 
 _lib = None
 
@@ -143,6 +147,8 @@ def load():
                                 C.c_int, C.c_int, P(Result)]
     L.spsamd_extract.argtypes = [C.c_void_p, P(Coo), C.c_char, C.c_void_p, C.c_size_t, C.c_void_p, C.c_size_t, C.c_int,
                                  C.c_int, C.c_int, C.c_int, C.c_int, P(Result)]
+    L.spsamd_reduce.argtypes = [C.c_void_p, P(Coo), C.c_char, C.c_int, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_void_p,
+                                C.c_size_t, C.c_int, P(C.c_size_t), P(Result)]
     L.spsamd_memcpy.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_size_t]
     L.spsamd_consolidate.argtypes = [C.c_void_p, P(Coo), C.c_int, C.c_int, C.c_int, P(Result)]
     L.spsamd_sorted_permutation.argtypes = [C.c_void_p, P(Coo), C.c_int, C.c_void_p]
@@ -192,6 +198,12 @@ def host_vec(idx, val, shape0, sort0=-1):
     a = np.ascontiguousarray(idx, dtype=np.int32)
     v = np.ascontiguousarray(val, dtype=np.float64)
     return Vec(a.ctypes.data, v.ctypes.data, v.size, int(shape0), sort0, MEM_HOST), (a, v)
+
+
+def device_vec(ptr_idx, ptr_val, nnz, shape0, sort0=-1):
+    """Vec struct over device memory (e.g. the sparse form of Context.reduce written into torch tensors): a scale vector
+    or MV right-hand side that never leaves the device."""
+    return Vec(ptr_idx, ptr_val, int(nnz), int(shape0), sort0, MEM_DEVICE)
 
 
 class Context:
@@ -326,6 +338,47 @@ class Context:
         del args
         self._check(rc)
         return res
+
+    def reduce(self, A, op, post=POST_NONE, transpose='.', duplicate_policy=ADD, zero_nan=False, dense=False, out=None,
+               result=None):
+        """spsamd_reduce: post(fold of every row of op(A)) -- REDUCE_* and POST_* -- bit for bit the serial loop over the
+        row's tuples in op(A)'s order.  A: a Coo struct.  Without out: returns numpy arrays, (idx, val) of the rows that
+        have a contributing tuple, or with dense=True val alone, one entry per row of op(A) (+0.0 where none contributes).
+        With out: torch tensors on this context's device that receive the result -- (idx int32, val float64) for the sparse
+        form, the float64 val alone (or (None, val)) for the dense form -- and the count is returned; a sparse out that is
+        too small raises SpsamdError with code -5.  result: a capi.Result to fill (timings, rows by kernel class)."""
+        nrow = int(A.shape1 if transpose == 'T' else A.shape0)
+        cnt = C.c_size_t(0)
+        rp = None if result is None else C.byref(result)
+
+        def call(pi, pv, cap, mem):
+            return self.L.spsamd_reduce(self.h, C.byref(A), transpose.encode(), int(op), int(post), duplicate_policy,
+                                        int(zero_nan), pi, pv, cap, mem, C.byref(cnt), rp)
+
+        if out is not None:
+            oi, ov = out if isinstance(out, (tuple, list)) else (None, out)
+            if dense and oi is not None:
+                raise ValueError("the dense form takes the value tensor alone")
+            pv, _ld, _n, mv = _dense_arg(ov, "out val", writable=True)
+            if mv != MEM_DEVICE or ov.ndim != 1 or not ov.is_contiguous():
+                raise ValueError("out val must be a contiguous 1-D float64 device tensor")
+            cap, pi = int(ov.shape[0]), None
+            if oi is not None:
+                pi, ni, mi, _k = _index_list(oi, "out idx")
+                if mi != MEM_DEVICE and ni:
+                    raise ValueError("out idx must be a device tensor")
+                cap = min(cap, ni)
+                pi = oi.data_ptr()
+            self._check(call(pi, pv, cap, MEM_DEVICE))
+            return int(cnt.value)
+        if dense:
+            val = np.empty(nrow, np.float64)
+            self._check(call(None, val.ctypes.data, nrow, MEM_HOST))
+            return val
+        cap = min(nrow, int(A.nnz)) if A.mem != MEM_PREPARED else nrow
+        idx, val = np.empty(max(cap, 1), np.int32), np.empty(max(cap, 1), np.float64)
+        self._check(call(idx.ctypes.data, val.ctypes.data, cap, MEM_HOST))
+        return idx[:cnt.value].copy(), val[:cnt.value].copy()
 
     def consolidate(self, A, so0, duplicate_policy=ADD, zero_nan=False):
         res = Result()

@@ -93,6 +93,7 @@ struct Tuning {
 	int sampled_path = 0;        // multiply_sampled: 0 auto | 1 lane kernel for every tuple | 2 slab kernel for every tuple (auto: by k and a probe of M's order)
 	int select_path = 0;         // select, ROW_TOPK: 0 by row length | 1 light | 2 mid | 3 heavy kernel for every row it can hold
 	int extract_path = 0;        // extract: 0 auto | 1 every row through the permuted path | 2 light | 3 mid | 4 heavy ordering kernel for every row it can hold
+	int reduce_path = 0;         // reduce: 0 by row length | 1 every row through the short rows' kernel | 2 every row through the long rows' kernel
 #ifdef SPSAMD_ABLATIONS
 	int dbg = 0;
 #endif
@@ -433,6 +434,13 @@ void select_tuples(spsamd_ctx *c, const spsamd_coo *A, char transpose, int predi
 // op(A)(I, J) into the sink: spsamd_extract after its null checks (rows / cols null: every index of that dimension)
 void extract_tuples(spsamd_ctx *c, const spsamd_coo *A, char transpose, const int32_t *rows, size_t nrows, const int32_t *cols,
 	size_t ncols, int index_mem, int duplicate_policy, int zero_nan, int sink_kind, int sink_flags, spsamd_result *res);
+
+// ---------------------------------------------------------------- reduction to a vector (k_reduce.hip)
+
+// post(fold of op(A)'s rows) into the caller's buffers: spsamd_reduce after its null checks.  Returns SPSAMD_OK, or
+// SPSAMD_ECAPACITY with *out_nnz = the entries needed and the context's last error set (nothing written).
+int reduce_rows(spsamd_ctx *c, const spsamd_coo *A, char transpose, int op, int post, int duplicate_policy, int zero_nan,
+	int32_t *out_idx, double *out_val, size_t capacity, int mem, size_t *out_nnz, spsamd_result *res);
 
 // The same operand struct twice (A * A): one consolidation can serve both sides (capi.hip).
 bool same_operand(const spsamd_coo *a, const spsamd_coo *b);
