@@ -220,6 +220,10 @@ const char *spsamd_version(void);
  *                                     tuples staged packed through LDS; correct for any length) | the long rows' kernel (a
  *                                     wave per 64 listed rows, a padded LDS tile of 32 values per row and step) (default:
  *                                     rows of at most 64 tuples short, the others long)
+ *   emult_path      1 | 2 | 3         emult: 1 the merge of the two key streams | 2 every tuple of op(A) looks its key up in op(B)
+ *                                     (inside the row where B is a prepared handle, else over the whole stream) | 3 every key of
+ *                                     op(B) looks up its run in op(A) (default: the cheapest by a byte model, DESIGN.md
+ *                                     section 17)
  * The environment variables of the same purpose (SPSAMD_W ...) are read once, inside spsamd_ctx_create; nothing reads
  * the environment later.  Unknown names: SPSAMD_EINVAL. */
 int spsamd_ctx_set_tuning(spsamd_ctx *ctx, const char *name, long value);
@@ -527,6 +531,53 @@ int spsamd_reduce(spsamd_ctx *ctx, const spsamd_coo *A, char transpose,
 	int op, int post, int duplicate_policy, int zero_nan,
 	int32_t *out_idx, double *out_val, size_t capacity, int mem,
 	size_t *out_nnz, spsamd_result *result /* may be NULL */);
+
+/*
+ * ret = op(A) o op(B) over the intersection of the two patterns, or op(A) restricted to / taken off op(B)'s pattern  --
+ * GraphBLAS GrB_eWiseMult and its structural relatives: the strength of connection A o A^T, a Galerkin product kept on a
+ * prescribed stencil, a frontier minus the visited set.
+ *   - Operand A.  op(A) is taken exactly as spsamd_select takes it (above), with duplicate_policy and zero_nan: a raw operand
+ *     is consolidated by op()'s rows; an operand whose sort0 names op()'s row order is trusted as stored; a SINK_COO result
+ *     of this context and a prepared handle of the same transpose are read in place.  Call the resulting sequence S_A.
+ *   - Trusted operands must ascend.  An operand trusted as stored must be non-descending in its full (row, col) key of op()
+ *     (equal keys allowed); otherwise SPSAMD_EINVAL, the rule of spsamd_add.  A SINK_COO result of this context handed back
+ *     in is NOT inspected (as in spsamd_add): a product, sum or consolidation ascends by construction, but a select, extract
+ *     or emult result is a subsequence of its own operand, so one made from a trusted operand whose columns descend inside
+ *     a row must not be chained into this call or spsamd_add -- its matches would be missed silently (never out of bounds).
+ *   - Operand B under TIMES is taken like A, giving S_B.  The partner of a tuple of S_A with key (i, j) is the FIRST tuple of
+ *     S_B with that key.
+ *   - Operand B under FIRST (with or without COMPLEMENT) is structural, exactly like M in spsamd_multiply_masked: B->val is
+ *     never read and may be NULL, duplicate keys count once, explicit zeros count, a false sort0 is rejected.
+ *   - Result.  For every tuple (i, j, a) of S_A at position p whose key is a key of B (under COMPLEMENT: is NOT a key of B)
+ *     the result holds one tuple, and no other; the order is (i, j, p) ascending, so the result is a subsequence of S_A.
+ *       TIMES   v = (alpha * a) * b: two rounded multiplies, left to right, a NaN result with the bits x86-64 gives it (the
+ *               left operand's NaN, quieted, else the right one's, else 0xFFF8000000000000), as in spsamd_add.  alpha is
+ *               applied even when it is 1 or 0.
+ *       FIRST   v = a, bits untouched (NaN payloads, signalling NaNs, -0.0); alpha is not read.
+ *     Nothing is dropped by value: a product that is 0.0 or NaN is emitted; the pattern depends on keys only.  For any
+ *     input, FIRST and FIRST | COMPLEMENT partition S_A.
+ * op(A) and op(B) must have equal shape (SPSAMD_EDIM); the result has that shape.  Sinks as for spsamd_select: SINK_COO
+ * (fetchable, usable with spsamd_result_scatter_dense, chainable as a MEM_DEVICE sort0 = 0 operand -- sort0 = 1 with
+ * SINK_PERMUTE), SINK_DIGEST (+ ROWSTATS); SINK_ORDERED and SINK_EXACT_PATTERN are accepted and change nothing.  An operand
+ * may live in the context's current output set: the result goes to the other set.  The same struct on both sides with equal
+ * transposes is legal (A o A).
+ * result: shape, nnz, nnz_a (= |S_A|), nnz_b (|S_B|; B's unique keys when B is structural), products (the probe tuples
+ * searched: 0 when the merge path ran, see the emult_path knob), ms_consolidate, ms_numeric, ms_total, workspace_bytes.
+ * Everything else 0 / NULL.
+ * SPSAMD_EINVAL, with a message and nothing written: A, B or result NULL; an unknown op or flag; COMPLEMENT with TIMES; a
+ * policy outside 0..2; an unknown sink; an index out of bounds; 2^31 or more tuples in either operand; a NULL val where it
+ * is read; both output sets of the context being operands of the call.  An empty A: an empty result (B is still checked).  An
+ * empty B: an empty result, under COMPLEMENT S_A.  Returns when the result is complete.
+ */
+#define SPSAMD_EMULT_TIMES 1  /* v = (alpha * a) * b: two rounded multiplies, left to right, x86 NaN bits (ref_mul of x86fp.h) */
+#define SPSAMD_EMULT_FIRST 2  /* v = a, bits untouched; B is structural */
+#define SPSAMD_EMULT_COMPLEMENT 1  /* emult_flags, FIRST only: keep the tuples of op(A) whose key is NOT a key of op(B) */
+
+int spsamd_emult(spsamd_ctx *ctx, int op, int emult_flags,
+	double alpha, const spsamd_coo *A, char transpose_A,
+	const spsamd_coo *B, char transpose_B,
+	int duplicate_policy, int zero_nan,
+	int sink_kind, int sink_flags, spsamd_result *result);
 
 /*
  * ret = (C * diag(scalei) * op(A) * diag(scalej) * op(B) * diag(scalek)) restricted to the keys of M  -- a masked product

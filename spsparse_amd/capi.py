@@ -31,6 +31,10 @@ REDUCE_SUM, REDUCE_SUM_ABS, REDUCE_SUM_SQ, REDUCE_MAX_ABS, REDUCE_COUNT, REDUCE_
 POST_NONE, POST_RECIP, POST_SQRT, POST_RSQRT = 0, 1, 2, 3
 # reduce: the longest row of the short rows' kernel class, and the values per row and step of the long rows' LDS tile
 reduce_light_max, reduce_chunk = 64, 32
+EMULT_TIMES, EMULT_FIRST = 1, 2
+EMULT_COMPLEMENT = 1
+# emult: the merged items per tile of the merge path, and the tuples per wave of the probe and compact kernels
+emult_tile, emult_unit = 2048, 512
 
 ERRORS = {-1: "EDIM", -2: "EINVAL", -3: "EHIP", -4: "ENOMEM", -5: "ECAPACITY", -6: "ENODEVICE", -7: "EPEER"}
 
@@ -94,7 +98,7 @@ SYMBOLS = ["spsamd_ctx_create", "spsamd_ctx_destroy", "spsamd_last_error", "spsa
            "spsamd_dist_unique_id", "spsamd_dist_create", "spsamd_dist_destroy", "spsamd_dist_multiply",
            "spsamd_operand_prepare", "spsamd_operand_as_coo", "spsamd_operand_bytes", "spsamd_operand_destroy",
            "spsamd_multiply_dense", "spsamd_add", "spsamd_multiply_stream", "spsamd_multiply_masked",
-           "spsamd_multiply_sampled", "spsamd_select", "spsamd_extract", "spsamd_reduce"]
+           "spsamd_multiply_sampled", "spsamd_select", "spsamd_extract", "spsamd_reduce", "spsamd_emult"]
 
 _lib = None
 
@@ -149,6 +153,8 @@ def load():
                                  C.c_int, C.c_int, C.c_int, C.c_int, P(Result)]
     L.spsamd_reduce.argtypes = [C.c_void_p, P(Coo), C.c_char, C.c_int, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_void_p,
                                 C.c_size_t, C.c_int, P(C.c_size_t), P(Result)]
+    L.spsamd_emult.argtypes = [C.c_void_p, C.c_int, C.c_int, C.c_double, P(Coo), C.c_char, P(Coo), C.c_char,
+                               C.c_int, C.c_int, C.c_int, C.c_int, P(Result)]
     L.spsamd_memcpy.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_size_t]
     L.spsamd_consolidate.argtypes = [C.c_void_p, P(Coo), C.c_int, C.c_int, C.c_int, P(Result)]
     L.spsamd_sorted_permutation.argtypes = [C.c_void_p, P(Coo), C.c_int, C.c_void_p]
@@ -321,6 +327,17 @@ class Context:
         rc = self.L.spsamd_select(self.h, C.byref(A), transpose.encode(), int(predicate), int(iparam), float(dparam),
                                   SELECT_COMPLEMENT if complement else 0, duplicate_policy, int(zero_nan), sink, flags,
                                   C.byref(res))
+        self._check(rc)
+        return res
+
+    def emult(self, op, A, B, tA='.', tB='.', alpha=1.0, complement=False, duplicate_policy=ADD, zero_nan=False,
+              sink=SINK_COO, flags=0):
+        """spsamd_emult: the tuples of op(A) whose key is a key of op(B) (complement: is not), in op(A)'s order.  op:
+        EMULT_TIMES -- the value is (alpha * a) * b with b the first tuple of op(B) of that key -- or EMULT_FIRST -- a's own
+        bits, B's values never read (B.val may be None).  complement goes with EMULT_FIRST only.  A, B: Coo structs."""
+        res = Result()
+        rc = self.L.spsamd_emult(self.h, int(op), EMULT_COMPLEMENT if complement else 0, float(alpha), C.byref(A), tA.encode(),
+                                 C.byref(B), tB.encode(), duplicate_policy, int(zero_nan), sink, flags, C.byref(res))
         self._check(rc)
         return res
 

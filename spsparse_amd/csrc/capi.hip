@@ -50,8 +50,8 @@ extern "C" int spsamd_ctx_create(spsamd_ctx **out, int device, void *hip_stream)
 	if (hipStreamCreateWithFlags(&c->side2, hipStreamNonBlocking) != hipSuccess) { spsamd_ctx_destroy(c); return SPSAMD_EHIP; }
 	for (auto &e : c->ev_side2) if (hipEventCreateWithFlags(&e, hipEventDisableTiming) != hipSuccess) { spsamd_ctx_destroy(c); return SPSAMD_EHIP; }
 	// developer knobs: the environment is consulted here and nowhere else
-	static const char *const knobs[] = {"window", "cell_cap", "dense_min", "no_tiles", "xcd", "emit_path", "light_path", "no_wmajor", "direct_min", "tiles_v1", "long_cap", "long_dense_min", "index_budget_mb", "trace", "light_two_pass", "spmm_path", "spmm_long_min", "add_path", "masked_path", "sampled_path", "select_path", "extract_path", "reduce_path"};
-	static const char *const envs[] = {"SPSAMD_W", "SPSAMD_CELL_CAP", "SPSAMD_DENSE_MIN", "SPSAMD_NO_TILES", "SPSAMD_XCD", "SPSAMD_EMIT_PATH", "SPSAMD_LIGHT_PATH", "SPSAMD_NO_WMAJOR", "SPSAMD_DIRECT_MIN", "SPSAMD_TILES_V1", "SPSAMD_LONG_CAP", "SPSAMD_LONG_DENSE_MIN", "SPSAMD_INDEX_BUDGET_MB", "SPSAMD_TRACE", "SPSAMD_LIGHT_TWO_PASS", "SPSAMD_SPMM_PATH", "SPSAMD_SPMM_LONG_MIN", "SPSAMD_ADD_PATH", "SPSAMD_MASKED_PATH", "SPSAMD_SAMPLED_PATH", "SPSAMD_SELECT_PATH", "SPSAMD_EXTRACT_PATH", "SPSAMD_REDUCE_PATH"};
+	static const char *const knobs[] = {"window", "cell_cap", "dense_min", "no_tiles", "xcd", "emit_path", "light_path", "no_wmajor", "direct_min", "tiles_v1", "long_cap", "long_dense_min", "index_budget_mb", "trace", "light_two_pass", "spmm_path", "spmm_long_min", "add_path", "masked_path", "sampled_path", "select_path", "extract_path", "reduce_path", "emult_path"};
+	static const char *const envs[] = {"SPSAMD_W", "SPSAMD_CELL_CAP", "SPSAMD_DENSE_MIN", "SPSAMD_NO_TILES", "SPSAMD_XCD", "SPSAMD_EMIT_PATH", "SPSAMD_LIGHT_PATH", "SPSAMD_NO_WMAJOR", "SPSAMD_DIRECT_MIN", "SPSAMD_TILES_V1", "SPSAMD_LONG_CAP", "SPSAMD_LONG_DENSE_MIN", "SPSAMD_INDEX_BUDGET_MB", "SPSAMD_TRACE", "SPSAMD_LIGHT_TWO_PASS", "SPSAMD_SPMM_PATH", "SPSAMD_SPMM_LONG_MIN", "SPSAMD_ADD_PATH", "SPSAMD_MASKED_PATH", "SPSAMD_SAMPLED_PATH", "SPSAMD_SELECT_PATH", "SPSAMD_EXTRACT_PATH", "SPSAMD_REDUCE_PATH", "SPSAMD_EMULT_PATH"};
 	static_assert(sizeof knobs / sizeof knobs[0] == sizeof envs / sizeof envs[0], "one environment variable per knob");
 	for (size_t k = 0; k < sizeof knobs / sizeof knobs[0]; ++k)
 		if (const char *e = getenv(envs[k])) (void)spsamd_ctx_set_tuning(c, knobs[k], atol(e));
@@ -72,7 +72,7 @@ extern "C" int spsamd_ctx_set_tuning(spsamd_ctx *c, const char *name, long value
 		{"light_path", &c->tune.light_path}, {"no_wmajor", &c->tune.no_wmajor}, {"direct_min", &c->tune.direct_min}, {"tiles_v1", &c->tune.tiles_v1}, {"long_cap", &c->tune.long_cap}, {"long_dense_min", &c->tune.long_dense_min}, {"index_budget_mb", &c->tune.index_budget_mb}, {"trace", &c->tune.trace}, {"light_two_pass", &c->tune.light_two_pass},
 		{"spmm_path", &c->tune.spmm_path}, {"spmm_long_min", &c->tune.spmm_long_min}, {"add_path", &c->tune.add_path},
 		{"masked_path", &c->tune.masked_path}, {"sampled_path", &c->tune.sampled_path}, {"select_path", &c->tune.select_path},
-		{"extract_path", &c->tune.extract_path}, {"reduce_path", &c->tune.reduce_path},
+		{"extract_path", &c->tune.extract_path}, {"reduce_path", &c->tune.reduce_path}, {"emult_path", &c->tune.emult_path},
 	};
 	for (auto &t : tab) if (!std::strcmp(t.n, name)) { *t.p = (int)value; return SPSAMD_OK; }
 	c->last_error = std::string("unknown tuning knob: ") + name;
@@ -519,6 +519,18 @@ extern "C" int spsamd_reduce(spsamd_ctx *c, const spsamd_coo *A, char transpose,
 		spsamd_result local;
 		return reduce_rows(c, A, transpose, op, post, duplicate_policy, zero_nan, out_idx, out_val, capacity, mem, out_nnz,
 			res ? res : &local);
+	)
+}
+
+// op(A) o op(B) over the intersection of the two patterns, op(A) on or off op(B)'s pattern (k_emult.hip)
+extern "C" int spsamd_emult(spsamd_ctx *c, int op, int emult_flags, double alpha, const spsamd_coo *A, char transpose_A,
+	const spsamd_coo *B, char transpose_B, int duplicate_policy, int zero_nan, int sink_kind, int sink_flags, spsamd_result *res)
+{
+	if (!c) return SPSAMD_EINVAL;
+	API_GUARD(c,
+		if (!A || !B || !res) throw Error{SPSAMD_EINVAL, "null operand or result"};
+		emult_matrices(c, op, emult_flags, alpha, A, transpose_A, B, transpose_B, duplicate_policy, zero_nan, sink_kind, sink_flags, res);
+		return SPSAMD_OK;
 	)
 }
 

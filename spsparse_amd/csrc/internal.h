@@ -94,6 +94,7 @@ struct Tuning {
 	int select_path = 0;         // select, ROW_TOPK: 0 by row length | 1 light | 2 mid | 3 heavy kernel for every row it can hold
 	int extract_path = 0;        // extract: 0 auto | 1 every row through the permuted path | 2 light | 3 mid | 4 heavy ordering kernel for every row it can hold
 	int reduce_path = 0;         // reduce: 0 by row length | 1 every row through the short rows' kernel | 2 every row through the long rows' kernel
+	int emult_path = 0;          // emult: 0 by a byte model | 1 merge | 2 every tuple of op(A) probes op(B) | 3 every key of op(B) probes op(A)
 #ifdef SPSAMD_ABLATIONS
 	int dbg = 0;
 #endif
@@ -227,6 +228,30 @@ const T *to_device(spsamd_ctx *c, const T *p, size_t n, int mem)
 	SPS_HIP(hipMemcpyAsync(d, p, n * sizeof(T), hipMemcpyHostToDevice, c->stream));
 	return d;
 }
+
+// A plain operand (host or device, X.nnz > 0) as a stream of op()'s tuples for the calls that merge or search sorted streams
+// (add, emult): the argument checks, the arrays on the device in op()'s orientation (lead = 1 for 'T') and, unless it is a
+// result this context wrote itself, the inspection flags (inspect_operand).  SPSAMD_EINVAL: an index out of bounds; a sort0
+// that names op()'s row order over (row, col) keys that descend somewhere (equal keys are allowed).
+struct PlainStream {
+	const int32_t *major = nullptr, *minor = nullptr;
+	const double *val = nullptr;
+	uint32_t flags = 0;           // inspect_operand's; 0 for an own result
+	bool own_result = false;
+};
+PlainStream plain_stream(spsamd_ctx *c, const spsamd_coo &X, int lead);
+
+// A structural operand (multiply_masked's M, emult's pattern operand): the keys of op(M) in row-major order, each once --
+// workspace memory, or M's own arrays where they already are that (`prep`: the handle of the same transpose they belong
+// to).  Only the indices are read (val may be null); duplicate keys count once, explicit zeros count; an index out of
+// bounds and a sort0 that names op()'s row order over keys that descend are SPSAMD_EINVAL.  lead = 1 for 'T'; nrow x ncol
+// is op(M)'s shape.
+struct MaskKeys {
+	const int32_t *i = nullptr, *j = nullptr;
+	uint32_t n = 0;
+	Prepared *prep = nullptr;
+};
+void mask_keys(spsamd_ctx *c, const spsamd_coo *M, int lead, uint64_t nrow, uint64_t ncol, MaskKeys *out);
 
 int bits_of(uint64_t dim);        // bits needed to hold indices 0 .. dim-1
 // keys[i] = major[i] << minor_bits | minor[i]: the sort key of radix_sort_pairs (payload: the storage position) ...
@@ -404,6 +429,20 @@ void spmm_dense(spsamd_ctx *c, const DenseOperand &m, const double *X, uint64_t 
 
 // ---------------------------------------------------------------- sparse addition (k_add.hip)
 
+// op(X) on the device, ordered by (row, col), storage order inside a key: one side of a merge
+struct AddStream {
+	const int32_t *row = nullptr, *col = nullptr;
+	const double *val = nullptr;
+	uint32_t n = 0;
+};
+constexpr int ADD_NT = 256;                    // lanes per tile
+constexpr int ADD_IPT = 8;                     // merged items per lane
+constexpr int ADD_TILE = ADD_NT * ADD_IPT;     // merged items per tile
+// Merge-path split of the merged sequence of a and b (64-bit keys row << 32 | col, ties: a first) into `ntiles` tiles of
+// ADD_TILE items: split[t] = how many of a's tuples lie in the first min(t * ADD_TILE, a.n + b.n) items (ntiles + 1 entries).
+// Shared by add and emult.
+void merge_partition(spsamd_ctx *c, const AddStream &a, const AddStream &b, uint32_t ntiles, uint32_t *split);
+
 // C = alpha * op(A) + beta * op(B) into the sink: spsamd_add after its null checks
 void add_matrices(spsamd_ctx *c, double alpha, const spsamd_coo *A, char transpose_A, double beta, const spsamd_coo *B,
 	char transpose_B, int duplicate_policy, int zero_nan, int sink_kind, int sink_flags, spsamd_result *res);
@@ -441,6 +480,13 @@ void extract_tuples(spsamd_ctx *c, const spsamd_coo *A, char transpose, const in
 // SPSAMD_ECAPACITY with *out_nnz = the entries needed and the context's last error set (nothing written).
 int reduce_rows(spsamd_ctx *c, const spsamd_coo *A, char transpose, int op, int post, int duplicate_policy, int zero_nan,
 	int32_t *out_idx, double *out_val, size_t capacity, int mem, size_t *out_nnz, spsamd_result *res);
+
+// ---------------------------------------------------------------- element-wise product and pattern restriction (k_emult.hip)
+
+// op(A) o op(B) (TIMES), op(A) on (FIRST) or off (FIRST | COMPLEMENT) op(B)'s pattern into the sink: spsamd_emult after
+// its null checks
+void emult_matrices(spsamd_ctx *c, int op, int emult_flags, double alpha, const spsamd_coo *A, char transpose_A,
+	const spsamd_coo *B, char transpose_B, int duplicate_policy, int zero_nan, int sink_kind, int sink_flags, spsamd_result *res);
 
 // The same operand struct twice (A * A): one consolidation can serve both sides (capi.hip).
 bool same_operand(const spsamd_coo *a, const spsamd_coo *b);

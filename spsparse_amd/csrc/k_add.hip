@@ -28,17 +28,6 @@
 
 namespace spsamd {
 
-constexpr int ADD_NT = 256;                    // lanes per tile
-constexpr int ADD_IPT = 8;                     // merged items per lane
-constexpr int ADD_TILE = ADD_NT * ADD_IPT;     // merged items per tile
-
-// op(X) on the device, ordered by (row, col), storage order inside a key
-struct AddStream {
-	const int32_t *row = nullptr, *col = nullptr;
-	const double *val = nullptr;
-	uint32_t n = 0;
-};
-
 // The first tuple of the merged sequence that consolidate() keeps whatever zero_nan says (neither 0 nor NaN after
 // scaling), as its position in merge order (key, stream, index): under zero_nan the NaNs before it are the leading
 // run the reference drops (algorithm.hpp:272-275).  key = ~0: there is none, every NaN is dropped.
@@ -96,6 +85,12 @@ __global__ void __launch_bounds__(256) k_add_partition(AddStream a, AddStream b,
 		else hi = mid;
 	}
 	split[t] = lo;
+}
+
+void merge_partition(spsamd_ctx *c, const AddStream &a, const AddStream &b, uint32_t ntiles, uint32_t *split)
+{
+	k_add_partition<<<dim3(grid_for((size_t)ntiles + 1)), dim3(256), 0, c->stream>>>(a, b, ntiles, split);
+	SPS_LAUNCH_CHECK();
 }
 
 constexpr int ADD_COUNT = -1;                  // MODE of the count pass; the write pass's MODE is the duplicate policy
@@ -234,24 +229,15 @@ static void add_stream(spsamd_ctx *c, const spsamd_coo *X, int lead, bool force_
 	X = &view.coo;
 	const size_t n = X->nnz;
 	if (n == 0) return;
-	check_operand(*X, OPERAND_VALUES | OPERAND_PLAIN_MEM);
 	const uint64_t shape[2] = {X->shape0, X->shape1};
-	const bool own_result = is_own_result(c, *X);                       // a SINK_COO result of this context handed back in
-	const int32_t *d0 = to_device(c, X->idx0, n, X->mem), *d1 = to_device(c, X->idx1, n, X->mem);
-	const double *dv = to_device(c, X->val, n, X->mem);
-	const int32_t *major = lead == 0 ? d0 : d1, *minor = lead == 0 ? d1 : d0;
-	bool ordered = own_result && X->sort0 == lead;
-	int low_bit = 0;
-	if (!own_result) {
-		const uint32_t f = inspect_operand(c, major, minor, dv, n, shape[lead], shape[1 - lead]);
-		if (f & 1u) throw Error{SPSAMD_EINVAL, "Sparse index out of bounds (VectorCooArray::add would reject it, VectorCooArray.hpp:246-262)"};
-		if (X->sort0 == lead && (f & 32u))
-			throw Error{SPSAMD_EINVAL, "operand claims sort_order but its (row, col) keys are not in that order (set_sorted() on unsorted tuples?)"};
-		ordered = !(f & 32u);
-		// strictly in (minor, major) order -- a row-major matrix used with 'T': the stable passes over the major digits alone
-		// leave equal majors in storage order, which is minor order (as consolidate_operand does)
-		if (!(f & 4u)) low_bit = -1;
-	}
+	const PlainStream ps = plain_stream(c, *X, lead);
+	const int32_t *major = ps.major, *minor = ps.minor;
+	const double *dv = ps.val;
+	// a SINK_COO result of this context handed back in is in the order its sort0 names; anything else: as inspected
+	const bool ordered = ps.own_result ? X->sort0 == lead : !(ps.flags & 32u);
+	// strictly in (minor, major) order -- a row-major matrix used with 'T': the stable passes over the major digits alone
+	// leave equal majors in storage order, which is minor order (as consolidate_operand does)
+	const int low_bit = !ps.own_result && !(ps.flags & 4u) ? -1 : 0;
 	if (ordered && !force_sort) { out->row = major; out->col = minor; out->val = dv; out->n = (uint32_t)n; return; }
 	// one stable radix sort on (major, minor), storage position as payload; the indices come back out of the sorted keys,
 	// so only the value is gathered from storage
@@ -327,8 +313,7 @@ void add_matrices(spsamd_ctx *c, double alpha, const spsamd_coo *A, char transpo
 	}
 	uint32_t *split = c->arena.get<uint32_t>((size_t)ntiles + 1);
 	uint32_t *tile_count = c->arena.get<uint32_t>((size_t)ntiles + 1), *tile_off = c->arena.get<uint32_t>((size_t)ntiles + 1);
-	k_add_partition<<<dim3(grid_for((size_t)ntiles + 1)), dim3(256), 0, st>>>(sa, sb, ntiles, split);
-	SPS_LAUNCH_CHECK();
+	merge_partition(c, sa, sb, ntiles, split);
 	launch_merge<ADD_COUNT>(c, ntiles, sa, sb, alpha, beta, zero_nan, first, split, tile_count, nullptr, nullptr, nullptr, nullptr);
 	scan_exclusive_u32_u32(c, tile_count, tile_off, ntiles);
 	const uint32_t total = read_back(c, tile_off + ntiles);

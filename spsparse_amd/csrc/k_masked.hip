@@ -332,88 +332,6 @@ __global__ void __launch_bounds__(256) k_masked_digest(const int32_t *__restrict
 	if (lane_id() == 0) { atomicAdd(&acc[0], n); atomicAdd(&acc[1], h); atomicAdd((double *)&acc[2], s); }
 }
 
-// ---------------------------------------------------------------- M's keys
-
-// bit0: an index out of bounds; bit1: the (row, col) key descends somewhere; bit2: a key repeats its predecessor
-__global__ void __launch_bounds__(256) k_mask_inspect(const int32_t *__restrict__ r, const int32_t *__restrict__ c, size_t n,
-	uint64_t nrow, uint64_t ncol, uint32_t *flags)
-{
-	uint32_t f = 0;
-	for (size_t t = (size_t)blockIdx.x * blockDim.x + threadIdx.x; t < n; t += (size_t)gridDim.x * blockDim.x) {
-		const int32_t x = r[t], y = c[t];
-		if (x < 0 || (uint64_t)x >= nrow || y < 0 || (uint64_t)y >= ncol) f |= 1u;
-		if (t > 0) {
-			const int32_t px = r[t - 1], py = c[t - 1];
-			if (px > x || (px == x && py > y)) f |= 2u;
-			if (px == x && py == y) f |= 4u;
-		}
-	}
-	uint32_t wf = 0;
-	for (uint32_t b = 1u; b <= 4u; b <<= 1) if (__ballot(f & b)) wf |= b;
-	if (lane_id() == 0 && wf) atomicOr(flags, wf);
-}
-
-__global__ void __launch_bounds__(256) k_mask_first(const uint64_t *__restrict__ keys, uint32_t n, uint8_t *__restrict__ first)
-{
-	const uint32_t t = blockIdx.x * blockDim.x + threadIdx.x;
-	if (t < n) first[t] = t == 0 || keys[t] != keys[t - 1];
-}
-
-__global__ void __launch_bounds__(256) k_mask_unique(const uint64_t *__restrict__ keys, const uint8_t *__restrict__ first,
-	const uint32_t *__restrict__ off, uint32_t n, int cbits, int32_t *__restrict__ mi, int32_t *__restrict__ mj)
-{
-	const uint32_t t = blockIdx.x * blockDim.x + threadIdx.x;
-	if (t >= n || !first[t]) return;
-	const uint64_t k = keys[t];
-	mi[off[t]] = (int32_t)(k >> cbits);
-	mj[off[t]] = (int32_t)(k & ((uint64_t(1) << cbits) - 1));
-}
-
-// M's keys, row-major and each once (arena memory, or M's own arrays where they already are that)
-struct MaskKeys {
-	const int32_t *i = nullptr, *j = nullptr;
-	uint32_t n = 0;
-};
-
-static void mask_keys(spsamd_ctx *c, const spsamd_coo *M, uint64_t nrow, uint64_t ncol, MaskKeys *out)
-{
-	*out = MaskKeys();
-	const OperandView view = operand_view(c, M);
-	if (view.prep && view.prep->lead == 0) { out->i = view.prep->m.row; out->j = view.prep->m.col; out->n = view.prep->m.nnz; return; }     // consolidated row-major
-	const spsamd_coo &X = view.coo;                  // (prepared for 'T': its consolidated tuples, sorted the other way)
-	const size_t n = X.nnz;
-	if (n == 0) return;
-	check_operand(X, OPERAND_PLAIN_MEM);             // only M's keys are read: val may be null
-	const int32_t *r = to_device(c, X.idx0, n, X.mem), *cc = to_device(c, X.idx1, n, X.mem);
-	uint32_t *flags = c->arena.get<uint32_t>(1);
-	fill_zero(c, flags, sizeof(uint32_t));
-	k_mask_inspect<<<dim3(std::min(grid_for(n, 1024), 2048u)), dim3(256), 0, c->stream>>>(r, cc, n, nrow, ncol, flags);
-	SPS_LAUNCH_CHECK();
-	const uint32_t f = read_back(c, flags);
-	if (f & 1u) throw Error{SPSAMD_EINVAL, "M: index out of bounds"};
-	if (X.sort0 == 0 && (f & 2u)) throw Error{SPSAMD_EINVAL, "M claims sort_order {0, 1} but its (row, col) keys are not in that order"};
-	if (!(f & 6u)) { out->i = r; out->j = cc; out->n = (uint32_t)n; return; }      // in order, no repeats: read in place
-	const int cb = bits_of(ncol), rb = bits_of(nrow);
-	uint64_t *keys0 = c->arena.get<uint64_t>(n);
-	build_keys(c, r, cc, n, cb, keys0);
-	const uint64_t *keys = keys0;
-	if (f & 2u) {
-		uint64_t *keys1 = c->arena.get<uint64_t>(n);
-		uint32_t *pay0 = c->arena.get<uint32_t>(n), *pay1 = c->arena.get<uint32_t>(n);
-		keys = radix_sort_pairs(c, keys0, pay0, keys1, pay1, n, cb + rb) ? keys1 : keys0;
-	}
-	uint8_t *first = c->arena.get<uint8_t>(n);
-	uint32_t *off = c->arena.get<uint32_t>(n + 1);
-	k_mask_first<<<dim3(grid_for(n)), dim3(256), 0, c->stream>>>(keys, (uint32_t)n, first);
-	SPS_LAUNCH_CHECK();
-	scan_exclusive_u8_u32(c, first, off, n);
-	const uint32_t nu = read_back(c, off + n);
-	int32_t *mi = c->arena.get<int32_t>(nu), *mj = c->arena.get<int32_t>(nu);
-	k_mask_unique<<<dim3(grid_for(n)), dim3(256), 0, c->stream>>>(keys, first, off, (uint32_t)n, cb, mi, mj);
-	SPS_LAUNCH_CHECK();
-	out->i = mi; out->j = mj; out->n = nu;
-}
-
 void multiply_masked(spsamd_ctx *c, double C,
 	const spsamd_vec *scalei, const spsamd_coo *A, char transpose_A,
 	const spsamd_vec *scalej, const spsamd_coo *B, char transpose_B,
@@ -458,7 +376,7 @@ void multiply_masked(spsamd_ctx *c, double C,
 	upload_scale(c, scalek, ncol, "scalek", &sk);
 	SPS_HIP(hipEventRecord(c->ev[EV_CONSOLIDATED], st));
 	MaskKeys mk;
-	mask_keys(c, M, nrow, ncol, &mk);
+	mask_keys(c, M, 0, nrow, ncol, &mk);
 	const uint32_t nm = mk.n;
 	ConMat mcon;
 	mcon.row = const_cast<int32_t *>(mk.i); mcon.col = const_cast<int32_t *>(mk.j); mcon.nnz = nm; mcon.nrow = nrow; mcon.ncol = ncol;

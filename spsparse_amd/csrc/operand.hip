@@ -2,7 +2,9 @@
 // starts -- which arrays hold its tuples, whether they may be trusted without the inspection pass, the argument checks --
 // and the frame of a product.  Each rule is written here once; what an operation does after intake is in its own file.
 #include "internal.h"
+#include "devutil.h"
 
+#include <algorithm>
 #include <cstdio>
 
 namespace spsamd {
@@ -85,6 +87,102 @@ void gather_sorted(spsamd_ctx *c, const uint64_t *keys, const uint32_t *perm, co
 {
 	k_gather_sorted<<<dim3(grid_for(n)), dim3(256), 0, c->stream>>>(keys, perm, val, (uint32_t)n, minor_bits, row, col, oval);
 	SPS_LAUNCH_CHECK();
+}
+
+PlainStream plain_stream(spsamd_ctx *c, const spsamd_coo &X, int lead)
+{
+	check_operand(X, OPERAND_VALUES | OPERAND_PLAIN_MEM);
+	const size_t n = X.nnz;
+	const uint64_t shape[2] = {X.shape0, X.shape1};
+	PlainStream s;
+	s.own_result = is_own_result(c, X);
+	const int32_t *d0 = to_device(c, X.idx0, n, X.mem), *d1 = to_device(c, X.idx1, n, X.mem);
+	s.val = to_device(c, X.val, n, X.mem);
+	s.major = lead == 0 ? d0 : d1; s.minor = lead == 0 ? d1 : d0;
+	if (s.own_result) return s;
+	s.flags = inspect_operand(c, s.major, s.minor, s.val, n, shape[lead], shape[1 - lead]);
+	if (s.flags & 1u) throw Error{SPSAMD_EINVAL, "Sparse index out of bounds (VectorCooArray::add would reject it, VectorCooArray.hpp:246-262)"};
+	if (X.sort0 == lead && (s.flags & 32u))
+		throw Error{SPSAMD_EINVAL, "operand claims sort_order but its (row, col) keys are not in that order (set_sorted() on unsorted tuples?)"};
+	return s;
+}
+
+// ---------------------------------------------------------------- structural keys (a mask M, emult's pattern operand)
+
+// bit0: an index out of bounds; bit1: the (row, col) key descends somewhere; bit2: a key repeats its predecessor
+__global__ void __launch_bounds__(256) k_mask_inspect(const int32_t *__restrict__ r, const int32_t *__restrict__ c, size_t n,
+	uint64_t nrow, uint64_t ncol, uint32_t *flags)
+{
+	uint32_t f = 0;
+	for (size_t t = (size_t)blockIdx.x * blockDim.x + threadIdx.x; t < n; t += (size_t)gridDim.x * blockDim.x) {
+		const int32_t x = r[t], y = c[t];
+		if (x < 0 || (uint64_t)x >= nrow || y < 0 || (uint64_t)y >= ncol) f |= 1u;
+		if (t > 0) {
+			const int32_t px = r[t - 1], py = c[t - 1];
+			if (px > x || (px == x && py > y)) f |= 2u;
+			if (px == x && py == y) f |= 4u;
+		}
+	}
+	uint32_t wf = 0;
+	for (uint32_t b = 1u; b <= 4u; b <<= 1) if (__ballot(f & b)) wf |= b;
+	if (lane_id() == 0 && wf) atomicOr(flags, wf);
+}
+
+__global__ void __launch_bounds__(256) k_mask_first(const uint64_t *__restrict__ keys, uint32_t n, uint8_t *__restrict__ first)
+{
+	const uint32_t t = blockIdx.x * blockDim.x + threadIdx.x;
+	if (t < n) first[t] = t == 0 || keys[t] != keys[t - 1];
+}
+
+__global__ void __launch_bounds__(256) k_mask_unique(const uint64_t *__restrict__ keys, const uint8_t *__restrict__ first,
+	const uint32_t *__restrict__ off, uint32_t n, int cbits, int32_t *__restrict__ mi, int32_t *__restrict__ mj)
+{
+	const uint32_t t = blockIdx.x * blockDim.x + threadIdx.x;
+	if (t >= n || !first[t]) return;
+	const uint64_t k = keys[t];
+	mi[off[t]] = (int32_t)(k >> cbits);
+	mj[off[t]] = (int32_t)(k & ((uint64_t(1) << cbits) - 1));
+}
+
+void mask_keys(spsamd_ctx *c, const spsamd_coo *M, int lead, uint64_t nrow, uint64_t ncol, MaskKeys *out)
+{
+	*out = MaskKeys();
+	const OperandView view = operand_view(c, M);
+	if (view.prep && view.prep->lead == lead) { out->i = view.prep->m.row; out->j = view.prep->m.col; out->n = view.prep->m.nnz; out->prep = view.prep; return; }     // consolidated in op()'s row order
+	const spsamd_coo &X = view.coo;                  // (prepared for the other transpose: its consolidated tuples, sorted the other way)
+	const size_t n = X.nnz;
+	if (n == 0) return;
+	check_operand(X, OPERAND_PLAIN_MEM);             // only M's keys are read: val may be null
+	const int32_t *d0 = to_device(c, X.idx0, n, X.mem), *d1 = to_device(c, X.idx1, n, X.mem);
+	const int32_t *r = lead == 0 ? d0 : d1, *cc = lead == 0 ? d1 : d0;
+	uint32_t *flags = c->arena.get<uint32_t>(1);
+	fill_zero(c, flags, sizeof(uint32_t));
+	k_mask_inspect<<<dim3(std::min(grid_for(n, 1024), 2048u)), dim3(256), 0, c->stream>>>(r, cc, n, nrow, ncol, flags);
+	SPS_LAUNCH_CHECK();
+	const uint32_t f = read_back(c, flags);
+	if (f & 1u) throw Error{SPSAMD_EINVAL, "pattern operand: index out of bounds"};
+	if (X.sort0 == lead && (f & 2u))
+		throw Error{SPSAMD_EINVAL, "pattern operand claims op()'s row order but its (row, col) keys are not in that order"};
+	if (!(f & 6u)) { out->i = r; out->j = cc; out->n = (uint32_t)n; return; }      // in order, no repeats: read in place
+	const int cb = bits_of(ncol), rb = bits_of(nrow);
+	uint64_t *keys0 = c->arena.get<uint64_t>(n);
+	build_keys(c, r, cc, n, cb, keys0);
+	const uint64_t *keys = keys0;
+	if (f & 2u) {
+		uint64_t *keys1 = c->arena.get<uint64_t>(n);
+		uint32_t *pay0 = c->arena.get<uint32_t>(n), *pay1 = c->arena.get<uint32_t>(n);
+		keys = radix_sort_pairs(c, keys0, pay0, keys1, pay1, n, cb + rb) ? keys1 : keys0;
+	}
+	uint8_t *first = c->arena.get<uint8_t>(n);
+	uint32_t *off = c->arena.get<uint32_t>(n + 1);
+	k_mask_first<<<dim3(grid_for(n)), dim3(256), 0, c->stream>>>(keys, (uint32_t)n, first);
+	SPS_LAUNCH_CHECK();
+	scan_exclusive_u8_u32(c, first, off, n);
+	const uint32_t nu = read_back(c, off + n);
+	int32_t *mi = c->arena.get<int32_t>(nu), *mj = c->arena.get<int32_t>(nu);
+	k_mask_unique<<<dim3(grid_for(n)), dim3(256), 0, c->stream>>>(keys, first, off, (uint32_t)n, cb, mi, mj);
+	SPS_LAUNCH_CHECK();
+	out->i = mi; out->j = mj; out->n = nu;
 }
 
 ProductFrame::ProductFrame(const spsamd_coo *A, char transpose_A, const spsamd_coo *B, char transpose_B, bool permute)
