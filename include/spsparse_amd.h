@@ -186,6 +186,7 @@ const char *spsamd_version(void);
  *   tiles_v1        1 | 2 | 3         hash tiles r01 | hash tiles v2 | bitmap-rank tiles (default: chosen per call)
  *   no_tiles, no_wmajor               1: no tiles | no window-major copy of B
  *   xcd                               0: one cell list for all XCDs | 1: static XCD parts (experiment) | 2: dense cells claimed from XCD parts (default)
+ *   tile_walk       1                 the heavy rows' tiles dealt with a static grid stride (default: claimed from a counter)
  *   emit_path       1 | 2             COO order of a hash cell: LDS radix sort | bitonic network (default: by cell width)
  *   light_path      1                 binned light kernels even where every row is light
  *   light_two_pass  1                 all-light COO sink: count, scan, store (two compute passes) instead of one pass + gather

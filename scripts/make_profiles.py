@@ -64,6 +64,9 @@ def main():
         dbs = glob.glob(os.path.join(d, "**", "*_results.db"), recursive=True)
         if dbs:
             kernel_stats(dbs[0], os.path.join(DST, "%s_kernel_stats.csv" % name))
+        if dbs and name == "cfg2":                           # the headline step's kernels one by one: order, streams, gaps
+            with open(os.path.join(DST, "cfg2_step_timeline.txt"), "w") as f:
+                subprocess.run([sys.executable, os.path.join(ROOT, "scripts", "step_timeline.py"), dbs[0]], stdout=f)
         b = os.path.join(SRC, "bench_%s.json" % name)
         if os.path.exists(b):
             shutil.copy(b, os.path.join(DST, "%s_bench_under_rocprof.json" % name))

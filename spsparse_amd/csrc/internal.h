@@ -94,6 +94,7 @@ struct Tuning {
 	int select_path = 0;         // select, ROW_TOPK: 0 by row length | 1 light | 2 mid | 3 heavy kernel for every row it can hold
 	int extract_path = 0;        // extract: 0 auto | 1 every row through the permuted path | 2 light | 3 mid | 4 heavy ordering kernel for every row it can hold
 	int reduce_path = 0;         // reduce: 0 by row length | 1 every row through the short rows' kernel | 2 every row through the long rows' kernel
+	int tile_walk = 0;           // tiles of the heavy rows: 0 claimed from a counter | 1 the static grid-stride walk
 	int emult_path = 0;          // emult: 0 by a byte model | 1 merge | 2 every tuple of op(A) probes op(B) | 3 every key of op(B) probes op(A)
 #ifdef SPSAMD_ABLATIONS
 	int dbg = 0;
@@ -384,6 +385,7 @@ struct MultiplyArgs {
 	hipEvent_t b_ready = nullptr;            // the TUPLES of B arrive on another stream (the distributed step's panel): wait for this
 	                                         // event before the first kernel that reads them; its row pointer (pb->rowptr) is valid at once
 	OutSet *out = nullptr;                   // SINK_COO: the arrays the tuples go to (null: the context's current output set)
+	bool static_walk = false;                // the distributed step's block product: its tiles keep the static walk
 };
 void spgemm(spsamd_ctx *c, MultiplyArgs &a, spsamd_result *res);
 void prepared_row_structure(spsamd_ctx *c, Prepared *p);      // its dense row pointer and longest row, now (spgemm.hip)

@@ -5,6 +5,8 @@
 
 namespace spsamd {
 
+constexpr uint32_t TILE_NONE = 0xFFFFFFFFu;          // no (further) tile for this workgroup
+
 // ---- hash tiles: cells are ranges [wa, wb) of sparse column windows, accumulated in the LDS hash table ----
 // Insertion: the R first probes of a lane are in flight together (ds_cmpswap with return), the rare collisions are
 // then walked one by one; the values follow with ds_add_f64; the newly occupied slots of a step are appended to the
@@ -13,7 +15,7 @@ namespace spsamd {
 
 template <int MODE, bool PAT>
 __global__ __launch_bounds__(TILE2_NT, 4) void k_hash_tiles2(const Tile *tiles, uint32_t ntile, const TCell *tcells, RowMeta m,
-	const uint32_t *bwin, uint32_t nwin1, uint32_t narrow, EmitParams ep, SinkParams sk)
+	const uint32_t *bwin, uint32_t nwin1, uint32_t narrow, EmitParams ep, SinkParams sk, uint32_t *claim_ctr)
 {
 	constexpr int NT = TILE2_NT, T = TILE2_T, NW = NT / 64, R = DENSE_R;
 	constexpr int NWORD = TILE2_ITEMS / 64;
@@ -29,6 +31,7 @@ __global__ __launch_bounds__(TILE2_NT, 4) void k_hash_tiles2(const Tile *tiles, 
 	__shared__ PatCell s_pat;
 	__shared__ unsigned long long s_u64[2 * NW];
 	__shared__ double s_f64[NW];
+	__shared__ uint32_t s_claim[4];
 
 	const unsigned tid = threadIdx.x, lane = lane_id();
 	const unsigned wv = (unsigned)__builtin_amdgcn_readfirstlane((int)wave_id());
@@ -45,11 +48,28 @@ __global__ __launch_bounds__(TILE2_NT, 4) void k_hash_tiles2(const Tile *tiles, 
 	unsigned long long st_[12] = {}; unsigned long long st_t = clock64();
 #endif
 
+	// Two ways to deal the (window-major) tile list.  STATIC (claim_ctr null): a grid stride.  CLAIMED: a workgroup's next tile
+	// is atomicAdd(claim_ctr, 1), so a workgroup that becomes resident late -- the LDS of its CU still held by another
+	// stream's kernel -- simply takes fewer tiles instead of owning 1 / grid of the list (static, the kernel runs as long as
+	// its last-started workgroup).  Thread 0 claims: three tiles before the loop, then one per tile at the top of the tile,
+	// with tile_expand for the answer to arrive (no register is free to hold it across the cell loop: a spill there is a wait
+	// for the atomic on the spot).  It publishes the answer in s_claim[2 + (iter & 1)] behind tile_expand; the other waves read
+	// it a tile later, behind the next tile_expand's barriers, as the tile after the next.
+	const bool claimed = claim_ctr != nullptr;
 	const uint32_t stride = gridDim.x;
 	const uint32_t tlast = ntile - 1;
-	// three-stage branch-free prefetch: tile record -> (A tuple, cell window range) -> B segment bounds
-	Tile rec1 = tiles[min(blockIdx.x, tlast)];
-	Tile rec2 = tiles[min(blockIdx.x + stride, tlast)];
+	uint32_t i0, i1;                                                // this tile, the next (uniform; TILE_NONE: none)
+	if (claimed) {
+		if (tid == 0) for (int q = 0; q < 3; ++q) { const uint32_t got = atomicAdd(claim_ctr, 1u); s_claim[q == 2 ? 3 : q] = got < ntile ? got : TILE_NONE; }
+		__syncthreads();
+		i0 = s_claim[0]; i1 = s_claim[1];                           // (the third: s_claim[3], read behind the first tile_expand)
+	} else {
+		i0 = blockIdx.x;
+		i1 = i0 + stride < ntile ? i0 + stride : TILE_NONE;
+	}
+	i0 = (uint32_t)__builtin_amdgcn_readfirstlane((int)i0); i1 = (uint32_t)__builtin_amdgcn_readfirstlane((int)i1);
+	// branch-free prefetch: (the next tile's record, read where its turn comes ->) A tuple, cell window range -> B segment bounds
+	Tile rec1 = tiles[min(i0, tlast)];
 	uint32_t nlo, nlen, nseg_, nw_; double na;
 	{
 		const uint32_t L = rec1.end - rec1.beg;
@@ -65,7 +85,7 @@ __global__ __launch_bounds__(TILE2_NT, 4) void k_hash_tiles2(const Tile *tiles, 
 		nlo = lo; nlen = act ? hi - lo : 0u; nseg_ = tc.seg; nw_ = (uint32_t)tc.wa | ((uint32_t)tc.wb << 16);
 	}
 	__syncthreads();
-	for (uint32_t ti = blockIdx.x; ti < ntile; ti += stride) {
+	for (uint32_t iter = 0, i2 = TILE_NONE; i0 != TILE_NONE; ++iter, i0 = i1, i1 = claimed ? i2 : (i1 != TILE_NONE && i1 + stride < ntile ? i1 + stride : TILE_NONE)) {
 		const Tile tile = rec1;
 		const uint32_t lo = nlo, len = nlen, myseg = nseg_, myw = nw_; const double a = na;
 		const uint32_t L = tile.end - tile.beg;
@@ -74,9 +94,8 @@ __global__ __launch_bounds__(TILE2_NT, 4) void k_hash_tiles2(const Tile *tiles, 
 		lsh = (uint32_t)__builtin_amdgcn_readfirstlane((int)lsh);
 		const int32_t rowid = tile.rowid;
 		// stage A / B for the next tile
-		rec1 = rec2;
-		rec2 = tiles[min(ti + 2 * stride, tlast)];
-		const bool has_next = ti + stride < ntile;
+		rec1 = tiles[min(i1, tlast)];
+		const bool has_next = i1 != TILE_NONE;
 		const uint32_t nL = rec1.end - rec1.beg;
 		uint32_t nsh = 0;
 		while ((1u << nsh) < nL) ++nsh;
@@ -86,12 +105,20 @@ __global__ __launch_bounds__(TILE2_NT, 4) void k_hash_tiles2(const Tile *tiles, 
 		const TCell ntc = tcells[rec1.first + (nc < rec1.ncells ? nc : 0u)];
 		const int32_t nk = m.acol[nec];
 		na = m.aval[nec];
+		uint32_t claim_pending = TILE_NONE;                         // (once a claim found the list used up no further one is made)
+		if (claimed && tid == 0 && i1 != TILE_NONE) claim_pending = atomicAdd(claim_ctr + cell_pend_zero(), 1u);     // (answered under tile_expand.  The
+		// per-lane zero keeps the address from looking uniform: the compiler then combines the wave's adds into one and reads the answer
+		// with s_waitcnt vmcnt(0) + v_readfirstlane at once -- the atomic's latency and every prefetch in flight drained, per tile)
 
 		uint32_t total, nzc;
 		STAMP_COUNT(8);
 		STAMP(0);
 		tile_expand(X, lsh, tile.ncells, lo, len, a, myseg, myw, flip, &total, &nzc);
 		STAMP(1);
+		if (claimed) {
+			if (tid == 0) s_claim[2 + (iter & 1u)] = claim_pending < ntile ? claim_pending : TILE_NONE;
+			i2 = (uint32_t)__builtin_amdgcn_readfirstlane((int)s_claim[2 + ((iter + 1u) & 1u)]);     // (published a tile ago)
+		}
 		// stage C: B segment bounds of the next tile
 		{
 			const uint32_t *bw = bwin + (uint64_t)(uint32_t)nk * nwin1;
@@ -193,7 +220,7 @@ __global__ __launch_bounds__(TILE2_NT, 4) void k_hash_tiles2(const Tile *tiles, 
 			lds_barrier();                                          // table clean, counter reset: next cell may insert
 			STAMP(7);
 		}
-		for (int q = tid; q < NWORD; q += NT) X.bmask[q] = 0ull;     // (every wave is past its last lookup)
+		for (int q = tid; q < NWORD; q += NT) X.bmask[q] = 0ull;     // (every wave is past its last lookup: the cell loop ends with a barrier)
 	}
 #ifdef SPSAMD_STAMPS
 	if (tid == 0 && sk.stamps) for (int i = 0; i < 12; ++i) sk.stamps[(size_t)blockIdx.x * 12 + i] = st_[i];
@@ -214,7 +241,7 @@ __global__ __launch_bounds__(TILE2_NT, 4) void k_hash_tiles2(const Tile *tiles, 
 
 template <int MODE, bool PAT>
 __global__ __launch_bounds__(BM_NT, 4) void k_bm_tiles(const Tile *tiles, uint32_t ntile, const TCell *tcells, RowMeta m,
-	const uint32_t *bwin, uint32_t nwin1, uint32_t narrow, EmitParams ep, SinkParams sk)
+	const uint32_t *bwin, uint32_t nwin1, uint32_t narrow, EmitParams ep, SinkParams sk, uint32_t *claim_ctr)
 {
 	constexpr int NT = BM_NT, NW = NT / 64, R = DENSE_R;
 	constexpr int NWORD = BM_ITEMS / 64;
@@ -231,6 +258,7 @@ __global__ __launch_bounds__(BM_NT, 4) void k_bm_tiles(const Tile *tiles, uint32
 	__shared__ uint32_t s_scan[NW + 1];
 	__shared__ unsigned long long s_u64[2 * NW];
 	__shared__ double s_f64[NW];
+	__shared__ uint32_t s_claim[4];
 
 	const unsigned tid = threadIdx.x, lane = lane_id();
 	const unsigned wv = (unsigned)__builtin_amdgcn_readfirstlane((int)wave_id());
@@ -247,10 +275,20 @@ __global__ __launch_bounds__(BM_NT, 4) void k_bm_tiles(const Tile *tiles, uint32
 	unsigned long long st_[12] = {}; unsigned long long st_t = clock64();
 #endif
 
+	const bool claimed = claim_ctr != nullptr;                      // (the walk: k_hash_tiles2 above)
 	const uint32_t stride = gridDim.x;
 	const uint32_t tlast = ntile - 1;
-	Tile rec1 = tiles[min(blockIdx.x, tlast)];
-	Tile rec2 = tiles[min(blockIdx.x + stride, tlast)];
+	uint32_t i0, i1;                                                // this tile, the next (uniform; TILE_NONE: none)
+	if (claimed) {
+		if (tid == 0) for (int q = 0; q < 3; ++q) { const uint32_t got = atomicAdd(claim_ctr, 1u); s_claim[q == 2 ? 3 : q] = got < ntile ? got : TILE_NONE; }
+		__syncthreads();
+		i0 = s_claim[0]; i1 = s_claim[1];                           // (the third: s_claim[3], read behind the first tile_expand)
+	} else {
+		i0 = blockIdx.x;
+		i1 = i0 + stride < ntile ? i0 + stride : TILE_NONE;
+	}
+	i0 = (uint32_t)__builtin_amdgcn_readfirstlane((int)i0); i1 = (uint32_t)__builtin_amdgcn_readfirstlane((int)i1);
+	Tile rec1 = tiles[min(i0, tlast)];
 	uint32_t nlo, nlen, nseg_, nw_; double na;
 	{
 		const uint32_t L = rec1.end - rec1.beg;
@@ -266,7 +304,7 @@ __global__ __launch_bounds__(BM_NT, 4) void k_bm_tiles(const Tile *tiles, uint32
 		nlo = lo; nlen = act ? hi - lo : 0u; nseg_ = tc.seg; nw_ = (uint32_t)tc.wa | ((uint32_t)tc.wb << 16);
 	}
 	__syncthreads();
-	for (uint32_t ti = blockIdx.x; ti < ntile; ti += stride) {
+	for (uint32_t iter = 0, i2 = TILE_NONE; i0 != TILE_NONE; ++iter, i0 = i1, i1 = claimed ? i2 : (i1 != TILE_NONE && i1 + stride < ntile ? i1 + stride : TILE_NONE)) {
 		const Tile tile = rec1;
 		const uint32_t lo = nlo, len = nlen, myseg = nseg_, myw = nw_; const double a = na;
 		const uint32_t L = tile.end - tile.beg;
@@ -275,9 +313,8 @@ __global__ __launch_bounds__(BM_NT, 4) void k_bm_tiles(const Tile *tiles, uint32
 		lsh = (uint32_t)__builtin_amdgcn_readfirstlane((int)lsh);
 		const int32_t rowid = tile.rowid;
 		const double a_scale = row_scale(ep, rowid);
-		rec1 = rec2;
-		rec2 = tiles[min(ti + 2 * stride, tlast)];
-		const bool has_next = ti + stride < ntile;
+		rec1 = tiles[min(i1, tlast)];
+		const bool has_next = i1 != TILE_NONE;
 		const uint32_t nL = rec1.end - rec1.beg;
 		uint32_t nsh = 0;
 		while ((1u << nsh) < nL) ++nsh;
@@ -287,12 +324,20 @@ __global__ __launch_bounds__(BM_NT, 4) void k_bm_tiles(const Tile *tiles, uint32
 		const TCell ntc = tcells[rec1.first + (nc < rec1.ncells ? nc : 0u)];
 		const int32_t nk = m.acol[nec];
 		na = m.aval[nec];
+		uint32_t claim_pending = TILE_NONE;                         // (once a claim found the list used up no further one is made)
+		if (claimed && tid == 0 && i1 != TILE_NONE) claim_pending = atomicAdd(claim_ctr + cell_pend_zero(), 1u);     // (answered under tile_expand.  The
+		// per-lane zero keeps the address from looking uniform: the compiler then combines the wave's adds into one and reads the answer
+		// with s_waitcnt vmcnt(0) + v_readfirstlane at once -- the atomic's latency and every prefetch in flight drained, per tile)
 
 		uint32_t total, nzc;
 		STAMP_COUNT(10);
 		STAMP(0);
 		tile_expand(X, lsh, tile.ncells, lo, len, a, myseg, myw, flip, &total, &nzc);
 		STAMP(1);
+		if (claimed) {
+			if (tid == 0) s_claim[2 + (iter & 1u)] = claim_pending < ntile ? claim_pending : TILE_NONE;
+			i2 = (uint32_t)__builtin_amdgcn_readfirstlane((int)s_claim[2 + ((iter + 1u) & 1u)]);     // (published a tile ago)
+		}
 		{
 			const uint32_t *bw = bwin + (uint64_t)(uint32_t)nk * nwin1;
 			const uint32_t nlo_ = bw[ntc.wa], nhi_ = bw[ntc.wb];
@@ -581,7 +626,7 @@ __global__ __launch_bounds__(BM_NT, 4) void k_bm_tiles(const Tile *tiles, uint32
 			lds_barrier();                                          // clean: the next cell may set bits
 			STAMP(9);
 		}
-		for (int q = tid; q < NWORD; q += NT) X.bmask[q] = 0ull;     // (every wave is past its last lookup)
+		for (int q = tid; q < NWORD; q += NT) X.bmask[q] = 0ull;     // (every wave is past its last lookup: the cell loop ends with a barrier)
 	}
 #ifdef SPSAMD_STAMPS
 	if (tid == 0 && sk.stamps) for (int i = 0; i < 12; ++i) sk.stamps[(size_t)blockIdx.x * 12 + i] = st_[i];
@@ -816,11 +861,12 @@ void launch_tiles_bm(spsamd_ctx *c, const Heavy &hv, const RowMeta &m, const Emi
 {
 	const uint32_t narrow = ((uint64_t)hv.nnzb + DENSE_R) * 12u < (uint64_t(1) << 32) ? 1u : 0u;
 	const unsigned grid = std::min<unsigned>(hv.ntile, (unsigned)c->num_cu * 2u);
+	uint32_t *claim = hv.tile_ctr ? hv.tile_ctr + (MODE == MODE_STORE ? 1 : 0) : nullptr;       // (one zeroed counter per launch of a call)
 #ifdef SPSAMD_STAMPS
 	SinkParams sk2 = sk;
 	sk2.stamps = c->arena.get<unsigned long long>((size_t)grid * 12);
 	fill_zero(c, sk2.stamps, (size_t)grid * 12 * sizeof(unsigned long long));
-	k_bm_tiles<MODE, false><<<dim3(grid), dim3(BM_NT), 0, c->stream>>>(hv.tb.tiles, hv.ntile, hv.tb.tcells, m, hv.bwin, hv.nwin1, narrow, ep, sk2);
+	k_bm_tiles<MODE, false><<<dim3(grid), dim3(BM_NT), 0, c->stream>>>(hv.tb.tiles, hv.ntile, hv.tb.tcells, m, hv.bwin, hv.nwin1, narrow, ep, sk2, claim);
 	{
 		std::vector<unsigned long long> h((size_t)grid * 12);
 		SPS_HIP(hipMemcpyAsync(h.data(), sk2.stamps, h.size() * 8, hipMemcpyDeviceToHost, c->stream));
@@ -833,8 +879,8 @@ void launch_tiles_bm(spsamd_ctx *c, const Heavy &hv, const RowMeta &m, const Emi
 		fprintf(stderr, "\n");
 	}
 #else
-	if (ep.pattern) k_bm_tiles<MODE, true><<<dim3(grid), dim3(BM_NT), 0, c->stream>>>(hv.tb.tiles, hv.ntile, hv.tb.tcells, m, hv.bwin, hv.nwin1, narrow, ep, sk);
-	else k_bm_tiles<MODE, false><<<dim3(grid), dim3(BM_NT), 0, c->stream>>>(hv.tb.tiles, hv.ntile, hv.tb.tcells, m, hv.bwin, hv.nwin1, narrow, ep, sk);
+	if (ep.pattern) k_bm_tiles<MODE, true><<<dim3(grid), dim3(BM_NT), 0, c->stream>>>(hv.tb.tiles, hv.ntile, hv.tb.tcells, m, hv.bwin, hv.nwin1, narrow, ep, sk, claim);
+	else k_bm_tiles<MODE, false><<<dim3(grid), dim3(BM_NT), 0, c->stream>>>(hv.tb.tiles, hv.ntile, hv.tb.tcells, m, hv.bwin, hv.nwin1, narrow, ep, sk, claim);
 #endif
 	SPS_LAUNCH_CHECK();
 }
@@ -850,11 +896,12 @@ void launch_tiles_hash2(spsamd_ctx *c, const Heavy &hv, const RowMeta &m, const 
 		per_cu2 = nb;
 	}
 	const unsigned grid = std::min<unsigned>(hv.ntile, (unsigned)(c->num_cu * per_cu2));
+	uint32_t *claim = hv.tile_ctr ? hv.tile_ctr + (MODE == MODE_STORE ? 1 : 0) : nullptr;       // (one zeroed counter per launch of a call)
 #ifdef SPSAMD_STAMPS
 	SinkParams sk2 = sk;
 	sk2.stamps = c->arena.get<unsigned long long>((size_t)grid * 12);
 	fill_zero(c, sk2.stamps, (size_t)grid * 12 * sizeof(unsigned long long));
-	k_hash_tiles2<MODE, false><<<dim3(grid), dim3(TILE2_NT), 0, c->stream>>>(hv.tb.tiles, hv.ntile, hv.tb.tcells, m, hv.bwin, hv.nwin1, narrow, ep, sk2);
+	k_hash_tiles2<MODE, false><<<dim3(grid), dim3(TILE2_NT), 0, c->stream>>>(hv.tb.tiles, hv.ntile, hv.tb.tcells, m, hv.bwin, hv.nwin1, narrow, ep, sk2, claim);
 	{
 		std::vector<unsigned long long> h((size_t)grid * 12);
 		SPS_HIP(hipMemcpyAsync(h.data(), sk2.stamps, h.size() * 8, hipMemcpyDeviceToHost, c->stream));
@@ -867,8 +914,8 @@ void launch_tiles_hash2(spsamd_ctx *c, const Heavy &hv, const RowMeta &m, const 
 		fprintf(stderr, "\n");
 	}
 #else
-	if (ep.pattern) k_hash_tiles2<MODE, true><<<dim3(grid), dim3(TILE2_NT), 0, c->stream>>>(hv.tb.tiles, hv.ntile, hv.tb.tcells, m, hv.bwin, hv.nwin1, narrow, ep, sk);
-	else k_hash_tiles2<MODE, false><<<dim3(grid), dim3(TILE2_NT), 0, c->stream>>>(hv.tb.tiles, hv.ntile, hv.tb.tcells, m, hv.bwin, hv.nwin1, narrow, ep, sk);
+	if (ep.pattern) k_hash_tiles2<MODE, true><<<dim3(grid), dim3(TILE2_NT), 0, c->stream>>>(hv.tb.tiles, hv.ntile, hv.tb.tcells, m, hv.bwin, hv.nwin1, narrow, ep, sk, claim);
+	else k_hash_tiles2<MODE, false><<<dim3(grid), dim3(TILE2_NT), 0, c->stream>>>(hv.tb.tiles, hv.ntile, hv.tb.tcells, m, hv.bwin, hv.nwin1, narrow, ep, sk, claim);
 #endif
 	SPS_LAUNCH_CHECK();
 }

@@ -568,6 +568,7 @@ static int64_t build_segments(spsamd_ctx *c, const MultiplyArgs &a, const RowLis
 	fill_u32(c, nseg, 1u, rl.nrows);
 	hv.n = bins.count[8]; hv.tuples = rc.hbc.tuples[8]; hv.coo = a.sink_kind == SPSAMD_SINK_COO;
 	if (hv.n) heavy_prepare(c, hv, bins, m, a.B, m.bptr, SENTINEL_ROWS, nseg, (a.sink_flags & SPSAMD_SINK_ORDERED) != 0, (a.sink_flags & SPSAMD_SINK_EXACT_PATTERN) != 0, pb);
+	if (a.static_walk) hv.tile_ctr = nullptr;
 	uint32_t *segbase = nullptr; int64_t nsegs = 0;
 	if (hv.coo) {
 		int64_t *segbase64 = c->arena.get<int64_t>((size_t)rl.nrows + 1);

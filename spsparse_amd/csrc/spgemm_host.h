@@ -36,6 +36,7 @@ struct Heavy {
 	uint32_t ntile2 = 0, ntcell2 = 0;
 	uint32_t direct_min = 0;
 	int tiles2 = 0;
+	uint32_t *tile_ctr = nullptr;    // claim counters of the tile launches, zeroed with the grouping's counters: [0] COUNT or DIGEST, [1] STORE (null: static walk)
 	uint32_t span_cap = 0;
 	uint32_t alt_cap = 0, alt_span = 0;
 	unsigned long long *alt_cells = nullptr;

@@ -568,10 +568,12 @@ void heavy_prepare(spsamd_ctx *c, Heavy &hv, const Bins &bins, const RowMeta &m,
 	// (a window between dense_min and cell_cap products becomes a dense cell; smaller ones are grouped up to cell_cap)
 	// everything the counting pass accumulates into sits in ONE block, zeroed by one memset (they were eleven)
 	const size_t hn4 = ((size_t)hv.n + 3) & ~(size_t)3;
-	uint32_t *zblock = c->arena.get<uint32_t>(4 * hn4 + 2 * (NCLS + 2) + 4);
-	const size_t zbytes = (4 * hn4 + 2 * (NCLS + 2) + 4) * sizeof(uint32_t);
+	uint32_t *zblock = c->arena.get<uint32_t>(4 * hn4 + 2 * (NCLS + 2) + 4 + 2);
+	const size_t zbytes = (4 * hn4 + 2 * (NCLS + 2) + 4 + 2) * sizeof(uint32_t);
 	unsigned long long *clsprod = reinterpret_cast<unsigned long long *>(zblock + 4 * hn4);
 	unsigned long long *alt_block = clsprod + NCLS + 2;
+	// (the last two words: the claim counters of the tile launches, k_tiles.hip; "tile_walk" 1: none, the static walk)
+	hv.tile_ctr = c->tune.tile_walk == 1 ? nullptr : zblock + 4 * hn4 + 2 * (NCLS + 2) + 4;
 	hv.tb.enabled = !c->tune.no_tiles;
 	// Tile kernel of the hash-class cells: 0 bitmap rank (k_bm_tiles) | 1 first generation | 2 hash tiles v2.
 	// ORDERED runs on the first generation (the variant that exists), EXACT_PATTERN on the bitmap tiles or the hash tiles v2;
