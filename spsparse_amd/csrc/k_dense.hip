@@ -1,5 +1,6 @@
 // k_dense.hip -- dense cells: one output row x ONE column window, f64 accumulator of W columns in LDS.
 #include "spgemm_host.h"
+#include "bank_layout.h"
 
 namespace spsamd {
 
@@ -19,9 +20,13 @@ namespace spsamd {
 // are read as one 12 R-byte piece, and the sums go to the LDS accumulator with ds_add_f64.
 // Occupancy: 16 waves per CU (two 512-thread workgroups, or one of 1024) = 4 per SIMD, so the kernel
 // is held to 128 VGPRs (launch bound 4): a build that needs more silently halves the occupancy.
+// Column wbase + s is accumulated in acc[dense_phys(s)] (bank_layout.h): the bank of a ds_add_f64 comes from the low bits
+// of its slot, and low column bits are skewed.  The scan-out undoes it: group g reads acc[g * 64 + (lane ^ dense_swz(g))].
 // The COUNT launch (first pass of the COO sink) needs no sums: its "accumulator" is one BYTE per column of the window (8 KB
 // instead of 64 KB, a scan-out of W / 16 16-byte words instead of W slots), set with plain byte stores -- every writer
 // stores the same 1 (29.0 -> 28.0 ms on cfg2; the launch is bound by the B reads, not by the accumulator).
+// (Its flag bytes are not swizzled: the remap costs the launch 17 VGPRs, 71 -> 88, which is one wave per SIMD less than its
+// three workgroups per CU need.)
 template <int W, int NT, int MODE, bool PAT>
 __global__ __launch_bounds__(NT, 4) void k_dense(const Cell *cells, uint32_t ncell, const uint32_t *xb, RowMeta m,
 	const uint32_t *widx, uint64_t kstride, uint64_t wstride, uint32_t narrow, EmitParams ep, SinkParams sk, uint32_t *claim_ctr)
@@ -217,7 +222,7 @@ __global__ __launch_bounds__(NT, 4) void k_dense(const Cell *cells, uint32_t nce
 					const double aq = s_caval[q];
 					for (uint32_t t = se.x + tid; t < se.y; t += NT) {
 						const BTup bt = m.btup[t];
-						const uint32_t slot = (uint32_t)bt.col - wbase;
+						const uint32_t slot = dense_phys((uint32_t)bt.col - wbase);
 						acc[slot] = acc[slot] + aq * btup_val(bt);
 					}
 					lds_barrier();
@@ -288,7 +293,8 @@ __global__ __launch_bounds__(NT, 4) void k_dense(const Cell *cells, uint32_t nce
 #pragma unroll
 					for (int u = 0; u < R; ++u) {
 						// a tuple past the segment's end goes to the lane's dump slot: straight-line code, no exec juggling
-						const uint32_t slot = (uint32_t)u < nv_ ? (ABL(ep, 64) ? (piece.w[3 * u] & (W - 1)) : piece.w[3 * u] - wbase) : (uint32_t)W + lane;
+						const uint32_t col = ABL(ep, 64) ? (piece.w[3 * u] & (W - 1)) : piece.w[3 * u] - wbase;
+						const uint32_t slot = (uint32_t)u < nv_ ? (MODE == MODE_COUNT ? col : dense_phys(col)) : (uint32_t)W + lane;
 						if (ABL(ep, 32)) { if (piece.w[3 * u + 2] == 0x7FF12345u) acc[MODE == MODE_COUNT ? 0 : slot] = av_; }          // no LDS accumulate
 						else if (MODE == MODE_COUNT) { if ((uint32_t)u < nv_) ctouch[slot] = (uint8_t)1; }      // structural: touched
 						else {
@@ -392,8 +398,9 @@ __global__ __launch_bounds__(NT, 4) void k_dense(const Cell *cells, uint32_t nce
 #pragma unroll
 		for (int gi = 0; gi < GPW; ++gi) {
 			int grp = wv * GPW + gi;
-			double x = acc[grp * 64 + lane];
-			acc[grp * 64 + lane] = CLEAN;
+			const uint32_t ps = grp * 64 + (lane ^ (uint32_t)__builtin_amdgcn_readfirstlane((int)dense_swz((uint32_t)grp)));     // (a permutation of the group's 64 slots: conflict-free)
+			double x = acc[ps];
+			acc[ps] = CLEAN;
 			bool ok;
 			if (MODE != MODE_COUNT && PAT) {
 				const bool touched = __double_as_longlong(x) != (long long)0x8000000000000000ull;

@@ -2,6 +2,8 @@
 // shared expansion: TileX, tile_expand, tile_lookup).
 #include "spgemm_host.h"
 #include "spgemm_hash.h"
+#include "bank_layout.h"
+#include <type_traits>
 
 namespace spsamd {
 
@@ -238,8 +240,13 @@ __global__ __launch_bounds__(TILE2_NT, 4) void k_hash_tiles2(const Tile *tiles, 
 // a cell (COUNT launch) is just the popcount total.  LDS: bitmap 16 KB + prefix 4 KB + acc 32 KB + columns 16 KB: with no
 // table of keys a cell may hold 4096 products instead of a hash table's 2048 -- and per-cell bookkeeping is what sets the
 // tiles' time (42.9 -> 41.8 ms on cfg2 from the cell size alone).
+// KEY: the launches that need no column order (DIGEST; COUNT without scalek) know a column inside the cell by
+// tile_key(column - first column) (bank_layout.h) instead: bitmap bit, rank and colof all take the key, whose bits 5..11 --
+// the banks of the ds_or and of the two rank lookup reads -- are spread where the column's are skewed.  The column comes
+// back once per output, tile_rel(colof[rank]).  A key lands anywhere in the 256 words of the wave that owns its column's word,
+// so possibly beyond the words of the cell's column range.
 
-template <int MODE, bool PAT>
+template <int MODE, bool PAT, bool KEY>
 __global__ __launch_bounds__(BM_NT, 4) void k_bm_tiles(const Tile *tiles, uint32_t ntile, const TCell *tcells, RowMeta m,
 	const uint32_t *bwin, uint32_t nwin1, uint32_t narrow, EmitParams ep, SinkParams sk, uint32_t *claim_ctr)
 {
@@ -247,6 +254,9 @@ __global__ __launch_bounds__(BM_NT, 4) void k_bm_tiles(const Tile *tiles, uint32
 	constexpr int NWORD = BM_ITEMS / 64;
 	constexpr int MAXST = (BM_MAXOUT / R + (int)TILE_LMAX + 64 + NT - 1) / NT;      // 64-item blocks of one cell per wave
 	constexpr int WPT = BM_WORDS / NT;       // bitmap words per thread in the scan (4)
+	static_assert(!KEY || MODE != MODE_STORE, "the COO store wants rank order to be column order");
+	static_assert(!KEY || BM_WORDS * 64 == (1 << TILE_KEY_BITS), "the keys fill the bitmap");
+	static_assert(!KEY || (BM_WORDS / NW) * 64 == (1 << TILE_KEY_LOW_BITS), "a key stays in the words of its column's wave");
 	__shared__ __attribute__((aligned(16))) unsigned long long bm[BM_WORDS];
 	__shared__ __attribute__((aligned(8))) uint16_t bpre[BM_WORDS];
 	__shared__ double acc[BM_MAXOUT];
@@ -395,7 +405,7 @@ __global__ __launch_bounds__(BM_NT, 4) void k_bm_tiles(const Tile *tiles, uint32
 #pragma unroll
 				for (int u = 0; u < R; ++u) {
 					if ((uint32_t)u < nv) {
-						const uint32_t rel = piece.w[3 * u] - colbase;
+						const uint32_t rel = KEY ? tile_key(piece.w[3 * u] - colbase) : piece.w[3 * u] - colbase;
 						krel[st][u] = rel;
 						if constexpr (MODE != MODE_COUNT) {
 							kval[st][u] = av * __hiloint2double((int)piece.w[3 * u + 2], (int)piece.w[3 * u + 1]);
@@ -419,7 +429,7 @@ __global__ __launch_bounds__(BM_NT, 4) void k_bm_tiles(const Tile *tiles, uint32
 			{
 				unsigned long long wd[WPT];
 #pragma unroll
-				for (int x = 0; x < WPT; ++x) wd[x] = bm[tid * WPT + x];      // (words beyond the cell's range are clean: zero)
+				for (int x = 0; x < WPT; ++x) wd[x] = bm[tid * WPT + x];      // (words no product of the cell set are clean: zero -- beyond the cell's range, or with KEY wherever no key fell)
 				// the next cell's first block(s): lookup and B request issued now, consumed after this cell is done
 				if (c + 1 < tile.ncells) {                              // uniform
 					const uint32_t i2 = X.cellI[c + 2];
@@ -437,7 +447,7 @@ __global__ __launch_bounds__(BM_NT, 4) void k_bm_tiles(const Tile *tiles, uint32
 			const uint32_t inc = wave_inclusive_scan_u32(mine);
 			if (lane == 63) s_wtot[sflip][wv] = inc;
 			{
-				// the thread's WPT prefixes in one 64-bit store (entries past the cell's words are never read)
+				// the thread's WPT prefixes in one 64-bit store (only the entries of words that hold a bit are ever read)
 				static_assert(WPT == 4, "packed prefix store");
 				const uint32_t r0 = inc - mine, r1 = r0 + wcnt[0], r2 = r1 + wcnt[1], r3 = r2 + wcnt[2];
 				reinterpret_cast<uint2 *>(bpre)[tid] = make_uint2(r0 | (r1 << 16), r2 | (r3 << 16));
@@ -458,7 +468,7 @@ __global__ __launch_bounds__(BM_NT, 4) void k_bm_tiles(const Tile *tiles, uint32
 				// structural count: the distinct columns (scalek absent: every column is allowed); clean up and go on
 				if (tid == 0) sk.segcount[seg] = distinct;
 #pragma unroll
-				for (int x = 0; x < WPT; ++x) { const uint32_t w = tid * WPT + x; if (w < nwords && wcnt[x]) bm[w] = 0ull; }
+				for (int x = 0; x < WPT; ++x) { const uint32_t w = tid * WPT + x; if ((KEY || w < nwords) && wcnt[x]) bm[w] = 0ull; }
 				lds_barrier();
 				continue;
 			}
@@ -514,14 +524,14 @@ __global__ __launch_bounds__(BM_NT, 4) void k_bm_tiles(const Tile *tiles, uint32
 						// read and clean in one LDS operation each
 						const double v0 = __longlong_as_double((long long)atomicExch(&acc64[i], 0ull));
 						const double v1 = __longlong_as_double((long long)atomicExch(&acc64[jj], 0ull));
-						note(rel0, v0);
-						if (two) note(rel1, v1);
+						note(KEY ? tile_rel(rel0) : rel0, v0);
+						if (two) note(KEY ? tile_rel(rel1) : rel1, v1);
 					}
 				} else {
 					for (uint32_t base = 0; base < distinct; base += NT) {  // uniform trips: pat_fix_wave wants whole waves
 						const uint32_t i = base + tid;
 						const bool valid = i < distinct;
-						const uint32_t rel = valid ? colof[i] : 0u;
+						const uint32_t rel = valid ? (KEY ? tile_rel(colof[i]) : colof[i]) : 0u;
 						double v = valid ? acc[i] : 0.0;
 						if (valid) acc[i] = 0.0;
 						v = pat_fix_wave(valid && !(fabs(v) > pthr), v, (int32_t)(colbase + rel), m, tile.beg, tile.end);
@@ -546,7 +556,7 @@ __global__ __launch_bounds__(BM_NT, 4) void k_bm_tiles(const Tile *tiles, uint32
 					while (word) {
 						const uint32_t bit = (uint32_t)__builtin_ctzll(word);
 						word &= word - 1ull;
-						if (col_allowed(ep, (int32_t)(colbase + (w << 6) + bit))) ++cnt;
+						if (col_allowed(ep, (int32_t)(colbase + (w << 6) + bit))) ++cnt;     // (bit = column: launch_tiles_bm never runs a KEY instantiation with scalek)
 					}
 				}
 				uint32_t tot;
@@ -866,7 +876,7 @@ void launch_tiles_bm(spsamd_ctx *c, const Heavy &hv, const RowMeta &m, const Emi
 	SinkParams sk2 = sk;
 	sk2.stamps = c->arena.get<unsigned long long>((size_t)grid * 12);
 	fill_zero(c, sk2.stamps, (size_t)grid * 12 * sizeof(unsigned long long));
-	k_bm_tiles<MODE, false><<<dim3(grid), dim3(BM_NT), 0, c->stream>>>(hv.tb.tiles, hv.ntile, hv.tb.tcells, m, hv.bwin, hv.nwin1, narrow, ep, sk2, claim);
+	k_bm_tiles<MODE, false, MODE == MODE_DIGEST><<<dim3(grid), dim3(BM_NT), 0, c->stream>>>(hv.tb.tiles, hv.ntile, hv.tb.tcells, m, hv.bwin, hv.nwin1, narrow, ep, sk2, claim);
 	{
 		std::vector<unsigned long long> h((size_t)grid * 12);
 		SPS_HIP(hipMemcpyAsync(h.data(), sk2.stamps, h.size() * 8, hipMemcpyDeviceToHost, c->stream));
@@ -879,8 +889,14 @@ void launch_tiles_bm(spsamd_ctx *c, const Heavy &hv, const RowMeta &m, const Emi
 		fprintf(stderr, "\n");
 	}
 #else
-	if (ep.pattern) k_bm_tiles<MODE, true><<<dim3(grid), dim3(BM_NT), 0, c->stream>>>(hv.tb.tiles, hv.ntile, hv.tb.tcells, m, hv.bwin, hv.nwin1, narrow, ep, sk, claim);
-	else k_bm_tiles<MODE, false><<<dim3(grid), dim3(BM_NT), 0, c->stream>>>(hv.tb.tiles, hv.ntile, hv.tb.tcells, m, hv.bwin, hv.nwin1, narrow, ep, sk, claim);
+	// keyed columns where the launch needs no column order: DIGEST, and COUNT unless scalek has it walk the bitmap by column
+	auto go = [&](auto pat, auto key) {
+		k_bm_tiles<MODE, decltype(pat)::value, decltype(key)::value><<<dim3(grid), dim3(BM_NT), 0, c->stream>>>(hv.tb.tiles, hv.ntile, hv.tb.tcells, m, hv.bwin, hv.nwin1, narrow, ep, sk, claim);
+	};
+	auto go_pat = [&](auto key) { if (ep.pattern) go(std::true_type{}, key); else go(std::false_type{}, key); };
+	if constexpr (MODE == MODE_DIGEST) go_pat(std::true_type{});
+	else if constexpr (MODE == MODE_COUNT) { if (ep.sk_pos) go_pat(std::false_type{}); else go_pat(std::true_type{}); }
+	else go_pat(std::false_type{});
 #endif
 	SPS_LAUNCH_CHECK();
 }
