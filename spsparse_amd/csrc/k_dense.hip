@@ -68,9 +68,7 @@ __global__ __launch_bounds__(NT, 4) void k_dense(const Cell *cells, uint32_t nce
 	PatAcc pat; pat_init(pat);
 	if (tid == 0) pat_reset(&s_pat);
 	uint32_t flip = 0;
-#ifdef SPSAMD_STAMPS
-	unsigned long long st_[12] = {}; unsigned long long st_t = clock64();
-#endif
+	STAMP_BEGIN();
 
 	// Cells are ordered by (window, descending products) and dealt with a grid stride, so the
 	// workgroups are on the same few column windows of B at any time and every workgroup gets a
@@ -459,9 +457,7 @@ __global__ __launch_bounds__(NT, 4) void k_dense(const Cell *cells, uint32_t nce
 		if (PAT) { lds_barrier(); if (tid == 0) pat_reset(&s_pat); }     // every thread has read the cell's record
 		if (claimed && tid == 0) s_claim[2 + ((iter + 1u) & 1u)] = tried < 8u ? claim_resolve(claim_pending) : NONE;
 	}
-#ifdef SPSAMD_STAMPS
-	if (tid == 0 && sk.stamps) for (int i = 0; i < 12; ++i) sk.stamps[(size_t)blockIdx.x * 12 + i] = st_[i];
-#endif
+	STAMP_FLUSH();
 	if (MODE == MODE_DIGEST) digest_flush<NT>(sk.digest, d_cnt, d_hash, d_sum, s_u64, s_f64);
 }
 
@@ -484,39 +480,21 @@ void launch_heavy_dense(spsamd_ctx *c, const Heavy &hv, const RowMeta &m0, const
 	const uint32_t *widx = hv.bwin;
 	uint64_t kstride = hv.nwin1, wstride = 1;
 	if (hv.wptr) { widx = hv.wptr; kstride = 1; wstride = hv.nrowb; m.btup = hv.btw; }
-	const uint32_t narrow = ((uint64_t)hv.nnzb + DENSE_R) * 12u < (uint64_t(1) << 32) ? 1u : 0u;    // 32-bit byte offsets into B suffice
-	if (hv.W == 8192) {
-		unsigned grid = std::min<unsigned>(hv.ncell[CLS_DENSE], (unsigned)c->num_cu * (MODE == MODE_COUNT ? 3u : 2u));
-		// (COUNT's 20 KB of LDS allow more than two workgroups per CU.  One list for all XCDs: 28.0 / 31.2 / 33.2 ms at two / three / four -- more
-		// cells in flight, fewer L2 hits; with the claimed XCD parts: 23.5 / 20.8 / 20.9)
-		if (grid >= 64) grid &= ~7u;
-#ifdef SPSAMD_STAMPS
-		SinkParams sk2 = sk;
-		sk2.stamps = c->arena.get<unsigned long long>((size_t)grid * 12);
-		fill_zero(c, sk2.stamps, (size_t)grid * 12 * sizeof(unsigned long long));
-		k_dense<8192, 512, MODE, false><<<dim3(grid), dim3(512), 0, c->stream>>>(hv.cells[CLS_DENSE], hv.ncell[CLS_DENSE], hv.xb[CLS_DENSE], m, widx, kstride, wstride, narrow, ep, sk2, claim);
-		{
-			std::vector<unsigned long long> h((size_t)grid * 12);
-			SPS_HIP(hipMemcpyAsync(h.data(), sk2.stamps, h.size() * 8, hipMemcpyDeviceToHost, c->stream));
-			SPS_HIP(hipStreamSynchronize(c->stream));
-			double sum[12] = {}; double mx = 0;
-			for (unsigned g = 0; g < grid; ++g) { double t = 0; for (int i = 0; i < 12; ++i) { sum[i] += (double)h[(size_t)g * 12 + i]; if (i < 8) t += (double)h[(size_t)g * 12 + i]; } mx = std::max(mx, t); }
-			static const char *nm[12] = {"pre-B1", "B1wait", "compact", "B2wait", "tables", "steps", "B3wait", "scanout", "cells", "chunks", "steps#", "-"};
-			fprintf(stderr, "k_dense stamps (mean cycles per workgroup; max total %.3g):", mx);
-			for (int i = 0; i < 11; ++i) fprintf(stderr, " %s %.4g", nm[i], sum[i] / grid);
-			fprintf(stderr, "\n");
-		}
-		return;
-#endif
-		if (ep.pattern) k_dense<8192, 512, MODE, true><<<dim3(grid), dim3(512), 0, c->stream>>>(hv.cells[CLS_DENSE], hv.ncell[CLS_DENSE], hv.xb[CLS_DENSE], m, widx, kstride, wstride, narrow, ep, sk, claim);
-		else k_dense<8192, 512, MODE, false><<<dim3(grid), dim3(512), 0, c->stream>>>(hv.cells[CLS_DENSE], hv.ncell[CLS_DENSE], hv.xb[CLS_DENSE], m, widx, kstride, wstride, narrow, ep, sk, claim);
-	} else {
-		unsigned grid = std::min<unsigned>(hv.ncell[CLS_DENSE], (unsigned)c->num_cu);
-		if (grid >= 64) grid &= ~7u;
-		if (ep.pattern) k_dense<16384, 1024, MODE, true><<<dim3(grid), dim3(1024), 0, c->stream>>>(hv.cells[CLS_DENSE], hv.ncell[CLS_DENSE], hv.xb[CLS_DENSE], m, widx, kstride, wstride, narrow, ep, sk, claim);
-		else k_dense<16384, 1024, MODE, false><<<dim3(grid), dim3(1024), 0, c->stream>>>(hv.cells[CLS_DENSE], hv.ncell[CLS_DENSE], hv.xb[CLS_DENSE], m, widx, kstride, wstride, narrow, ep, sk, claim);
-	}
+	const uint32_t narrow = hv.narrow();
+	unsigned grid = std::min<unsigned>(hv.ncell[CLS_DENSE], (unsigned)c->num_cu * (hv.W != 8192 ? 1u : (MODE == MODE_COUNT ? 3u : 2u)));
+	// (W = 8192: COUNT's 20 KB of LDS allow more than two workgroups per CU.  One list for all XCDs: 28.0 / 31.2 / 33.2 ms at two / three / four -- more
+	// cells in flight, fewer L2 hits; with the claimed XCD parts: 23.5 / 20.8 / 20.9)
+	if (grid >= 64) grid &= ~7u;
+	const SinkParams &sks = stamps_sink(c, sk, grid);
+	auto go = [&](auto w, auto nt, auto pat) {
+		k_dense<decltype(w)::value, decltype(nt)::value, MODE, decltype(pat)::value><<<dim3(grid), dim3(decltype(nt)::value), 0, c->stream>>>(hv.cells[CLS_DENSE], hv.ncell[CLS_DENSE], hv.xb[CLS_DENSE], m, widx, kstride, wstride, narrow, ep, sks, claim);
+	};
+	auto go_pat = [&](auto w, auto nt) { if (ep.pattern) go(w, nt, std::true_type{}); else go(w, nt, std::false_type{}); };
+	if (hv.W == 8192) go_pat(std::integral_constant<int, 8192>{}, std::integral_constant<int, 512>{});
+	else go_pat(std::integral_constant<int, 16384>{}, std::integral_constant<int, 1024>{});
 	SPS_LAUNCH_CHECK();
+	static const char *const nm[11] = {"pre-B1", "B1wait", "compact", "B2wait", "tables", "steps", "B3wait", "scanout", "cells", "chunks", "steps#"};
+	stamps_report(c, sks, grid, "k_dense", nm, 11, 8);
 }
 
 // Window-major copy of B (see k_wm_counts): built once the cell grouping has shown that dense cells exist.

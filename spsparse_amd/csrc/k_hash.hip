@@ -139,70 +139,28 @@ __global__ __launch_bounds__(TILE_NT) void k_hash_tiles(const Tile *tiles, uint3
 	if (tid == 0) pat_reset(&s_pat);
 	DigestAcc dacc{0, 0, 0.0};
 	uint32_t flip = 0;
-#ifdef SPSAMD_STAMPS
-	unsigned long long st_[12] = {}; unsigned long long st_t = clock64();
-#endif
-
-	const uint32_t stride = gridDim.x;
-	const uint32_t tlast = ntile - 1;
-	// three-stage branch-free prefetch: tile record -> (A tuple, cell window range) -> B segment bounds
-	Tile rec1 = tiles[min(blockIdx.x, tlast)];
-	Tile rec2 = tiles[min(blockIdx.x + stride, tlast)];
-	uint32_t nlo, nlen, nseg_; double na;
-	{
-		const uint32_t L = rec1.end - rec1.beg;
-		uint32_t lsh = 0;
-		while ((1u << lsh) < L) ++lsh;
-		const uint32_t c = tid >> lsh, ei = tid & ((1u << lsh) - 1u);
-		const bool act = c < rec1.ncells && ei < L;
-		const uint32_t ec = rec1.beg + (ei < L ? ei : 0u);
-		const TCell tc = tcells[rec1.first + (c < rec1.ncells ? c : 0u)];
-		const uint32_t *bw = bwin + (uint64_t)m.acol[ec] * nwin1;
-		const uint32_t lo = bw[tc.wa], hi = bw[tc.wb];
-		na = m.aval[ec];
-		nlo = lo; nlen = act ? hi - lo : 0u; nseg_ = tc.seg;
-	}
-	for (uint32_t ti = blockIdx.x; ti < ntile; ti += stride) {
-		const Tile tile = rec1;
-		const uint32_t lo = nlo, len = nlen, myseg = nseg_; const double a = na;
-		const uint32_t L = tile.end - tile.beg;
-		uint32_t lsh = 0;
-		while ((1u << lsh) < L) ++lsh;
-		const uint32_t myc = tid >> lsh, myei = tid & ((1u << lsh) - 1u);
-		// stage A / B for the next tile
-		rec1 = rec2;
-		rec2 = tiles[min(ti + 2 * stride, tlast)];
-		const bool has_next = ti + stride < ntile;
-		const uint32_t nL = rec1.end - rec1.beg;
-		uint32_t nsh = 0;
-		while ((1u << nsh) < nL) ++nsh;
-		const uint32_t nc = tid >> nsh, nei = tid & ((1u << nsh) - 1u);
-		const bool nact = has_next && nc < rec1.ncells && nei < nL;
-		const uint32_t nec = rec1.beg + (nei < nL ? nei : 0u);
-		const TCell ntc = tcells[rec1.first + (nc < rec1.ncells ? nc : 0u)];
-		const int32_t nk = m.acol[nec];
-		na = m.aval[nec];
+	STAMP_BEGIN();
+	TileWalk<BoundsRowMajor, false> walk;
+	for (walk.begin(tiles, ntile, tcells, m.acol, m.aval, BoundsRowMajor{bwin, nwin1}); walk.more(); walk.next()) {
+		const TileTake t = walk.take();
+		const Tile &tile = t.tile;
+		const uint32_t myc = tid >> t.lsh, myei = tid & ((1u << t.lsh) - 1u);
 
 		STAMP_COUNT(8);
 		STAMP(0);
 		lds_barrier();                                              // previous tile fully emitted
 		STAMP(1);
 		uint32_t total, nzc, ex;
-		expand_load(X, lo, len, a, &total, &nzc, flip, &ex);
+		expand_load(X, t.lo, t.len, t.a, &total, &nzc, flip, &ex);
 		if (myei == 0 && myc < tile.ncells) cellP[myc] = ex;       // first product of each cell
 		if (tid == 0) { cellP[tile.ncells] = total; s_nocc = 0; }
 		// segment ids of the cells of this tile: thread (c, 0) holds cell c's
-		const uint32_t seg_of_mine = myseg;
+		const uint32_t seg_of_mine = t.seg;
 		STAMP(2);
 		if (total) expand_batch(X, 0, total, nzc);
 		else lds_barrier();
 		STAMP(3);
-		// stage C: B segment bounds of the next tile
-		{
-			const uint32_t *bw = bwin + (uint64_t)nk * nwin1;
-			const uint32_t nlo_ = bw[ntc.wa], nhi_ = bw[ntc.wb];
-			nlo = nlo_; nlen = nact ? nhi_ - nlo_ : 0u; nseg_ = ntc.seg;
-		}
+		walk.expanded();
 		for (uint32_t c = 0; c < tile.ncells; ++c) {
 			STAMP_COUNT(9);
 			STAMP(0);
@@ -238,9 +196,7 @@ __global__ __launch_bounds__(TILE_NT) void k_hash_tiles(const Tile *tiles, uint3
 			lds_barrier();
 		}
 	}
-#ifdef SPSAMD_STAMPS
-	if (tid == 0 && sk.stamps) for (int i = 0; i < 12; ++i) sk.stamps[(size_t)blockIdx.x * 12 + i] = st_[i];
-#endif
+	STAMP_FLUSH();
 	if (MODE == MODE_DIGEST) digest_flush<NT>(sk.digest, dacc.cnt, dacc.hash, dacc.sum, s_u64, s_f64);
 }
 
@@ -249,13 +205,7 @@ static void launch_hash(spsamd_ctx *c, const Cell *cells, uint32_t ncell, const 
 	uint32_t nwin1, const EmitParams &ep, const SinkParams &sk)
 {
 	if (!ncell) return;
-	static int per_cu = 0;                     // resident workgroups per CU of this instantiation
-	if (!per_cu) {
-		int nb = 0;
-		if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&nb, k_hash<T, NT, MODE, WINDOWED, false>, NT, 0) != hipSuccess || nb < 1) nb = 1;
-		per_cu = nb;
-	}
-	unsigned grid = std::min<unsigned>(ncell, (unsigned)(c->num_cu * per_cu));
+	unsigned grid = std::min<unsigned>(ncell, (unsigned)(c->num_cu * resident_per_cu<&k_hash<T, NT, MODE, WINDOWED, false>>(NT)));
 	if (grid >= 64) grid &= ~7u;               // multiple of 8: the XCD-aware walk
 	if (ep.pattern) k_hash<T, NT, MODE, WINDOWED, true><<<dim3(grid), dim3(NT), 0, c->stream>>>(cells, ncell, xb, m, bwin, nwin1, ep, sk);
 	else k_hash<T, NT, MODE, WINDOWED, false><<<dim3(grid), dim3(NT), 0, c->stream>>>(cells, ncell, xb, m, bwin, nwin1, ep, sk);
@@ -282,33 +232,12 @@ void launch_hash_windowed(spsamd_ctx *c, const Heavy &hv, const RowMeta &m, cons
 template <int MODE>
 void launch_tiles_v1(spsamd_ctx *c, const Heavy &hv, const RowMeta &m, const EmitParams &ep, const SinkParams &sk)
 {
-	static int per_cu = 0;
-	if (!per_cu) {
-		int nb = 0;
-		if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&nb, k_hash_tiles<MODE>, TILE_NT, 0) != hipSuccess || nb < 1) nb = 1;
-		per_cu = nb;
-	}
-	unsigned grid = std::min<unsigned>(hv.ntile, (unsigned)(c->num_cu * per_cu));
-#ifdef SPSAMD_STAMPS
-	SinkParams sk2 = sk;
-	sk2.stamps = c->arena.get<unsigned long long>((size_t)grid * 12);
-	fill_zero(c, sk2.stamps, (size_t)grid * 12 * sizeof(unsigned long long));
-	k_hash_tiles<MODE><<<dim3(grid), dim3(TILE_NT), 0, c->stream>>>(hv.tb.tiles, hv.ntile, hv.tb.tcells, m, hv.bwin, hv.nwin1, ep, sk2);
-	{
-		std::vector<unsigned long long> h((size_t)grid * 12);
-		SPS_HIP(hipMemcpyAsync(h.data(), sk2.stamps, h.size() * 8, hipMemcpyDeviceToHost, c->stream));
-		SPS_HIP(hipStreamSynchronize(c->stream));
-		double sum[12] = {};
-		for (unsigned g = 0; g < grid; ++g) for (int i = 0; i < 12; ++i) sum[i] += (double)h[(size_t)g * 12 + i];
-		static const char *nm[12] = {"pre", "Bwait", "expand_load", "expand_batch", "products", "Bwait2", "segbcast", "emit", "tiles", "cells", "-", "-"};
-		fprintf(stderr, "k_hash_tiles stamps (mean cycles per workgroup, grid %u):", grid);
-		for (int i = 0; i < 10; ++i) fprintf(stderr, " %s %.4g", nm[i], sum[i] / grid);
-		fprintf(stderr, "\n");
-	}
-#else
-	k_hash_tiles<MODE><<<dim3(grid), dim3(TILE_NT), 0, c->stream>>>(hv.tb.tiles, hv.ntile, hv.tb.tcells, m, hv.bwin, hv.nwin1, ep, sk);
-#endif
+	const unsigned grid = std::min<unsigned>(hv.ntile, (unsigned)(c->num_cu * resident_per_cu<&k_hash_tiles<MODE>>(TILE_NT)));
+	const SinkParams &sks = stamps_sink(c, sk, grid);
+	k_hash_tiles<MODE><<<dim3(grid), dim3(TILE_NT), 0, c->stream>>>(hv.tb.tiles, hv.ntile, hv.tb.tcells, m, hv.bwin, hv.nwin1, ep, sks);
 	SPS_LAUNCH_CHECK();
+	static const char *const nm[10] = {"pre", "Bwait", "expand_load", "expand_batch", "products", "Bwait2", "segbcast", "emit", "tiles", "cells"};
+	stamps_report(c, sks, grid, "k_hash_tiles", nm, 10);
 }
 
 template void launch_mid<MODE_COUNT>(spsamd_ctx *, const Bins &, const MidCells &, const RowMeta &, const EmitParams &, const SinkParams &);

@@ -7,8 +7,6 @@
 
 namespace spsamd {
 
-constexpr uint32_t TILE_NONE = 0xFFFFFFFFu;          // no (further) tile for this workgroup
-
 // ---- hash tiles: cells are ranges [wa, wb) of sparse column windows, accumulated in the LDS hash table ----
 // Insertion: the R first probes of a lane are in flight together (ds_cmpswap with return), the rare collisions are
 // then walked one by one; the values follow with ds_add_f64; the newly occupied slots of a step are appended to the
@@ -33,7 +31,7 @@ __global__ __launch_bounds__(TILE2_NT, 4) void k_hash_tiles2(const Tile *tiles, 
 	__shared__ PatCell s_pat;
 	__shared__ unsigned long long s_u64[2 * NW];
 	__shared__ double s_f64[NW];
-	__shared__ uint32_t s_claim[4];
+	__shared__ uint32_t s_claim[4];                                  // (the walk's, where the tiles are claimed)
 
 	const unsigned tid = threadIdx.x, lane = lane_id();
 	const unsigned wv = (unsigned)__builtin_amdgcn_readfirstlane((int)wave_id());
@@ -46,91 +44,20 @@ __global__ __launch_bounds__(TILE2_NT, 4) void k_hash_tiles2(const Tile *tiles, 
 	DigestAcc dacc{0, 0, 0.0};
 	uint32_t flip = 0;
 	const char *bbase = reinterpret_cast<const char *>(m.btup);
-#ifdef SPSAMD_STAMPS
-	unsigned long long st_[12] = {}; unsigned long long st_t = clock64();
-#endif
-
-	// Two ways to deal the (window-major) tile list.  STATIC (claim_ctr null): a grid stride.  CLAIMED: a workgroup's next tile
-	// is atomicAdd(claim_ctr, 1), so a workgroup that becomes resident late -- the LDS of its CU still held by another
-	// stream's kernel -- simply takes fewer tiles instead of owning 1 / grid of the list (static, the kernel runs as long as
-	// its last-started workgroup).  Thread 0 claims: three tiles before the loop, then one per tile at the top of the tile,
-	// with tile_expand for the answer to arrive (no register is free to hold it across the cell loop: a spill there is a wait
-	// for the atomic on the spot).  It publishes the answer in s_claim[2 + (iter & 1)] behind tile_expand; the other waves read
-	// it a tile later, behind the next tile_expand's barriers, as the tile after the next.
-	const bool claimed = claim_ctr != nullptr;
-	const uint32_t stride = gridDim.x;
-	const uint32_t tlast = ntile - 1;
-	uint32_t i0, i1;                                                // this tile, the next (uniform; TILE_NONE: none)
-	if (claimed) {
-		if (tid == 0) for (int q = 0; q < 3; ++q) { const uint32_t got = atomicAdd(claim_ctr, 1u); s_claim[q == 2 ? 3 : q] = got < ntile ? got : TILE_NONE; }
-		__syncthreads();
-		i0 = s_claim[0]; i1 = s_claim[1];                           // (the third: s_claim[3], read behind the first tile_expand)
-	} else {
-		i0 = blockIdx.x;
-		i1 = i0 + stride < ntile ? i0 + stride : TILE_NONE;
-	}
-	i0 = (uint32_t)__builtin_amdgcn_readfirstlane((int)i0); i1 = (uint32_t)__builtin_amdgcn_readfirstlane((int)i1);
-	// branch-free prefetch: (the next tile's record, read where its turn comes ->) A tuple, cell window range -> B segment bounds
-	Tile rec1 = tiles[min(i0, tlast)];
-	uint32_t nlo, nlen, nseg_, nw_; double na;
-	{
-		const uint32_t L = rec1.end - rec1.beg;
-		uint32_t lsh = 0;
-		while ((1u << lsh) < L) ++lsh;
-		const uint32_t c = tid >> lsh, ei = tid & ((1u << lsh) - 1u);
-		const bool act = c < rec1.ncells && ei < L;
-		const uint32_t ec = rec1.beg + (ei < L ? ei : 0u);
-		const TCell tc = tcells[rec1.first + (c < rec1.ncells ? c : 0u)];
-		const uint32_t *bw = bwin + (uint64_t)(uint32_t)m.acol[ec] * nwin1;
-		const uint32_t lo = bw[tc.wa], hi = bw[tc.wb];
-		na = m.aval[ec];
-		nlo = lo; nlen = act ? hi - lo : 0u; nseg_ = tc.seg; nw_ = (uint32_t)tc.wa | ((uint32_t)tc.wb << 16);
-	}
-	__syncthreads();
-	for (uint32_t iter = 0, i2 = TILE_NONE; i0 != TILE_NONE; ++iter, i0 = i1, i1 = claimed ? i2 : (i1 != TILE_NONE && i1 + stride < ntile ? i1 + stride : TILE_NONE)) {
-		const Tile tile = rec1;
-		const uint32_t lo = nlo, len = nlen, myseg = nseg_, myw = nw_; const double a = na;
-		const uint32_t L = tile.end - tile.beg;
-		uint32_t lsh = 0;
-		while ((1u << lsh) < L) ++lsh;
-		lsh = (uint32_t)__builtin_amdgcn_readfirstlane((int)lsh);
+	STAMP_BEGIN();
+	TileWalk<BoundsRowMajor, true> walk;
+	for (walk.begin(tiles, ntile, tcells, m.acol, m.aval, BoundsRowMajor{bwin, nwin1}, claim_ctr, s_claim); walk.more(); walk.next()) {
+		const TileTake t = walk.take();
+		const Tile &tile = t.tile;
 		const int32_t rowid = tile.rowid;
-		// stage A / B for the next tile
-		rec1 = tiles[min(i1, tlast)];
-		const bool has_next = i1 != TILE_NONE;
-		const uint32_t nL = rec1.end - rec1.beg;
-		uint32_t nsh = 0;
-		while ((1u << nsh) < nL) ++nsh;
-		const uint32_t nc = tid >> nsh, nei = tid & ((1u << nsh) - 1u);
-		const bool nact = has_next && nc < rec1.ncells && nei < nL;
-		const uint32_t nec = rec1.beg + (nei < nL ? nei : 0u);
-		const TCell ntc = tcells[rec1.first + (nc < rec1.ncells ? nc : 0u)];
-		const int32_t nk = m.acol[nec];
-		na = m.aval[nec];
-		uint32_t claim_pending = TILE_NONE;                         // (once a claim found the list used up no further one is made)
-		if (claimed && tid == 0 && i1 != TILE_NONE) claim_pending = atomicAdd(claim_ctr + cell_pend_zero(), 1u);     // (answered under tile_expand.  The
-		// per-lane zero keeps the address from looking uniform: the compiler then combines the wave's adds into one and reads the answer
-		// with s_waitcnt vmcnt(0) + v_readfirstlane at once -- the atomic's latency and every prefetch in flight drained, per tile)
 
 		uint32_t total, nzc;
 		STAMP_COUNT(8);
 		STAMP(0);
-		tile_expand(X, lsh, tile.ncells, lo, len, a, myseg, myw, flip, &total, &nzc);
+		tile_expand(X, t.lsh, tile.ncells, t.lo, t.len, t.a, t.seg, t.w, flip, &total, &nzc);
 		STAMP(1);
-		if (claimed) {
-			if (tid == 0) s_claim[2 + (iter & 1u)] = claim_pending < ntile ? claim_pending : TILE_NONE;
-			i2 = (uint32_t)__builtin_amdgcn_readfirstlane((int)s_claim[2 + ((iter + 1u) & 1u)]);     // (published a tile ago)
-		}
-		// stage C: B segment bounds of the next tile
-		{
-			const uint32_t *bw = bwin + (uint64_t)(uint32_t)nk * nwin1;
-			const uint32_t nlo_ = bw[ntc.wa], nhi_ = bw[ntc.wb];
-			nlo = nlo_; nlen = nact ? nhi_ - nlo_ : 0u; nseg_ = ntc.seg; nw_ = (uint32_t)ntc.wa | ((uint32_t)ntc.wb << 16);
-		}
-		if (total == 0 || nzc == 0) {                               // uniform; cannot happen for real tiles
-			if (MODE != MODE_DIGEST) for (uint32_t c = tid; c < tile.ncells; c += NT) { if (MODE == MODE_COUNT) sk.segcount[X.cellseg[c]] = 0; else sk.segactual[X.cellseg[c]] = 0; }
-			continue;
-		}
+		walk.expanded();
+		if (total == 0 || nzc == 0) { X.template empty_tile<MODE>(tile.ncells, sk); continue; }     // uniform
 		TileTab<NWORD / 64> tab;
 		tile_tables(X, tab);
 
@@ -224,9 +151,7 @@ __global__ __launch_bounds__(TILE2_NT, 4) void k_hash_tiles2(const Tile *tiles, 
 		}
 		for (int q = tid; q < NWORD; q += NT) X.bmask[q] = 0ull;     // (every wave is past its last lookup: the cell loop ends with a barrier)
 	}
-#ifdef SPSAMD_STAMPS
-	if (tid == 0 && sk.stamps) for (int i = 0; i < 12; ++i) sk.stamps[(size_t)blockIdx.x * 12 + i] = st_[i];
-#endif
+	STAMP_FLUSH();
 	if (MODE == MODE_DIGEST) digest_flush<NT>(sk.digest, dacc.cnt, dacc.hash, dacc.sum, s_u64, s_f64);
 }
 
@@ -281,11 +206,11 @@ __global__ __launch_bounds__(BM_NT, 4) void k_bm_tiles(const Tile *tiles, uint32
 	if (PAT && tid == 0) pat_reset(&s_pat);
 	uint32_t flip = 0, sflip = 0;
 	const char *bbase = reinterpret_cast<const char *>(m.btup);
-#ifdef SPSAMD_STAMPS
-	unsigned long long st_[12] = {}; unsigned long long st_t = clock64();
-#endif
-
-	const bool claimed = claim_ctr != nullptr;                      // (the walk: k_hash_tiles2 above)
+	STAMP_BEGIN();
+	// The walk, written out: what TileWalk<BoundsRowMajor, true> (spgemm_dev.h, where it is explained) does for the other three
+	// tile kernels.  This kernel, the benchmark's longest, sits at 128 VGPRs and ran 0.1 ms of 28.5 slower through the struct
+	// (profiles/walk/); on this text its instructions are the ones it had before.  A change to the walk is made in both places.
+	const bool claimed = claim_ctr != nullptr;
 	const uint32_t stride = gridDim.x;
 	const uint32_t tlast = ntile - 1;
 	uint32_t i0, i1;                                                // this tile, the next (uniform; TILE_NONE: none)
@@ -353,10 +278,7 @@ __global__ __launch_bounds__(BM_NT, 4) void k_bm_tiles(const Tile *tiles, uint32
 			const uint32_t nlo_ = bw[ntc.wa], nhi_ = bw[ntc.wb];
 			nlo = nlo_; nlen = nact ? nhi_ - nlo_ : 0u; nseg_ = ntc.seg; nw_ = (uint32_t)ntc.wa | ((uint32_t)ntc.wb << 16);
 		}
-		if (total == 0 || nzc == 0) {                               // uniform; cannot happen for real tiles
-			if (MODE != MODE_DIGEST) for (uint32_t c = tid; c < tile.ncells; c += NT) { if (MODE == MODE_COUNT) sk.segcount[X.cellseg[c]] = 0; else sk.segactual[X.cellseg[c]] = 0; }
-			continue;
-		}
+		if (total == 0 || nzc == 0) { X.template empty_tile<MODE>(tile.ncells, sk); continue; }     // uniform
 		TileTab<NWORD / 64> tab;
 		tile_tables(X, tab);
 
@@ -539,7 +461,7 @@ __global__ __launch_bounds__(BM_NT, 4) void k_bm_tiles(const Tile *tiles, uint32
 					}
 				}
 				d_cnt += cnt; d_sum += vs; d_hash += rh;
-				if (sk.row_nnz) {
+				if (sk.row_nnz) {                                       // (row_stats_add, spelled out for the same reason as the walk)
 					const unsigned long long rc = wave_reduce_sum(cnt); const double rs = wave_reduce_sum(vs);
 					rh = wave_reduce_sum(rh);
 					if (lane == 0 && rc) { atomicAdd((unsigned long long *)&sk.row_nnz[rowid], rc); atomicAdd(&sk.row_sum[rowid], rs); atomicAdd(&sk.row_hash[rowid], rh); }
@@ -638,9 +560,7 @@ __global__ __launch_bounds__(BM_NT, 4) void k_bm_tiles(const Tile *tiles, uint32
 		}
 		for (int q = tid; q < NWORD; q += NT) X.bmask[q] = 0ull;     // (every wave is past its last lookup: the cell loop ends with a barrier)
 	}
-#ifdef SPSAMD_STAMPS
-	if (tid == 0 && sk.stamps) for (int i = 0; i < 12; ++i) sk.stamps[(size_t)blockIdx.x * 12 + i] = st_[i];
-#endif
+	STAMP_FLUSH();
 	if (MODE == MODE_DIGEST) digest_flush<NT>(sk.digest, d_cnt, d_hash, d_sum, s_u64, s_f64);
 }
 
@@ -680,59 +600,17 @@ __global__ __launch_bounds__(NT, 4) void k_direct_tiles(const Tile *tiles, uint3
 	unsigned long long d_cnt = 0, d_hash = 0; double d_sum = 0;
 	uint32_t flip = 0;
 	const char *bbase = reinterpret_cast<const char *>(m.btup);
-
-	const uint32_t stride = gridDim.x;
-	const uint32_t tlast = ntile - 1;
-	Tile rec1 = tiles[min(blockIdx.x, tlast)];
-	Tile rec2 = tiles[min(blockIdx.x + stride, tlast)];
-	uint32_t nlo, nlen, nseg_, nw_; double na;
-	{
-		const uint32_t L = rec1.end - rec1.beg;
-		uint32_t lsh = 0;
-		while ((1u << lsh) < L) ++lsh;
-		const uint32_t c = tid >> lsh, ei = tid & ((1u << lsh) - 1u);
-		const bool act = c < rec1.ncells && ei < L;
-		const uint32_t ec = rec1.beg + (ei < L ? ei : 0u);
-		const TCell tc = tcells[rec1.first + (c < rec1.ncells ? c : 0u)];
-		const uint32_t *bw = wptr + (uint64_t)tc.wa * nrowb + (uint32_t)m.acol[ec];
-		const uint32_t lo = bw[0], hi = bw[1];
-		na = m.aval[ec];
-		nlo = lo; nlen = act ? hi - lo : 0u; nseg_ = tc.seg; nw_ = tc.wa;
-	}
-	__syncthreads();
-	for (uint32_t ti = blockIdx.x; ti < ntile; ti += stride) {
-		const Tile tile = rec1;
-		const uint32_t lo = nlo, len = nlen, myseg = nseg_, myw = nw_; const double a = na;
-		const uint32_t L = tile.end - tile.beg;
-		uint32_t lsh = 0;
-		while ((1u << lsh) < L) ++lsh;
-		lsh = (uint32_t)__builtin_amdgcn_readfirstlane((int)lsh);
+	TileWalk<BoundsWindowMajor, false> walk;
+	for (walk.begin(tiles, ntile, tcells, m.acol, m.aval, BoundsWindowMajor{wptr, nrowb}); walk.more(); walk.next()) {
+		const TileTake t = walk.take();
+		const Tile &tile = t.tile;
 		const int32_t rowid = tile.rowid;
 		const double a_scale = row_scale(ep, rowid);
-		rec1 = rec2;
-		rec2 = tiles[min(ti + 2 * stride, tlast)];
-		const bool has_next = ti + stride < ntile;
-		const uint32_t nL = rec1.end - rec1.beg;
-		uint32_t nsh = 0;
-		while ((1u << nsh) < nL) ++nsh;
-		const uint32_t nc = tid >> nsh, nei = tid & ((1u << nsh) - 1u);
-		const bool nact = has_next && nc < rec1.ncells && nei < nL;
-		const uint32_t nec = rec1.beg + (nei < nL ? nei : 0u);
-		const TCell ntc = tcells[rec1.first + (nc < rec1.ncells ? nc : 0u)];
-		const int32_t nk = m.acol[nec];
-		na = m.aval[nec];
 
 		uint32_t total, nzc;
-		tile_expand(X, lsh, tile.ncells, lo, len, a, myseg, myw, flip, &total, &nzc);
-		{
-			const uint32_t *bw = wptr + (uint64_t)ntc.wa * nrowb + (uint32_t)nk;
-			const uint32_t nlo_ = bw[0], nhi_ = bw[1];
-			nlo = nlo_; nlen = nact ? nhi_ - nlo_ : 0u; nseg_ = ntc.seg; nw_ = ntc.wa;
-		}
-		if (total == 0 || nzc == 0) {                               // uniform; cannot happen for real tiles
-			if (MODE != MODE_DIGEST) for (uint32_t c = tid; c < tile.ncells; c += NT) { if (MODE == MODE_COUNT) sk.segcount[X.cellseg[c]] = 0; else sk.segactual[X.cellseg[c]] = 0; }
-			continue;
-		}
+		tile_expand(X, t.lsh, tile.ncells, t.lo, t.len, t.a, t.seg, t.w, flip, &total, &nzc);
+		walk.expanded();
+		if (total == 0 || nzc == 0) { X.template empty_tile<MODE>(tile.ncells, sk); continue; }     // uniform
 		TileTab<NWORD / 64> tab;
 		tile_tables(X, tab);
 		// first block of cell 0, prefetched like every later cell's (requested while the previous cell is claimed)
@@ -814,11 +692,7 @@ __global__ __launch_bounds__(NT, 4) void k_direct_tiles(const Tile *tiles, uint3
 			}
 			if constexpr (MODE == MODE_DIGEST) {
 				d_cnt += mycount; d_sum += mysum; d_hash += myhash;
-				if (sk.row_nnz) {
-					const unsigned long long rc = wave_reduce_sum((unsigned long long)mycount); const double rs = wave_reduce_sum(mysum);
-					myhash = wave_reduce_sum(myhash);
-					if (lane == 0 && rc) { atomicAdd((unsigned long long *)&sk.row_nnz[rowid], rc); atomicAdd(&sk.row_sum[rowid], rs); atomicAdd(&sk.row_hash[rowid], myhash); }
-				}
+				row_stats_add(sk, rowid, mycount, mysum, myhash);
 				lds_barrier();                                      // claims done before the next cell accumulates
 			} else if constexpr (MODE == MODE_COUNT) {
 				const uint32_t wc = (uint32_t)wave_reduce_sum((unsigned long long)mycount);
@@ -869,71 +743,31 @@ __global__ __launch_bounds__(NT, 4) void k_direct_tiles(const Tile *tiles, uint3
 template <int MODE>
 void launch_tiles_bm(spsamd_ctx *c, const Heavy &hv, const RowMeta &m, const EmitParams &ep, const SinkParams &sk)
 {
-	const uint32_t narrow = ((uint64_t)hv.nnzb + DENSE_R) * 12u < (uint64_t(1) << 32) ? 1u : 0u;
 	const unsigned grid = std::min<unsigned>(hv.ntile, (unsigned)c->num_cu * 2u);
-	uint32_t *claim = hv.tile_ctr ? hv.tile_ctr + (MODE == MODE_STORE ? 1 : 0) : nullptr;       // (one zeroed counter per launch of a call)
-#ifdef SPSAMD_STAMPS
-	SinkParams sk2 = sk;
-	sk2.stamps = c->arena.get<unsigned long long>((size_t)grid * 12);
-	fill_zero(c, sk2.stamps, (size_t)grid * 12 * sizeof(unsigned long long));
-	k_bm_tiles<MODE, false, MODE == MODE_DIGEST><<<dim3(grid), dim3(BM_NT), 0, c->stream>>>(hv.tb.tiles, hv.ntile, hv.tb.tcells, m, hv.bwin, hv.nwin1, narrow, ep, sk2, claim);
-	{
-		std::vector<unsigned long long> h((size_t)grid * 12);
-		SPS_HIP(hipMemcpyAsync(h.data(), sk2.stamps, h.size() * 8, hipMemcpyDeviceToHost, c->stream));
-		SPS_HIP(hipStreamSynchronize(c->stream));
-		double sum[12] = {};
-		for (unsigned g = 0; g < grid; ++g) for (int i = 0; i < 12; ++i) sum[i] += (double)h[(size_t)g * 12 + i];
-		static const char *nm[12] = {"pre", "expand", "bits", "B", "scan", "B", "rank-add", "B", "emit", "B", "tiles", "cells"};
-		fprintf(stderr, "k_bm_tiles stamps (mean cycles per workgroup, grid %u):", grid);
-		for (int i = 0; i < 12; ++i) fprintf(stderr, " %s %.4g", nm[i], sum[i] / grid);
-		fprintf(stderr, "\n");
-	}
-#else
+	const SinkParams &sks = stamps_sink(c, sk, grid);
 	// keyed columns where the launch needs no column order: DIGEST, and COUNT unless scalek has it walk the bitmap by column
 	auto go = [&](auto pat, auto key) {
-		k_bm_tiles<MODE, decltype(pat)::value, decltype(key)::value><<<dim3(grid), dim3(BM_NT), 0, c->stream>>>(hv.tb.tiles, hv.ntile, hv.tb.tcells, m, hv.bwin, hv.nwin1, narrow, ep, sk, claim);
+		k_bm_tiles<MODE, decltype(pat)::value, decltype(key)::value><<<dim3(grid), dim3(BM_NT), 0, c->stream>>>(hv.tb.tiles, hv.ntile, hv.tb.tcells, m, hv.bwin, hv.nwin1, hv.narrow(), ep, sks, hv.tile_claim<MODE>());
 	};
 	auto go_pat = [&](auto key) { if (ep.pattern) go(std::true_type{}, key); else go(std::false_type{}, key); };
 	if constexpr (MODE == MODE_DIGEST) go_pat(std::true_type{});
 	else if constexpr (MODE == MODE_COUNT) { if (ep.sk_pos) go_pat(std::false_type{}); else go_pat(std::true_type{}); }
 	else go_pat(std::false_type{});
-#endif
 	SPS_LAUNCH_CHECK();
+	static const char *const nm[12] = {"pre", "expand", "bits", "B", "scan", "B", "rank-add", "B", "emit", "B", "tiles", "cells"};
+	stamps_report(c, sks, grid, "k_bm_tiles", nm, 12);
 }
 
 template <int MODE>
 void launch_tiles_hash2(spsamd_ctx *c, const Heavy &hv, const RowMeta &m, const EmitParams &ep, const SinkParams &sk)
 {
-	const uint32_t narrow = ((uint64_t)hv.nnzb + DENSE_R) * 12u < (uint64_t(1) << 32) ? 1u : 0u;
-	static int per_cu2 = 0;
-	if (!per_cu2) {
-		int nb = 0;
-		if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&nb, k_hash_tiles2<MODE, false>, TILE2_NT, 0) != hipSuccess || nb < 1) nb = 1;
-		per_cu2 = nb;
-	}
-	const unsigned grid = std::min<unsigned>(hv.ntile, (unsigned)(c->num_cu * per_cu2));
-	uint32_t *claim = hv.tile_ctr ? hv.tile_ctr + (MODE == MODE_STORE ? 1 : 0) : nullptr;       // (one zeroed counter per launch of a call)
-#ifdef SPSAMD_STAMPS
-	SinkParams sk2 = sk;
-	sk2.stamps = c->arena.get<unsigned long long>((size_t)grid * 12);
-	fill_zero(c, sk2.stamps, (size_t)grid * 12 * sizeof(unsigned long long));
-	k_hash_tiles2<MODE, false><<<dim3(grid), dim3(TILE2_NT), 0, c->stream>>>(hv.tb.tiles, hv.ntile, hv.tb.tcells, m, hv.bwin, hv.nwin1, narrow, ep, sk2, claim);
-	{
-		std::vector<unsigned long long> h((size_t)grid * 12);
-		SPS_HIP(hipMemcpyAsync(h.data(), sk2.stamps, h.size() * 8, hipMemcpyDeviceToHost, c->stream));
-		SPS_HIP(hipStreamSynchronize(c->stream));
-		double sum[12] = {};
-		for (unsigned g = 0; g < grid; ++g) for (int i = 0; i < 12; ++i) sum[i] += (double)h[(size_t)g * 12 + i];
-		static const char *nm[12] = {"pre", "expand", "tables+pf", "insert", "Bwait", "pf-next", "emit", "Bwait2", "tiles", "cells", "-", "-"};
-		fprintf(stderr, "k_hash_tiles2 stamps (mean cycles per workgroup, grid %u):", grid);
-		for (int i = 0; i < 10; ++i) fprintf(stderr, " %s %.4g", nm[i], sum[i] / grid);
-		fprintf(stderr, "\n");
-	}
-#else
-	if (ep.pattern) k_hash_tiles2<MODE, true><<<dim3(grid), dim3(TILE2_NT), 0, c->stream>>>(hv.tb.tiles, hv.ntile, hv.tb.tcells, m, hv.bwin, hv.nwin1, narrow, ep, sk, claim);
-	else k_hash_tiles2<MODE, false><<<dim3(grid), dim3(TILE2_NT), 0, c->stream>>>(hv.tb.tiles, hv.ntile, hv.tb.tcells, m, hv.bwin, hv.nwin1, narrow, ep, sk, claim);
-#endif
+	const unsigned grid = std::min<unsigned>(hv.ntile, (unsigned)(c->num_cu * resident_per_cu<&k_hash_tiles2<MODE, false>>(TILE2_NT)));
+	const SinkParams &sks = stamps_sink(c, sk, grid);
+	if (ep.pattern) k_hash_tiles2<MODE, true><<<dim3(grid), dim3(TILE2_NT), 0, c->stream>>>(hv.tb.tiles, hv.ntile, hv.tb.tcells, m, hv.bwin, hv.nwin1, hv.narrow(), ep, sks, hv.tile_claim<MODE>());
+	else k_hash_tiles2<MODE, false><<<dim3(grid), dim3(TILE2_NT), 0, c->stream>>>(hv.tb.tiles, hv.ntile, hv.tb.tcells, m, hv.bwin, hv.nwin1, hv.narrow(), ep, sks, hv.tile_claim<MODE>());
 	SPS_LAUNCH_CHECK();
+	static const char *const nm[10] = {"pre", "expand", "tables+pf", "insert", "Bwait", "pf-next", "emit", "Bwait2", "tiles", "cells"};
+	stamps_report(c, sks, grid, "k_hash_tiles2", nm, 10);
 }
 
 template <int MODE>
@@ -941,13 +775,12 @@ void launch_tiles_direct(spsamd_ctx *c, const Heavy &hv, const RowMeta &m, const
 {
 	RowMeta m2 = m;
 	m2.btup = hv.btw;
-	const uint32_t narrow = ((uint64_t)hv.nnzb + DENSE_R) * 12u < (uint64_t(1) << 32) ? 1u : 0u;
 	if (hv.W == 8192) {
 		const unsigned grid = std::min<unsigned>(hv.ntile2, (unsigned)c->num_cu * 2u);
-		k_direct_tiles<8192, 512, MODE><<<dim3(grid), dim3(512), 0, c->stream>>>(hv.tb2.tiles, hv.ntile2, hv.tb2.tcells, m2, hv.wptr, hv.nrowb, narrow, ep, sk);
+		k_direct_tiles<8192, 512, MODE><<<dim3(grid), dim3(512), 0, c->stream>>>(hv.tb2.tiles, hv.ntile2, hv.tb2.tcells, m2, hv.wptr, hv.nrowb, hv.narrow(), ep, sk);
 	} else {
 		const unsigned grid = std::min<unsigned>(hv.ntile2, (unsigned)c->num_cu);
-		k_direct_tiles<16384, 1024, MODE><<<dim3(grid), dim3(1024), 0, c->stream>>>(hv.tb2.tiles, hv.ntile2, hv.tb2.tcells, m2, hv.wptr, hv.nrowb, narrow, ep, sk);
+		k_direct_tiles<16384, 1024, MODE><<<dim3(grid), dim3(1024), 0, c->stream>>>(hv.tb2.tiles, hv.ntile2, hv.tb2.tcells, m2, hv.wptr, hv.nrowb, hv.narrow(), ep, sk);
 	}
 	SPS_LAUNCH_CHECK();
 }

@@ -69,12 +69,17 @@ struct SinkParams {
 #endif
 };
 
+constexpr int STAMP_COLS = 12;          // stamp words per workgroup (a kernel keeps them in st_[]; stamps_sink / stamps_report, spgemm_host.h)
 #ifdef SPSAMD_STAMPS
 #define STAMP(i) do { const unsigned long long now_ = clock64(); st_[i] += now_ - st_t; st_t = now_; } while (0)
+#define STAMP_BEGIN() unsigned long long st_[STAMP_COLS] = {}; unsigned long long st_t = clock64()
 #define STAMP_COUNT(i) (++st_[i])
+#define STAMP_FLUSH() do { if (threadIdx.x == 0 && sk.stamps) for (int i_ = 0; i_ < STAMP_COLS; ++i_) sk.stamps[(size_t)blockIdx.x * STAMP_COLS + i_] = st_[i_]; } while (0)
 #else
+#define STAMP_BEGIN() do { } while (0)
 #define STAMP(i) do { } while (0)
 #define STAMP_COUNT(i) do { } while (0)
+#define STAMP_FLUSH() do { } while (0)
 #endif
 
 // (BTup, one B tuple as the numeric kernels read it -- column and value side by side, 12 bytes -- is defined in internal.h)
@@ -244,6 +249,16 @@ __device__ __forceinline__ void digest_flush(DigestSlot *slots, unsigned long lo
 		}
 	}
 	__syncthreads();
+}
+
+// Row statistics of a heavy-row cell (DIGEST, where the caller asked for them): every wave adds what its lanes emitted
+// of row `rowid` -- tuples, value sum, index hash -- to the row's words.  Every lane of the wave must call it.
+__device__ __forceinline__ void row_stats_add(const SinkParams &sk, int32_t rowid, unsigned long long cnt, double sum, unsigned long long hash)
+{
+	if (!sk.row_nnz) return;
+	const unsigned long long rc = wave_reduce_sum(cnt); const double rs = wave_reduce_sum(sum);
+	hash = wave_reduce_sum(hash);
+	if (lane_id() == 0 && rc) { atomicAdd((unsigned long long *)&sk.row_nnz[rowid], rc); atomicAdd(&sk.row_sum[rowid], rs); atomicAdd(&sk.row_hash[rowid], hash); }
 }
 
 // ====================================================================== hash cells (LDS hash accumulator)
@@ -533,6 +548,138 @@ struct TileBases { uint32_t *ntc, *ntl, *tcbase, *tlbase; TCell *tcells; Tile *t
 struct TileKinds { TileBases k[2]; uint32_t direct_min; uint32_t span_cap; uint32_t long_cap; uint32_t long_dense_min; uint32_t tile_cap;
 	uint32_t alt_cap, alt_span; unsigned long long *alt_cells; };   // alt_*: (counting pass) the tile cells another cap / span would give   // long_*: cell_cap / dense_min of the rows too long for tiles    // span_cap: most windows one tile cell may cover (0: any)
 
+// ====================================================================== the walk over a tile list
+//
+// Every tile kernel (k_hash_tiles, k_hash_tiles2, k_bm_tiles, k_direct_tiles) is a loop of persistent workgroups over a
+// (window-major) tile list.  Three of them run it through TileWalk (k_bm_tiles has the same walk written out in its body:
+// at the VGPR limit it measured slower through the struct, k_tiles.hip):
+//     for (w.begin(..); w.more(); w.next()) { const TileTake t = w.take(); <expand t> w.expanded(); <the tile's cells> }
+// The walk deals the tiles and keeps the next tile's inputs in flight: a branch-free prefetch (indices clamped to valid
+// tiles / tuples, results masked afterwards -- a load inside a conditional is waited for at the join) in three stages,
+//     the next tile's record -> (A) A tuple and (B) cell of thread (cell tid >> lsh, tuple tid & (2^lsh - 1))
+//                            -> (C) bounds of the B segment that A tuple selects in that cell.
+// take() hands out the current tile with this thread's segment and starts A / B for the next; expanded(), called behind
+// the expansion's barriers, runs C.
+//
+// Two ways to deal the list.  STATIC (no claim counter): a grid stride.  CLAIMED: a workgroup's next tile is
+// atomicAdd(ctr, 1), so a workgroup that becomes resident late -- the LDS of its CU still held by another stream's
+// kernel -- simply takes fewer tiles instead of owning 1 / grid of the list (static, the kernel runs as long as its
+// last-started workgroup).  Thread 0 claims: three tiles in begin(), then one per tile in take(), with the expansion for
+// the answer to arrive (no register is free to hold it across the cell loop: a spill there is a wait for the atomic on
+// the spot).  expanded() publishes the answer in s_claim[2 + (iter & 1)]; the other waves read it a tile later, behind
+// the next expansion's barriers, as the tile after the next.  CLAIM = false (k_hash_tiles, k_direct_tiles: never a
+// counter) compiles all of that away; s_claim is then null, otherwise four words of LDS.
+constexpr uint32_t TILE_NONE = 0xFFFFFFFFu;          // no (further) tile for this workgroup
+
+// B segment [lo, hi) of A column k in cell tc, and the cell's window word for TileX::cellw: B's window index row-major
+// (bwin[k][window]; cells are window ranges [wa, wb)) ...
+struct BoundsRowMajor {
+	const uint32_t *bwin; uint32_t nwin1;
+	__device__ __forceinline__ void operator()(uint32_t k, const TCell &tc, uint32_t *lo, uint32_t *hi, uint32_t *w) const
+	{
+		const uint32_t *bw = bwin + (uint64_t)k * nwin1;
+		*lo = bw[tc.wa]; *hi = bw[tc.wb]; *w = (uint32_t)tc.wa | ((uint32_t)tc.wb << 16);
+	}
+};
+// ... or window-major (wptr[window][k], the row pointer of B's window-major copy; direct cells are ONE window)
+struct BoundsWindowMajor {
+	const uint32_t *wptr; uint64_t nrowb;
+	__device__ __forceinline__ void operator()(uint32_t k, const TCell &tc, uint32_t *lo, uint32_t *hi, uint32_t *w) const
+	{
+		const uint32_t *bw = wptr + (uint64_t)tc.wa * nrowb + k;
+		*lo = bw[0]; *hi = bw[1]; *w = tc.wa;
+	}
+};
+
+// What take() hands out: the tile, log2 of its A tuples rounded up to a power of two, and this thread's seed for the expansion
+struct TileTake { Tile tile; uint32_t lsh, lo, len, seg, w; double a; };
+
+template <class BOUNDS, bool CLAIM>
+struct TileWalk {
+	const Tile *tiles; const TCell *tcells; const int32_t *acol; const double *aval;
+	BOUNDS bounds;
+	uint32_t ntile, tlast, stride, *ctr, *s_claim;  // (tlast, stride: ntile - 1 and the grid)
+	uint32_t i0, i1, i2, iter;                      // this tile, the next, the one after (uniform; TILE_NONE: none)
+	Tile rec;                                       // the record read ahead
+	uint32_t lo, len, seg, w; double a;             // ... and this thread's seed for it
+	TCell ntc; int32_t nk; bool nact;               // take() .. expanded(): stage A / B of the next tile
+	uint32_t pending;                               // ... and the claim under way
+
+	__device__ __forceinline__ bool claimed() const { return CLAIM && ctr != nullptr; }
+
+	// log2 of the tile's A tuples rounded up to a power of two: thread t is (cell t >> lsh, tuple t & (2^lsh - 1))
+	static __device__ __forceinline__ uint32_t lsh_of(const Tile &tile)
+	{
+		const uint32_t L = tile.end - tile.beg;
+		uint32_t lsh = 0;
+		while ((1u << lsh) < L) ++lsh;
+		return lsh;
+	}
+	__device__ __forceinline__ void stage_ab(bool has)
+	{
+		const uint32_t tid = threadIdx.x, L = rec.end - rec.beg, sh = lsh_of(rec);
+		const uint32_t c = tid >> sh, ei = tid & ((1u << sh) - 1u);
+		nact = has && c < rec.ncells && ei < L;
+		const uint32_t ec = rec.beg + (ei < L ? ei : 0u);
+		ntc = tcells[rec.first + (c < rec.ncells ? c : 0u)];
+		nk = acol[ec];
+		a = aval[ec];
+	}
+	__device__ __forceinline__ void stage_c()
+	{
+		uint32_t hi;
+		bounds((uint32_t)nk, ntc, &lo, &hi, &w);
+		len = nact ? hi - lo : 0u; seg = ntc.seg;
+	}
+
+	__device__ __forceinline__ void begin(const Tile *tiles_, uint32_t ntile_, const TCell *tcells_, const int32_t *acol_, const double *aval_,
+		const BOUNDS &bounds_, uint32_t *ctr_ = nullptr, uint32_t *s_claim_ = nullptr)
+	{
+		tiles = tiles_; ntile = ntile_; tcells = tcells_; acol = acol_; aval = aval_; bounds = bounds_; ctr = ctr_; s_claim = s_claim_;
+		tlast = ntile - 1u; stride = gridDim.x;
+		if (claimed()) {
+			if (threadIdx.x == 0) for (int q = 0; q < 3; ++q) { const uint32_t got = atomicAdd(ctr, 1u); s_claim[q == 2 ? 3 : q] = got < ntile ? got : TILE_NONE; }
+			__syncthreads();
+			i0 = s_claim[0]; i1 = s_claim[1];                           // (the third: s_claim[3], read behind the first expansion)
+		} else {
+			i0 = blockIdx.x;
+			i1 = i0 + stride < ntile ? i0 + stride : TILE_NONE;
+		}
+		i0 = (uint32_t)__builtin_amdgcn_readfirstlane((int)i0); i1 = (uint32_t)__builtin_amdgcn_readfirstlane((int)i1);
+		i2 = TILE_NONE; iter = 0;
+		rec = tiles[min(i0, tlast)];
+		stage_ab(true);
+		stage_c();
+		__syncthreads();
+	}
+	__device__ __forceinline__ bool more() const { return i0 != TILE_NONE; }
+	__device__ __forceinline__ void next()
+	{
+		++iter; i0 = i1;
+		i1 = claimed() ? i2 : (i1 != TILE_NONE && i1 + stride < ntile ? i1 + stride : TILE_NONE);
+	}
+
+	__device__ __forceinline__ TileTake take()
+	{
+		const TileTake t{rec, (uint32_t)__builtin_amdgcn_readfirstlane((int)lsh_of(rec)), lo, len, seg, w, a};
+		rec = tiles[min(i1, tlast)];
+		stage_ab(i1 != TILE_NONE);
+		pending = TILE_NONE;                                        // (once a claim found the list used up no further one is made)
+		if (claimed() && threadIdx.x == 0 && i1 != TILE_NONE) pending = atomicAdd(ctr + cell_pend_zero(), 1u);     // (answered under the expansion.  The
+		// per-lane zero keeps the address from looking uniform: the compiler then combines the wave's adds into one and reads the answer
+		// with s_waitcnt vmcnt(0) + v_readfirstlane at once -- the atomic's latency and every prefetch in flight drained, per tile)
+		return t;
+	}
+	__device__ __forceinline__ void expanded()
+	{
+		if (claimed()) {
+			if (threadIdx.x == 0) s_claim[2 + (iter & 1u)] = pending < ntile ? pending : TILE_NONE;
+			i2 = (uint32_t)__builtin_amdgcn_readfirstlane((int)s_claim[2 + ((iter + 1u) & 1u)]);     // (published a tile ago)
+		}
+		stage_c();
+	}
+};
+
 // ====================================================================== tiles, second generation
 //
 // A tile is up to 16 cells of ONE heavy row with few A tuples (L <= 256) that share one expansion
@@ -552,6 +699,13 @@ struct TileX {
 	uint32_t cellI[TILE_MAXCELLS + 1];       // first item of every cell (+ end), multiples of 64
 	uint32_t cellseg[TILE_MAXCELLS];         // output segment id of every cell
 	uint32_t cellw[TILE_MAXCELLS];           // wa | wb << 16 of every cell
+
+	// A tile whose expansion found no item (cannot happen for real tiles): its cells' segments are empty.
+	template <int MODE>
+	__device__ __forceinline__ void empty_tile(uint32_t ncells, const SinkParams &sk) const
+	{
+		if (MODE != MODE_DIGEST) for (uint32_t c = threadIdx.x; c < ncells; c += NT) { if (MODE == MODE_COUNT) sk.segcount[cellseg[c]] = 0; else sk.segactual[cellseg[c]] = 0; }
+	}
 };
 
 // Contains two barriers (B1 after the per-wave totals, B2 after the tables are written); the first one also

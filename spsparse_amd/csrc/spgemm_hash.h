@@ -211,11 +211,7 @@ __device__ __forceinline__ void hash_emit(uint32_t nocc, int32_t rowid, uint32_t
 			}
 		}
 		d.cnt += cnt; d.sum += vs; d.hash += rh;
-		if (sk.row_nnz) {
-			unsigned long long rc = wave_reduce_sum(cnt); double rs = wave_reduce_sum(vs);
-			rh = wave_reduce_sum(rh);
-			if (lane_id() == 0 && rc) { atomicAdd((unsigned long long *)&sk.row_nnz[rowid], rc); atomicAdd(&sk.row_sum[rowid], rs); atomicAdd(&sk.row_hash[rowid], rh); }
-		}
+		row_stats_add(sk, rowid, cnt, vs, rh);
 	} else {
 		// surviving columns -> sorted -> emitted in order, cleaning the table.  Where the cell's column
 		// range and the position in the occupied list fit one 32-bit word (they do for every cell of a

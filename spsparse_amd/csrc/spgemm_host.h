@@ -47,6 +47,11 @@ struct Heavy {
 	BTup *btw = nullptr;             // ... and tuples
 	uint64_t nrowb = 0;
 	uint32_t nnzb = 0;
+
+	// 32-bit byte offsets into B's tuples suffice (fetch_piece): always, short of 3.5e8 tuples
+	uint32_t narrow() const { return ((uint64_t)nnzb + DENSE_R) * 12u < (uint64_t(1) << 32) ? 1u : 0u; }
+	// the claim counter of a tile launch (one zeroed counter per launch of a call; null: static walk)
+	template <int MODE> uint32_t *tile_claim() const { return tile_ctr ? tile_ctr + (MODE == MODE_STORE ? 1 : 0) : nullptr; }
 };
 
 static inline TileKinds tile_kinds(const Heavy &hv)
@@ -62,6 +67,53 @@ static inline float elapsed(hipEvent_t a, hipEvent_t b)
 	SPS_HIP(hipEventElapsedTime(&ms, a, b));
 	return ms;
 }
+
+// Resident workgroups per CU of KERNEL at nt threads and no dynamic LDS (asked once per kernel)
+template <auto KERNEL>
+static inline int resident_per_cu(int nt)
+{
+	static int per_cu = 0;
+	if (!per_cu) {
+		int nb = 0;
+		if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&nb, KERNEL, nt, 0) != hipSuccess || nb < 1) nb = 1;
+		per_cu = nb;
+	}
+	return per_cu;
+}
+
+// Diagnostic builds (-DSPSAMD_STAMPS): the kernels that keep per-phase cycle counters (STAMP, spgemm_dev.h) are launched with
+// stamps_sink's copy of their sink, which has a zeroed block of STAMP_COLS counters per workgroup; stamps_report, behind the
+// launch, prints the means over the workgroups of the first ncol columns under their names, and with nmax > 0 the largest
+// sum of one workgroup's first nmax columns (its total).  In every other build: the sink itself, and nothing.
+#ifdef SPSAMD_STAMPS
+static inline SinkParams stamps_sink(spsamd_ctx *c, const SinkParams &sk, unsigned grid)
+{
+	SinkParams sk2 = sk;
+	sk2.stamps = c->arena.get<unsigned long long>((size_t)grid * STAMP_COLS);
+	fill_zero(c, sk2.stamps, (size_t)grid * STAMP_COLS * sizeof(unsigned long long));
+	return sk2;
+}
+static inline void stamps_report(spsamd_ctx *c, const SinkParams &sk2, unsigned grid, const char *kernel, const char *const *nm, int ncol, int nmax = 0)
+{
+	std::vector<unsigned long long> h((size_t)grid * STAMP_COLS);
+	SPS_HIP(hipMemcpyAsync(h.data(), sk2.stamps, h.size() * 8, hipMemcpyDeviceToHost, c->stream));
+	SPS_HIP(hipStreamSynchronize(c->stream));
+	double sum[STAMP_COLS] = {}, mx = 0;
+	for (unsigned g = 0; g < grid; ++g) {
+		double t = 0;
+		for (int i = 0; i < STAMP_COLS; ++i) { sum[i] += (double)h[(size_t)g * STAMP_COLS + i]; if (i < nmax) t += (double)h[(size_t)g * STAMP_COLS + i]; }
+		mx = std::max(mx, t);
+	}
+	fprintf(stderr, "%s stamps (mean cycles per workgroup, grid %u", kernel, grid);
+	if (nmax) fprintf(stderr, "; max total %.3g", mx);
+	fprintf(stderr, "):");
+	for (int i = 0; i < ncol; ++i) fprintf(stderr, " %s %.4g", nm[i], sum[i] / grid);
+	fprintf(stderr, "\n");
+}
+#else
+static inline const SinkParams &stamps_sink(spsamd_ctx *, const SinkParams &sk, unsigned) { return sk; }
+static inline void stamps_report(spsamd_ctx *, const SinkParams &, unsigned, const char *, const char *const *, int, int = 0) { }
+#endif
 
 // ---- launchers (explicitly instantiated for MODE_COUNT / MODE_STORE / MODE_DIGEST in the file named)
 template <int MODE> void launch_light(spsamd_ctx *c, const Bins &b, const RowMeta &m, const EmitParams &ep, const SinkParams &sk);             // k_light.hip

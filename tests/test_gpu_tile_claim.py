@@ -1,10 +1,12 @@
 """The heavy rows' tiles claimed from a counter (k_bm_tiles, k_hash_tiles2): same tuples, same digest as the oracle, call
-after call, with the static walk (the `tile_walk` knob) beside it.  GPU only.
+after call, with the static walk (the `tile_walk` knob) beside it; the same walk dealing statically in the first-generation
+and the direct tiles (k_hash_tiles, k_direct_tiles) at the same list lengths.  GPU only.
 
 The few-tile products are built so that every heavy row is exactly one tile (80 A tuples, 5120 products spread over four
-column windows: two or three cells); the symbolic phase's trace line confirms the count.  A claim can go wrong where the
-list is shorter than the grid (most workgroups claim nothing), where it holds one tile, and where it is one longer than
-the grid (one workgroup's second claim is the last tile, every other second claim finds the list used up)."""
+column windows: two or three cells, four in the first generation, whose cells hold 2048 products); the symbolic phase's
+trace line confirms the count.  A claim can go wrong where the list is shorter than the grid (most workgroups claim
+nothing), where it holds one tile, and where it is one longer than the grid (one workgroup's second claim is the last
+tile, every other second claim finds the list used up)."""
 import functools
 import re
 
@@ -88,17 +90,28 @@ def _one_tile_rows(nrows):
 
 
 def _tile_grid():
+    return 2 * _cus()
+
+
+def _cus():
     import torch
-    return 2 * torch.cuda.get_device_properties(0).multi_processor_count
+    return torch.cuda.get_device_properties(0).multi_processor_count
 
 
-@pytest.mark.parametrize("scheme", [3, 2], ids=["bitmap", "hash2"])
-@pytest.mark.parametrize("ntiles", ["one", "few", "grid_plus_one"])
+# grid_plus_one: one more than k_bm_tiles' grid (two workgroups a CU).  The hash kernels size their grids by the workgroups
+# resident on a CU -- at 512 threads never more than four, eight waves a SIMD -- so "beyond_every_grid" is a list longer
+# than any of the grids: there every kernel's static walk goes on to a second tile.
+_FEW = {"one": lambda: 1, "few": lambda: 7, "grid_plus_one": lambda: _tile_grid() + 1, "beyond_every_grid": lambda: 8 * _cus() + 1}
+_FEW_IDS = list(_FEW)
+
+
+@pytest.mark.parametrize("scheme", [3, 2, 1], ids=["bitmap", "hash2", "hash1"])
+@pytest.mark.parametrize("ntiles", _FEW_IDS)
 def test_few_tiles(ctx, capfd, ntiles, scheme):
     """One tile, fewer tiles than workgroups, one tile more than workgroups: the COO result tuple by tuple against the
-    oracle, the digest against the digest of those tuples, both tile kernels."""
+    oracle, the digest against the digest of those tuples, the three tile kernels of the hash-class cells."""
     from spsparse_amd import capi
-    nrows = {"one": 1, "few": 7, "grid_plus_one": _tile_grid() + 1}[ntiles]
+    nrows = _FEW[ntiles]()
     A, B, want = _one_tile_rows(nrows)
     with _Knobs(ctx, {"tiles_v1": scheme, "trace": 1}):
         capfd.readouterr()
@@ -111,6 +124,25 @@ def test_few_tiles(ctx, capfd, ntiles, scheme):
     assert got[3].rows_heavy == nrows and got[3].products_tiles == got[3].products == nrows * L_TILE * B_LEN
     _check_tuples(got, want)
     _check_digest(d, got)                                       # ... of the stored tuples
+    _check_digest(d, want)
+
+
+@pytest.mark.parametrize("ntiles", _FEW_IDS)
+def test_few_direct_tiles(ctx, ntiles):
+    """The same three list lengths for the direct tiles: with direct cells from 1024 products on, each of a row's four
+    windows (1280 products) is a direct cell and the row one direct tile."""
+    from spsparse_amd import capi
+    A, B, want = _one_tile_rows(_FEW[ntiles]())
+    with _Knobs(ctx, {"direct_min": 1024}):
+        got = _multiply(ctx, A, B, capi.SINK_COO)
+        d = _multiply(ctx, A, B, capi.SINK_DIGEST)[3]
+    assert got[3].products_direct > 0 and d.products_direct > 0
+    # every window a direct cell: the row's four cells fill one 512-thread tile (128 threads a cell), so the direct list
+    # has one tile a row
+    nrows = A.shape[0]
+    assert got[3].products_direct == got[3].products == d.products_direct == nrows * L_TILE * B_LEN
+    _check_tuples(got, want)
+    _check_digest(d, got)
     _check_digest(d, want)
 
 
