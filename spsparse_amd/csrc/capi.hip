@@ -134,8 +134,7 @@ int spsamd::multiply_body(spsamd_ctx *c, double C,
 	const spsamd_vec *scalek, int duplicate_policy, int zero_nan,
 	int sink_kind, int sink_flags, spsamd_result *res, const char *what, bool arena_ready, const OperandParts *parts, bool b_rank1)
 {
-	if (duplicate_policy < 0 || duplicate_policy > 2) throw Error{SPSAMD_EINVAL, "bad duplicate_policy"};
-	if (sink_kind != SPSAMD_SINK_COO && sink_kind != SPSAMD_SINK_DIGEST) throw Error{SPSAMD_EINVAL, "bad sink_kind"};
+	check_sink_args(duplicate_policy, sink_kind);
 	std::memset(res, 0, sizeof(*res));
 	const bool permute = (sink_flags & SPSAMD_SINK_PERMUTE) && sink_kind == SPSAMD_SINK_COO;
 	const ProductFrame f(A, transpose_A, B, transpose_B, permute);

@@ -83,6 +83,62 @@ __device__ __forceinline__ T block_exclusive_scan(T v, T *scratch, T *total)
 	return base + inc - v;
 }
 
+// mag(x): the bits of x with the sign cleared, compared as an unsigned integer where no floating-point comparison may decide
+__device__ __forceinline__ uint64_t mag_of(double v) { return (uint64_t)__double_as_longlong(v) & 0x7FFFFFFFFFFFFFFFull; }
+
+// ---- order-preserving compaction over wave tiles, lists claimed from a counter ----------------
+// A new operation calls these, it does not copy them.  Every lane of the wave must call them (they ballot).
+
+constexpr int WAVE_TILE_ROUNDS = 8;
+constexpr int WAVE_TILE = 64 * WAVE_TILE_ROUNDS;   // elements a wave of a count / compact pass takes: 8 rounds of 64
+
+// How many i of [base, min(base + WAVE_TILE, n)) have keep(i).  keep is called for i < n only (it may store per element).
+template <class Keep>
+__device__ __forceinline__ uint32_t wave_tile_count(uint64_t base, uint64_t n, Keep keep)
+{
+	uint32_t cnt = 0;
+#pragma unroll
+	for (int r = 0; r < WAVE_TILE_ROUNDS; ++r) {
+		const uint64_t i = base + (uint64_t)r * 64 + lane_id();
+		cnt += (uint32_t)__popcll(__ballot(i < n && keep(i)));
+	}
+	return cnt;
+}
+
+// store(i, p) for every i of the wave-uniform range [a0, a1) with keep(i), p = o, o + 1, ... in the order of i: `o` is the
+// scanned count of what the waves before this one keep.  No atomic: the output is in input order.  The range may be empty
+// or longer than a tile.  A whole tile's eight rounds are unrolled, so that their loads are issued together; what is left
+// of the range goes round by round, so a short range (the merge path hands out half tiles) pays for the rounds it has.
+template <class Keep, class Store>
+__device__ __forceinline__ void wave_range_compact(uint64_t a0, uint64_t a1, uint32_t o, Keep keep, Store store)
+{
+	auto round = [&](uint64_t base) {
+		const uint64_t i = base + lane_id();
+		const bool k = i < a1 && keep(i);
+		const uint64_t m = __ballot(k);
+		if (k) store(i, o + (uint32_t)__popcll(m & lanemask_lt()));
+		o += (uint32_t)__popcll(m);
+	};
+	uint64_t base = a0;
+	for (; base + WAVE_TILE <= a1; base += WAVE_TILE) {                // uniform
+#pragma unroll
+		for (int r = 0; r < WAVE_TILE_ROUNDS; ++r) round(base + (uint64_t)r * 64);
+	}
+	for (; base < a1; base += 64) round(base);                         // uniform
+}
+
+// Appends the lanes with `pred` to the list that *counter counts and returns each one's slot (a lane without `pred` gets a
+// number that means nothing): one atomic per wave, none when no lane has it.  The list ends up in no particular order.
+__device__ __forceinline__ uint32_t wave_claim(uint32_t *counter, bool pred)
+{
+	const uint64_t m = __ballot(pred);
+	if (!m) return 0;                                                  // uniform
+	uint32_t at = 0;
+	if (lane_id() == 0) at = atomicAdd(counter, (uint32_t)__popcll(m));
+	at = (uint32_t)__builtin_amdgcn_readfirstlane((int)at);
+	return at + (uint32_t)__popcll(m & lanemask_lt());
+}
+
 // Index hash of the digest sink: one 64-bit multiply and a fold of (i, j).
 // Same arithmetic as orc_mix64 in the test oracle.
 __host__ __device__ __forceinline__ uint64_t mix64(uint32_t i, uint32_t j)

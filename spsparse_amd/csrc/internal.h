@@ -496,6 +496,8 @@ bool same_operand(const spsamd_coo *a, const spsamd_coo *b);
 // ---------------------------------------------------------------- sink tail (sink.hip)
 // How an operation hands its result over.  A new operation calls these (and the intake above), it does not copy them.
 
+// What every entry point with a sink refuses first: "bad duplicate_policy", "bad sink_kind" (SPSAMD_EINVAL).
+void check_sink_args(int duplicate_policy, int sink_kind);
 // Select the output set the next result is written to: the current one unless a device operand lives in it.
 void pick_output_set(spsamd_ctx *c, const spsamd_coo *const *operands, int n);
 // Does output set `s` of the context hold an array of one of the device operands?
@@ -508,6 +510,9 @@ CooOut grow_output(OutSet &o, size_t total);
 CooOut coo_output(spsamd_ctx *c, size_t total);
 // Workspace arrays for `total` tuples: where the DIGEST sink of an operation that stores its tuples first keeps them.
 CooOut scratch_output(spsamd_ctx *c, size_t total);
+// The frame between a count pass and its store pass: offs = exclusive scan of counts (n + 1 entries), *total = offs[n] read
+// back, and the output for that many tuples: coo_output, or scratch_output for the DIGEST sink.
+CooOut counted_output(spsamd_ctx *c, const uint32_t *counts, uint32_t *offs, size_t n, bool coo, uint32_t *total);
 // SINK_COO: fill res (nnz, idx0, idx1, val; its shape is set already) and register the tuples in c->own -- row-major sorted,
 // every (i, j) once, indices valid: consolidated by sort order {0, 1}.  `permute` (PermuteAccum {1,0}): the same tuples
 // with res->idx0 / idx1 swapped, which read that way are consolidated by {1, 0}.
@@ -521,5 +526,8 @@ void digest_stored(spsamd_ctx *c, spsamd_result *res, const int32_t *orow, const
 	uint64_t nrow, int sink_flags);
 // The end of a call: EV_END recorded and waited for, ms_total (from EV_BEGIN) and workspace_bytes filled.
 void finish_call(spsamd_ctx *c, spsamd_result *res);
+// The tail of an operation whose `total` tuples are stored in `o` (rows of [0, nrow)): res->nnz, publish_coo or
+// digest_stored, finish_call.  The ms_* fields other than ms_total stay with the caller: which events they span differs.
+void deliver_stored(spsamd_ctx *c, spsamd_result *res, const CooOut &o, uint32_t total, uint64_t nrow, bool coo, bool permute, int sink_flags);
 
 } // namespace spsamd

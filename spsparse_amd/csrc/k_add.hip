@@ -265,8 +265,7 @@ static void launch_merge(spsamd_ctx *c, uint32_t ntiles, const AddStream &a, con
 void add_matrices(spsamd_ctx *c, double alpha, const spsamd_coo *A, char transpose_A, double beta, const spsamd_coo *B,
 	char transpose_B, int duplicate_policy, int zero_nan, int sink_kind, int sink_flags, spsamd_result *res)
 {
-	if (duplicate_policy < 0 || duplicate_policy > 2) throw Error{SPSAMD_EINVAL, "bad duplicate_policy"};
-	if (sink_kind != SPSAMD_SINK_COO && sink_kind != SPSAMD_SINK_DIGEST) throw Error{SPSAMD_EINVAL, "bad sink_kind"};
+	check_sink_args(duplicate_policy, sink_kind);
 	std::memset(res, 0, sizeof(*res));
 	const int la = transpose_A == 'T' ? 1 : 0, lb = transpose_B == 'T' ? 1 : 0;
 	const uint64_t ash[2] = {A->shape0, A->shape1}, bsh[2] = {B->shape0, B->shape1};
@@ -315,19 +314,14 @@ void add_matrices(spsamd_ctx *c, double alpha, const spsamd_coo *A, char transpo
 	uint32_t *tile_count = c->arena.get<uint32_t>((size_t)ntiles + 1), *tile_off = c->arena.get<uint32_t>((size_t)ntiles + 1);
 	merge_partition(c, sa, sb, ntiles, split);
 	launch_merge<ADD_COUNT>(c, ntiles, sa, sb, alpha, beta, zero_nan, first, split, tile_count, nullptr, nullptr, nullptr, nullptr);
-	scan_exclusive_u32_u32(c, tile_count, tile_off, ntiles);
-	const uint32_t total = read_back(c, tile_off + ntiles);
-
-	const CooOut o = coo ? coo_output(c, total) : scratch_output(c, total);
+	uint32_t total;
+	const CooOut o = counted_output(c, tile_count, tile_off, ntiles, coo, &total);
 	switch (duplicate_policy) {
 	case SPSAMD_ADD: launch_merge<SPSAMD_ADD>(c, ntiles, sa, sb, alpha, beta, zero_nan, first, split, nullptr, tile_off, o.row, o.col, o.val); break;
 	case SPSAMD_REPLACE: launch_merge<SPSAMD_REPLACE>(c, ntiles, sa, sb, alpha, beta, zero_nan, first, split, nullptr, tile_off, o.row, o.col, o.val); break;
 	default: launch_merge<SPSAMD_LEAVE_ALONE>(c, ntiles, sa, sb, alpha, beta, zero_nan, first, split, nullptr, tile_off, o.row, o.col, o.val); break;
 	}
-	res->nnz = total;
-	if (coo) publish_coo(c, res, o.row, o.col, o.val, total, permute);
-	else digest_stored(c, res, o.row, o.col, o.val, total, nrow, sink_flags);
-	finish_call(c, res);
+	deliver_stored(c, res, o, total, nrow, coo, permute, sink_flags);
 	if (sorted_a || sorted_b) SPS_HIP(hipEventElapsedTime(&res->ms_consolidate, c->ev[EV_BEGIN], c->ev[EV_CONSOLIDATED]));
 }
 

@@ -20,8 +20,8 @@
 //               Without COMPLEMENT the run lengths are scanned and k_em_emit_runs stores the runs: no array of nnz(A)
 //               entries exists.  Under COMPLEMENT the probe writes its position over the run in a word array preset to
 //               all ones, and the flag tail below runs over S_A.
-//   flag tail   the per-wave counts are scanned; k_em_compact reads each word once and, for a kept tuple, a (and b under
-//               TIMES) and stores (i, j, v) at the wave's offset plus the tuple's rank (ballot + popcount): S_A's order.
+//   flag tail   the shared compaction over wave tiles (devutil.h): the per-wave counts are scanned; k_em_compact reads each
+//               word and, for a kept tuple, a (and b under TIMES) and stores (i, j, v) in S_A's order.
 // Every product has the bits x86-64 gives it (x86fp.h).
 #include "internal.h"
 #include "devutil.h"
@@ -35,8 +35,6 @@
 namespace spsamd {
 
 constexpr uint32_t EM_MISS = 0xFFFFFFFFu;      // the word of an A tuple whose key is no key of B
-constexpr int EM_ROUNDS = 8;
-constexpr int EM_UNIT = 64 * EM_ROUNDS;        // A tuples per wave of the probe, count and compact kernels (fixed units)
 // Auto choice: the fraction of a probe's search steps charged one 64-byte line of memory traffic (measured 0.29 on the
 // lopsided benchmark workload: DESIGN.md section 17, profiles/emult/)
 constexpr double EM_PROBE_MISS = 0.25;
@@ -76,7 +74,7 @@ __device__ __forceinline__ uint32_t em_run_end(const AddStream &s, uint32_t lo, 
 // One tile of the merged sequence: hit[] for the tile's A tuples; per wave, where its A range starts (bounds[4 * tile + wave])
 // and how many of its A tuples are kept (hits, under `flip` misses).
 __global__ void __launch_bounds__(ADD_NT) k_em_merge(AddStream a, AddStream b, const uint32_t *__restrict__ split, uint32_t ntiles, int flip,
-	uint32_t *__restrict__ hit, uint32_t *__restrict__ bounds, uint32_t *__restrict__ unit_count)
+	uint32_t *__restrict__ hit, uint32_t *__restrict__ bounds, uint32_t *__restrict__ wave_count)
 {
 	__shared__ uint64_t s_key[ADD_TILE];
 	const uint32_t tile = blockIdx.x;
@@ -118,24 +116,26 @@ __global__ void __launch_bounds__(ADD_NT) k_em_merge(AddStream a, AddStream b, c
 	}
 	kept = wave_reduce_sum<uint32_t>(kept);
 	if (lane_id() == 0) {
-		const uint32_t unit = tile * (ADD_NT / 64) + wave_id();
-		bounds[unit] = first_a;
-		unit_count[unit] = kept;
+		const uint32_t w = tile * (ADD_NT / 64) + wave_id();         // the wave tile of k_em_compact that stores this range
+		bounds[w] = first_a;
+		wave_count[w] = kept;
 		if (tile == ntiles - 1 && wave_id() == 0) bounds[ntiles * (ADD_NT / 64)] = a.n;
 	}
 }
 
 // ---------------------------------------------------------------- path 2: every tuple of S_A probes S_B
 
+// (wave_tile_count of devutil.h with the probe as its `keep`, spelled out: that helper unrolls all eight rounds, and this
+// loop stays as it was tuned, two binary searches in flight per lane)
 __global__ void __launch_bounds__(256) k_em_probe_a(AddStream a, AddStream b, const uint32_t *__restrict__ brp, int flip,
-	uint32_t *__restrict__ hit, uint32_t *__restrict__ unit_count)
+	uint32_t *__restrict__ hit, uint32_t *__restrict__ tile_count)
 {
-	const uint32_t unit = blockIdx.x * 4 + wave_id();
-	const uint64_t base = (uint64_t)unit * EM_UNIT;
+	const uint32_t tile = blockIdx.x * 4 + wave_id();
+	const uint64_t base = (uint64_t)tile * WAVE_TILE;
 	if (base >= a.n) return;
 	uint32_t cnt = 0;
 #pragma unroll 2
-	for (int r = 0; r < EM_ROUNDS; ++r) {
+	for (int r = 0; r < WAVE_TILE_ROUNDS; ++r) {
 		const uint64_t i = base + (uint64_t)r * 64 + lane_id();
 		bool k = false;
 		if (i < a.n) {
@@ -147,7 +147,7 @@ __global__ void __launch_bounds__(256) k_em_probe_a(AddStream a, AddStream b, co
 		}
 		cnt += (uint32_t)__popcll(__ballot(k));
 	}
-	if (lane_id() == 0) unit_count[unit] = cnt;
+	if (lane_id() == 0) tile_count[tile] = cnt;
 }
 
 // ---------------------------------------------------------------- path 3: every first-of-key tuple of S_B probes S_A
@@ -195,46 +195,33 @@ __global__ void __launch_bounds__(256) k_em_emit_runs(AddStream a, AddStream b, 
 
 // ---------------------------------------------------------------- the flag tail
 
-// kept tuples per fixed unit of EM_UNIT words (the paths whose probe does not count: 3 under COMPLEMENT, an empty B)
-__global__ void __launch_bounds__(256) k_em_count(const uint32_t *__restrict__ hit, uint32_t n, int flip, uint32_t *__restrict__ unit_count)
+// kept tuples per fixed tile of WAVE_TILE words (the paths whose probe does not count: 3 under COMPLEMENT, an empty B)
+__global__ void __launch_bounds__(256) k_em_count(const uint32_t *__restrict__ hit, uint32_t n, int flip, uint32_t *__restrict__ tile_count)
 {
-	const uint32_t unit = blockIdx.x * 4 + wave_id();
-	const uint64_t base = (uint64_t)unit * EM_UNIT;
+	const uint32_t tile = blockIdx.x * 4 + wave_id();
+	const uint64_t base = (uint64_t)tile * WAVE_TILE;
 	if (base >= n) return;
-	uint32_t cnt = 0;
-#pragma unroll
-	for (int r = 0; r < EM_ROUNDS; ++r) {
-		const uint64_t i = base + (uint64_t)r * 64 + lane_id();
-		cnt += (uint32_t)__popcll(__ballot(i < n && (hit[i] != EM_MISS) != (flip != 0)));
-	}
-	if (lane_id() == 0) unit_count[unit] = cnt;
+	const uint32_t cnt = wave_tile_count(base, n, [&](uint64_t i) { return (hit[i] != EM_MISS) != (flip != 0); });
+	if (lane_id() == 0) tile_count[tile] = cnt;
 }
 
-// A wave per unit: the A range [bounds[unit], bounds[unit + 1]) (null: fixed units of EM_UNIT), stored from unit_off[unit] on
+// A wave per tile: the A range [bounds[tile], bounds[tile + 1]) (null: fixed tiles of WAVE_TILE), stored from tile_off[tile] on
 template <int OP>
 __global__ void __launch_bounds__(256) k_em_compact(AddStream a, const double *__restrict__ bval, double alpha,
-	const uint32_t *__restrict__ hit, const uint32_t *__restrict__ bounds, const uint32_t *__restrict__ unit_off, uint32_t nunits, int flip,
+	const uint32_t *__restrict__ hit, const uint32_t *__restrict__ bounds, const uint32_t *__restrict__ tile_off, uint32_t ntiles, int flip,
 	int32_t *__restrict__ orow, int32_t *__restrict__ ocol, double *__restrict__ oval)
 {
-	const uint32_t unit = blockIdx.x * 4 + wave_id();
-	if (unit >= nunits) return;
+	const uint32_t tile = blockIdx.x * 4 + wave_id();
+	if (tile >= ntiles) return;
 	uint32_t a0, a1;
-	if (bounds) { a0 = bounds[unit]; a1 = bounds[unit + 1]; }
-	else { a0 = unit * (uint32_t)EM_UNIT; a1 = (uint32_t)std::min<uint64_t>((uint64_t)a0 + EM_UNIT, a.n); }
+	if (bounds) { a0 = bounds[tile]; a1 = bounds[tile + 1]; }
+	else { a0 = tile * (uint32_t)WAVE_TILE; a1 = (uint32_t)std::min<uint64_t>((uint64_t)a0 + WAVE_TILE, a.n); }
 	a0 = (uint32_t)__builtin_amdgcn_readfirstlane((int)a0); a1 = (uint32_t)__builtin_amdgcn_readfirstlane((int)a1);
-	uint32_t o = unit_off[unit];
-	for (uint32_t base = a0; base < a1; base += 64) {                // uniform
-		const uint32_t i = base + lane_id();
-		const uint32_t h = i < a1 ? hit[i] : EM_MISS;
-		const bool k = i < a1 && (h != EM_MISS) != (flip != 0);
-		const uint64_t m = __ballot(k);
-		if (k) {
-			const uint32_t p = o + (uint32_t)__popcll(m & lanemask_lt());
+	wave_range_compact(a0, a1, tile_off[tile], [&](uint64_t i) { return (hit[i] != EM_MISS) != (flip != 0); },
+		[&](uint64_t i, uint32_t p) {
 			orow[p] = a.row[i]; ocol[p] = a.col[i];
-			oval[p] = em_value<OP>(a.val[i], bval, h, alpha);
-		}
-		o += (uint32_t)__popcll(m);
-	}
+			oval[p] = em_value<OP>(a.val[i], bval, hit[i], alpha);
+		});
 }
 
 // ---------------------------------------------------------------- driver
@@ -279,9 +266,9 @@ static int em_choose(uint64_t na, uint64_t nb, bool flip, bool a_rows, bool b_ro
 
 template <int OP>
 static void em_tail(spsamd_ctx *c, const AddStream &a, const double *bval, double alpha, const uint32_t *hit, const uint32_t *bounds,
-	const uint32_t *unit_off, uint32_t nunits, int flip, const CooOut &o)
+	const uint32_t *tile_off, uint32_t nwt, int flip, const CooOut &o)
 {
-	k_em_compact<OP><<<dim3(grid_for(nunits, 4)), dim3(256), 0, c->stream>>>(a, bval, alpha, hit, bounds, unit_off, nunits, flip, o.row, o.col, o.val);
+	k_em_compact<OP><<<dim3(grid_for(nwt, 4)), dim3(256), 0, c->stream>>>(a, bval, alpha, hit, bounds, tile_off, nwt, flip, o.row, o.col, o.val);
 	SPS_LAUNCH_CHECK();
 }
 
@@ -292,8 +279,7 @@ void emult_matrices(spsamd_ctx *c, int op, int emult_flags, double alpha, const 
 	if (emult_flags & ~SPSAMD_EMULT_COMPLEMENT) throw Error{SPSAMD_EINVAL, "unknown emult_flags"};
 	const int flip = (emult_flags & SPSAMD_EMULT_COMPLEMENT) ? 1 : 0;
 	if (flip && op != SPSAMD_EMULT_FIRST) throw Error{SPSAMD_EINVAL, "SPSAMD_EMULT_COMPLEMENT goes with SPSAMD_EMULT_FIRST only"};
-	if (duplicate_policy < 0 || duplicate_policy > 2) throw Error{SPSAMD_EINVAL, "bad duplicate_policy"};
-	if (sink_kind != SPSAMD_SINK_COO && sink_kind != SPSAMD_SINK_DIGEST) throw Error{SPSAMD_EINVAL, "bad sink_kind"};
+	check_sink_args(duplicate_policy, sink_kind);
 	const int path = c->tune.emult_path;
 	if (path < 0 || path > 3) throw Error{SPSAMD_EINVAL, "emult_path must be 0 (auto), 1 (merge), 2 (probe A in B) or 3 (probe B in A)"};
 	const int la = transpose_A == 'T' ? 1 : 0, lb = transpose_B == 'T' ? 1 : 0;
@@ -352,9 +338,7 @@ void emult_matrices(spsamd_ctx *c, int op, int emult_flags, double alpha, const 
 			uint32_t *run_lo = c->arena.get<uint32_t>(nb), *run_len = c->arena.get<uint32_t>((size_t)nb + 1), *off = c->arena.get<uint32_t>((size_t)nb + 1);
 			k_em_probe_b<false><<<dim3(grid_for(nb)), dim3(256), 0, st>>>(sb, sa, arp, run_lo, run_len, nullptr);
 			SPS_LAUNCH_CHECK();
-			scan_exclusive_u32_u32(c, run_len, off, nb);
-			total = read_back(c, off + nb);
-			o = coo ? coo_output(c, total) : scratch_output(c, total);
+			o = counted_output(c, run_len, off, nb, coo, &total);
 			if (total) {
 				if (times) k_em_emit_runs<SPSAMD_EMULT_TIMES><<<dim3(grid_for(nb)), dim3(256), 0, st>>>(sa, sb, alpha, run_lo, run_len, off, o.row, o.col, o.val);
 				else k_em_emit_runs<SPSAMD_EMULT_FIRST><<<dim3(grid_for(nb)), dim3(256), 0, st>>>(sa, sb, alpha, run_lo, run_len, off, o.row, o.col, o.val);
@@ -363,50 +347,45 @@ void emult_matrices(spsamd_ctx *c, int op, int emult_flags, double alpha, const 
 			res->products = nb;
 		} else {
 			uint32_t *hit = c->arena.get<uint32_t>((size_t)na + 1);
-			uint32_t nunits = (uint32_t)(((uint64_t)na + EM_UNIT - 1) / EM_UNIT);
+			uint32_t nwt = (uint32_t)(((uint64_t)na + WAVE_TILE - 1) / WAVE_TILE);       // wave tiles of the flag tail
 			const uint32_t *bounds = nullptr;
-			uint32_t *unit_count = nullptr;
+			uint32_t *tile_count = nullptr;
 			if (p == 1) {
 				const uint64_t n = (uint64_t)na + nb;
 				const uint32_t ntiles = (uint32_t)((n + ADD_TILE - 1) / ADD_TILE);
-				nunits = ntiles * (ADD_NT / 64);
-				uint32_t *split = c->arena.get<uint32_t>((size_t)ntiles + 1), *bnd = c->arena.get<uint32_t>((size_t)nunits + 1);
-				unit_count = c->arena.get<uint32_t>((size_t)nunits + 1);
+				nwt = ntiles * (ADD_NT / 64);
+				uint32_t *split = c->arena.get<uint32_t>((size_t)ntiles + 1), *bnd = c->arena.get<uint32_t>((size_t)nwt + 1);
+				tile_count = c->arena.get<uint32_t>((size_t)nwt + 1);
 				merge_partition(c, sa, sb, ntiles, split);
-				k_em_merge<<<dim3(ntiles), dim3(ADD_NT), 0, st>>>(sa, sb, split, ntiles, flip, hit, bnd, unit_count);
+				k_em_merge<<<dim3(ntiles), dim3(ADD_NT), 0, st>>>(sa, sb, split, ntiles, flip, hit, bnd, tile_count);
 				SPS_LAUNCH_CHECK();
 				bounds = bnd;
 			} else if (p == 2) {
-				unit_count = c->arena.get<uint32_t>((size_t)nunits + 1);
-				k_em_probe_a<<<dim3(grid_for(nunits, 4)), dim3(256), 0, st>>>(sa, sb, brp, flip, hit, unit_count);
+				tile_count = c->arena.get<uint32_t>((size_t)nwt + 1);
+				k_em_probe_a<<<dim3(grid_for(nwt, 4)), dim3(256), 0, st>>>(sa, sb, brp, flip, hit, tile_count);
 				SPS_LAUNCH_CHECK();
 				res->products = na;
 			} else {
-				unit_count = c->arena.get<uint32_t>((size_t)nunits + 1);
+				tile_count = c->arena.get<uint32_t>((size_t)nwt + 1);
 				fill_u32(c, hit, EM_MISS, na);
 				if (nb) {
 					k_em_probe_b<true><<<dim3(grid_for(nb)), dim3(256), 0, st>>>(sb, sa, arp, nullptr, nullptr, hit);
 					SPS_LAUNCH_CHECK();
 				}
-				k_em_count<<<dim3(grid_for(nunits, 4)), dim3(256), 0, st>>>(hit, na, flip, unit_count);
+				k_em_count<<<dim3(grid_for(nwt, 4)), dim3(256), 0, st>>>(hit, na, flip, tile_count);
 				SPS_LAUNCH_CHECK();
 				res->products = nb;
 			}
-			uint32_t *unit_off = c->arena.get<uint32_t>((size_t)nunits + 1);
-			scan_exclusive_u32_u32(c, unit_count, unit_off, nunits);
-			total = read_back(c, unit_off + nunits);
-			o = coo ? coo_output(c, total) : scratch_output(c, total);
+			uint32_t *tile_off = c->arena.get<uint32_t>((size_t)nwt + 1);
+			o = counted_output(c, tile_count, tile_off, nwt, coo, &total);
 			if (total) {
-				if (times) em_tail<SPSAMD_EMULT_TIMES>(c, sa, sb.val, alpha, hit, bounds, unit_off, nunits, flip, o);
-				else em_tail<SPSAMD_EMULT_FIRST>(c, sa, sb.val, alpha, hit, bounds, unit_off, nunits, flip, o);
+				if (times) em_tail<SPSAMD_EMULT_TIMES>(c, sa, sb.val, alpha, hit, bounds, tile_off, nwt, flip, o);
+				else em_tail<SPSAMD_EMULT_FIRST>(c, sa, sb.val, alpha, hit, bounds, tile_off, nwt, flip, o);
 			}
 		}
 	} else o = coo ? coo_output(c, 0) : scratch_output(c, 0);
-	res->nnz = total;
 	// a subsequence of S_A: in op(A)'s row order (read permuted: sorted by {1, 0}), indices checked
-	if (coo) publish_coo(c, res, o.row, o.col, o.val, total, permute);
-	else digest_stored(c, res, o.row, o.col, o.val, total, nrow, sink_flags);
-	finish_call(c, res);
+	deliver_stored(c, res, o, total, nrow, coo, permute, sink_flags);
 	SPS_HIP(hipEventElapsedTime(&res->ms_consolidate, c->ev[EV_BEGIN], c->ev[EV_CONSOLIDATED]));
 	SPS_HIP(hipEventElapsedTime(&res->ms_numeric, c->ev[EV_CONSOLIDATED], c->ev[EV_END]));
 }

@@ -113,12 +113,8 @@ __global__ void __launch_bounds__(256) k_ext_src_classify(const int32_t *__restr
 	const int cls = len <= (uint32_t)EXT_SHORT_MAX ? -1 : len <= (uint32_t)EXT_MID_MAX ? 0 : 1;
 #pragma unroll
 	for (int q = 0; q < 2; ++q) {
-		const uint64_t m = __ballot(cls == q);
-		if (!m) continue;                                          // uniform
-		uint32_t at = 0;
-		if (lane_id() == 0) at = atomicAdd(&w[q], (uint32_t)__popcll(m));
-		at = (uint32_t)__builtin_amdgcn_readfirstlane((int)at);
-		if (cls == q) (q == 0 ? long_list : huge_list)[at + (uint32_t)__popcll(m & lanemask_lt())] = (uint32_t)r;
+		const uint32_t slot = wave_claim(&w[q], cls == q);
+		if (cls == q) (q == 0 ? long_list : huge_list)[slot] = (uint32_t)r;
 	}
 }
 
@@ -268,16 +264,15 @@ __global__ void __launch_bounds__(256) k_ext_classify(const uint32_t *__restrict
 		const int cls = n >= 2 ? ext_class(n, path) : -1;
 #pragma unroll
 		for (int q = 0; q < 3; ++q) {
-			const uint64_t m = __ballot(cls == q);
+			const bool in = cls == q;
+			const uint64_t m = __ballot(in);
 			if (!m) continue;                                      // uniform
-			const uint32_t tup = wave_reduce_sum<uint32_t>(cls == q ? n : 0u);
+			const uint32_t tup = wave_reduce_sum<uint32_t>(in ? n : 0u);
 			if (q == 0) { lrows += (uint32_t)__popcll(m); ltup += tup; continue; }
-			uint32_t at = 0;
-			if (lane_id() == 0) { at = atomicAdd(&w[q], (uint32_t)__popcll(m)); atomicAdd(&w[3 + q], tup); }
-			at = (uint32_t)__builtin_amdgcn_readfirstlane((int)at);
-			const uint32_t slot = at + (uint32_t)__popcll(m & lanemask_lt());
-			if (cls == q && q == 1) mid_list[slot] = (uint32_t)r;
-			if (cls == q && q == 2) { heavy_list[slot] = (uint32_t)r; heavy_len[slot] = n; }
+			const uint32_t slot = wave_claim(&w[q], in);
+			if (lane_id() == 0) atomicAdd(&w[3 + q], tup);
+			if (in && q == 1) mid_list[slot] = (uint32_t)r;
+			if (in && q == 2) { heavy_list[slot] = (uint32_t)r; heavy_len[slot] = n; }
 		}
 	}
 	if (lane_id() == 0 && lrows) { atomicAdd(&w[0], lrows); atomicAdd(&w[3], ltup); }
@@ -450,8 +445,7 @@ static void check_list_pointer(const int32_t *p, int index_mem, const char *name
 void extract_tuples(spsamd_ctx *c, const spsamd_coo *A, char transpose, const int32_t *rows, size_t nrows, const int32_t *cols,
 	size_t ncols, int index_mem, int duplicate_policy, int zero_nan, int sink_kind, int sink_flags, spsamd_result *res)
 {
-	if (duplicate_policy < 0 || duplicate_policy > 2) throw Error{SPSAMD_EINVAL, "bad duplicate_policy"};
-	if (sink_kind != SPSAMD_SINK_COO && sink_kind != SPSAMD_SINK_DIGEST) throw Error{SPSAMD_EINVAL, "bad sink_kind"};
+	check_sink_args(duplicate_policy, sink_kind);
 	if (index_mem != SPSAMD_MEM_HOST && index_mem != SPSAMD_MEM_DEVICE) throw Error{SPSAMD_EINVAL, "index_mem must be SPSAMD_MEM_HOST or SPSAMD_MEM_DEVICE"};
 	if ((rows && nrows >= (size_t(1) << 31)) || (cols && ncols >= (size_t(1) << 31))) throw Error{SPSAMD_EINVAL, "an index list of 2^31 or more entries"};
 	SPS_HIP(hipSetDevice(c->device));
@@ -595,11 +589,8 @@ void extract_tuples(spsamd_ctx *c, const spsamd_coo *A, char transpose, const in
 			SPS_LAUNCH_CHECK();
 		}
 	}
-	res->nnz = total;
 	// row-major, every row in (c, p) order (read permuted: sorted by {1, 0}), indices checked
-	if (coo) publish_coo(c, res, o.row, o.col, o.val, total, permute);
-	else digest_stored(c, res, o.row, o.col, o.val, total, nR, sink_flags);
-	finish_call(c, res);
+	deliver_stored(c, res, o, total, nR, coo, permute, sink_flags);
 	SPS_HIP(hipEventElapsedTime(&res->ms_consolidate, c->ev[EV_BEGIN], c->ev[EV_CONSOLIDATED]));
 	SPS_HIP(hipEventElapsedTime(&res->ms_symbolic, c->ev[EV_CONSOLIDATED], c->ev[EV_SYMBOLIC]));
 	SPS_HIP(hipEventElapsedTime(&res->ms_numeric, c->ev[EV_SYMBOLIC], c->ev[EV_END]));

@@ -338,8 +338,7 @@ void multiply_masked(spsamd_ctx *c, double C,
 	const spsamd_vec *scalek, const spsamd_coo *M, int duplicate_policy, int zero_nan,
 	int sink_kind, int sink_flags, spsamd_result *res)
 {
-	if (duplicate_policy < 0 || duplicate_policy > 2) throw Error{SPSAMD_EINVAL, "bad duplicate_policy"};
-	if (sink_kind != SPSAMD_SINK_COO && sink_kind != SPSAMD_SINK_DIGEST) throw Error{SPSAMD_EINVAL, "bad sink_kind"};
+	check_sink_args(duplicate_policy, sink_kind);
 	std::memset(res, 0, sizeof(*res));
 	const bool coo = sink_kind == SPSAMD_SINK_COO;
 	const bool permute = coo && (sink_flags & SPSAMD_SINK_PERMUTE);

@@ -16,8 +16,8 @@
 //      consecutive values, loaded by half a wave (256 contiguous bytes) into a padded [row][RED_CHUNK + 1] LDS tile; each lane
 //      folds its row's chunk while the next step's loads are in flight (they are issued into registers ahead of the adds).
 //   4. both kernels apply the post-operation and store dense: out_val itself (dense form, device memory) or a workspace
-//      array.  The sparse form runs one more pass over the ROWS: k_red_tile_count, a scan, k_red_compact (ballot + popcount
-//      inside tiles of 512 rows, as k_sel_compact does over tuples).
+//      array.  The sparse form runs one more pass over the ROWS: k_red_tile_count, a scan, k_red_compact (the shared
+//      compaction over wave tiles, devutil.h).
 // COUNT reads the row pointer only (k_red_rowcount).  MAX_ABS goes through the same two kernels with an integer max on mag.
 #include "internal.h"
 #include "devutil.h"
@@ -31,7 +31,6 @@ namespace spsamd {
 constexpr int RED_LIGHT_MAX = 64;              // longest row of the short class
 constexpr int RED_SPAN = 512;                  // values a wave of k_red_short stages per step (8 per lane)
 constexpr int RED_CHUNK = 32;                  // values per row and step of k_red_long
-constexpr int RED_TILE = 512;                  // rows per wave of the compaction pass
 constexpr uint64_t RED_INF = 0x7FF0000000000000ull;
 
 struct RedArgs {
@@ -44,8 +43,6 @@ struct RedArgs {
 	uint8_t *has;                              // DIAG: does the row have a diagonal tuple
 	uint32_t *nz;                              // DIAG: the number of such rows
 };
-
-__device__ __forceinline__ uint64_t red_mag(double v) { return (uint64_t)__double_as_longlong(v) & 0x7FFFFFFFFFFFFFFFull; }
 
 // the LDS of these kernels is private to a wave, whose DS operations execute in order: only the compiler has to be held
 __device__ __forceinline__ void wave_lds_sync()
@@ -60,10 +57,10 @@ template <int OP>
 __device__ __forceinline__ double red_step(double acc, double v, bool on_diag, bool &has)
 {
 	if (OP == SPSAMD_REDUCE_SUM) return ref_add(acc, v);
-	if (OP == SPSAMD_REDUCE_SUM_ABS) return ref_add(acc, __longlong_as_double((long long)red_mag(v)));
+	if (OP == SPSAMD_REDUCE_SUM_ABS) return ref_add(acc, __longlong_as_double((long long)mag_of(v)));
 	if (OP == SPSAMD_REDUCE_SUM_SQ) return ref_add(acc, ref_mul(v, v));
 	if (OP == SPSAMD_REDUCE_MAX_ABS) {
-		const uint64_t x = red_mag(v);
+		const uint64_t x = mag_of(v);
 		return (x <= RED_INF && x > (uint64_t)__double_as_longlong(acc)) ? __longlong_as_double((long long)x) : acc;
 	}
 	if (on_diag) { has = true; return ref_add(acc, v); }
@@ -129,15 +126,10 @@ __global__ void __launch_bounds__(256) k_red_classify(const uint32_t *__restrict
 	while (todo) {                                                 // uniform
 		const int l = __builtin_amdgcn_readfirstlane(__ffsll((unsigned long long)todo) - 1);
 		const int bb = __builtin_amdgcn_readlane(b, l);
-		const uint64_t m = __ballot(lng && b == bb);
-		todo &= ~m;
-		if (!FILL) { if (lane_id() == 0) atomicAdd(&bins[bb], (uint32_t)__popcll(m)); }
-		else {
-			uint32_t at = 0;
-			if (lane_id() == 0) at = atomicAdd(&bins[bb], (uint32_t)__popcll(m));
-			at = (uint32_t)__builtin_amdgcn_readfirstlane((int)at);
-			if (lng && b == bb) list[at + (uint32_t)__popcll(m & lanemask_lt())] = (uint32_t)r;
-		}
+		const bool in = lng && b == bb;
+		todo &= ~__ballot(in);
+		const uint32_t slot = wave_claim(&bins[bb], in);           // (FILL = false: counted only)
+		if (FILL && in) list[slot] = (uint32_t)r;
 	}
 }
 
@@ -282,14 +274,9 @@ __global__ void __launch_bounds__(256) k_red_tile_count(const uint32_t *__restri
 	uint32_t *__restrict__ tile_count)
 {
 	const uint64_t tile = (uint64_t)blockIdx.x * 4 + wave_id();
-	const uint64_t base = tile * RED_TILE;
+	const uint64_t base = tile * WAVE_TILE;
 	if (base >= nrow) return;
-	uint32_t cnt = 0;
-#pragma unroll
-	for (int k = 0; k < RED_TILE / 64; ++k) {
-		const uint64_t r = base + (uint64_t)k * 64 + lane_id();
-		cnt += (uint32_t)__popcll(__ballot(r < nrow && red_present(ptr, has, r)));
-	}
+	const uint32_t cnt = wave_tile_count(base, nrow, [&](uint64_t r) { return red_present(ptr, has, r); });
 	if (lane_id() == 0) tile_count[tile] = cnt;
 }
 
@@ -297,20 +284,10 @@ __global__ void __launch_bounds__(256) k_red_compact(const uint32_t *__restrict_
 	const double *__restrict__ dval, const uint32_t *__restrict__ tile_off, int32_t *__restrict__ oidx, double *__restrict__ oval)
 {
 	const uint64_t tile = (uint64_t)blockIdx.x * 4 + wave_id();
-	const uint64_t base = tile * RED_TILE;
+	const uint64_t base = tile * WAVE_TILE;
 	if (base >= nrow) return;
-	uint32_t o = tile_off[tile];
-#pragma unroll
-	for (int k = 0; k < RED_TILE / 64; ++k) {
-		const uint64_t r = base + (uint64_t)k * 64 + lane_id();
-		const bool p = r < nrow && red_present(ptr, has, r);
-		const uint64_t m = __ballot(p);
-		if (p) {
-			const uint32_t at = o + (uint32_t)__popcll(m & lanemask_lt());
-			oidx[at] = (int32_t)r; oval[at] = dval[r];
-		}
-		o += (uint32_t)__popcll(m);
-	}
+	wave_range_compact(base, std::min<uint64_t>(base + WAVE_TILE, nrow), tile_off[tile], [&](uint64_t r) { return red_present(ptr, has, r); },
+		[&](uint64_t r, uint32_t at) { oidx[at] = (int32_t)r; oval[at] = dval[r]; });
 }
 
 template <int OP>
@@ -472,7 +449,7 @@ int reduce_rows(spsamd_ctx *c, const spsamd_coo *A, char transpose, int op, int 
 	}
 
 	if (sparse && count) {
-		const uint32_t ntiles = (uint32_t)((nrow + RED_TILE - 1) / RED_TILE);
+		const uint32_t ntiles = (uint32_t)((nrow + WAVE_TILE - 1) / WAVE_TILE);
 		uint32_t *tile_count = c->arena.get<uint32_t>((size_t)ntiles + 1), *tile_off = c->arena.get<uint32_t>((size_t)ntiles + 1);
 		k_red_tile_count<<<dim3(grid_for(ntiles, 4)), dim3(256), 0, st>>>(ptr, a.has, nrow, tile_count);
 		SPS_LAUNCH_CHECK();

@@ -12,8 +12,7 @@
 //                           k_sel_topk_mid    n <= 4096: a workgroup per row, keys in LDS, MSD radix select of the k-th key,
 //                           k_sel_topk_heavy  beyond: the same select, keys re-read from memory for every digit,
 //                         then k_sel_count counts the bytes;
-//   2. tiles of 512 tuples (one wave each): the counts are scanned, k_sel_compact stores every kept tuple at its tile's
-//      offset plus its rank inside the tile (ballot + popcount).  No atomics touch the output: it is in S's order.
+//   2. the shared compaction over wave tiles (devutil.h): k_sel_compact stores the kept tuples in S's order.
 // mag(x) = the bits of x with the sign cleared, compared as an unsigned integer; no floating-point comparison decides.
 #include "internal.h"
 #include "devutil.h"
@@ -28,11 +27,7 @@ constexpr int SEL_LIGHT_MAX = 64;              // longest row of the light class
 constexpr int SEL_MID_MAX = 4096;              // longest row of the mid class (keys in 32 KiB of LDS)
 constexpr int SEL_MID_NT = 256;
 constexpr int SEL_HEAVY_NT = 1024;
-constexpr int SEL_ROUNDS = 8;
-constexpr int SEL_TILE = 64 * SEL_ROUNDS;      // tuples per wave of the flag / count / compact kernels
 constexpr uint64_t SEL_INF = 0x7FF0000000000000ull;
-
-__device__ __forceinline__ uint64_t mag_of(double v) { return (uint64_t)__double_as_longlong(v) & 0x7FFFFFFFFFFFFFFFull; }
 
 struct SelArgs {
 	const int32_t *row, *col;
@@ -45,47 +40,37 @@ struct SelArgs {
 	int flip;                                  // COMPLEMENT
 };
 
-// keep[t] and the number of kept tuples per tile
+// keep[t] and the number of kept tuples per tile: the predicate is the `keep` of wave_tile_count, and stores its byte
 template <int PRED>
 __global__ void __launch_bounds__(256) k_sel_flag(SelArgs a, uint8_t *__restrict__ keep, uint32_t *__restrict__ tile_count)
 {
 	const uint32_t tile = blockIdx.x * 4 + wave_id();
-	const uint64_t base = (uint64_t)tile * SEL_TILE;
+	const uint64_t base = (uint64_t)tile * WAVE_TILE;
 	if (base >= a.n) return;
-	uint32_t cnt = 0;
-#pragma unroll
-	for (int r = 0; r < SEL_ROUNDS; ++r) {
-		const uint64_t i = base + (uint64_t)r * 64 + lane_id();
-		bool k = false;
-		if (i < a.n) {
-			if (PRED <= SPSAMD_SELECT_OFFDIAG) {
-				const long long diff = (long long)a.col[i] - (long long)a.row[i];
-				k = PRED == SPSAMD_SELECT_TRIL ? diff <= a.d : PRED == SPSAMD_SELECT_TRIU ? diff >= a.d :
-					PRED == SPSAMD_SELECT_DIAG ? diff == a.d : diff != a.d;
-			} else if (PRED == SPSAMD_SELECT_ABS_GE) k = mag_of(a.val[i]) >= a.tmag;
-			else {
-				const double t = a.theta * __longlong_as_double((long long)a.rowmax[a.row[i]]);
-				k = mag_of(a.val[i]) >= mag_of(t);
-			}
-			k = k != (a.flip != 0);
-			keep[i] = k ? 1 : 0;
+	const uint32_t cnt = wave_tile_count(base, a.n, [&](uint64_t i) {
+		bool k;
+		if (PRED <= SPSAMD_SELECT_OFFDIAG) {
+			const long long diff = (long long)a.col[i] - (long long)a.row[i];
+			k = PRED == SPSAMD_SELECT_TRIL ? diff <= a.d : PRED == SPSAMD_SELECT_TRIU ? diff >= a.d :
+				PRED == SPSAMD_SELECT_DIAG ? diff == a.d : diff != a.d;
+		} else if (PRED == SPSAMD_SELECT_ABS_GE) k = mag_of(a.val[i]) >= a.tmag;
+		else {
+			const double t = a.theta * __longlong_as_double((long long)a.rowmax[a.row[i]]);
+			k = mag_of(a.val[i]) >= mag_of(t);
 		}
-		cnt += (uint32_t)__popcll(__ballot(k));
-	}
+		k = k != (a.flip != 0);
+		keep[i] = k ? 1 : 0;
+		return k;
+	});
 	if (lane_id() == 0) tile_count[tile] = cnt;
 }
 
 __global__ void __launch_bounds__(256) k_sel_count(const uint8_t *__restrict__ keep, uint32_t n, uint32_t *__restrict__ tile_count)
 {
 	const uint32_t tile = blockIdx.x * 4 + wave_id();
-	const uint64_t base = (uint64_t)tile * SEL_TILE;
+	const uint64_t base = (uint64_t)tile * WAVE_TILE;
 	if (base >= n) return;
-	uint32_t cnt = 0;
-#pragma unroll
-	for (int r = 0; r < SEL_ROUNDS; ++r) {
-		const uint64_t i = base + (uint64_t)r * 64 + lane_id();
-		cnt += (uint32_t)__popcll(__ballot(i < n && keep[i]));
-	}
+	const uint32_t cnt = wave_tile_count(base, n, [&](uint64_t i) { return keep[i] != 0; });
 	if (lane_id() == 0) tile_count[tile] = cnt;
 }
 
@@ -94,20 +79,10 @@ __global__ void __launch_bounds__(256) k_sel_compact(const int32_t *__restrict__
 	int32_t *__restrict__ orow, int32_t *__restrict__ ocol, double *__restrict__ oval)
 {
 	const uint32_t tile = blockIdx.x * 4 + wave_id();
-	const uint64_t base = (uint64_t)tile * SEL_TILE;
+	const uint64_t base = (uint64_t)tile * WAVE_TILE;
 	if (base >= n) return;
-	uint32_t o = tile_off[tile];
-#pragma unroll
-	for (int r = 0; r < SEL_ROUNDS; ++r) {
-		const uint64_t i = base + (uint64_t)r * 64 + lane_id();
-		const bool k = i < n && keep[i];
-		const uint64_t m = __ballot(k);
-		if (k) {
-			const uint32_t p = o + (uint32_t)__popcll(m & lanemask_lt());
-			orow[p] = row[i]; ocol[p] = col[i]; oval[p] = val[i];
-		}
-		o += (uint32_t)__popcll(m);
-	}
+	wave_range_compact(base, std::min<uint64_t>(base + WAVE_TILE, n), tile_off[tile], [&](uint64_t i) { return keep[i] != 0; },
+		[&](uint64_t i, uint32_t p) { orow[p] = row[i]; ocol[p] = col[i]; oval[p] = val[i]; });
 }
 
 // rowmax[r] = max of mag(v) over the non-NaN entries of row r (the array starts at 0): a segmented max scan across the wave
@@ -154,13 +129,12 @@ __global__ void __launch_bounds__(256) k_sel_classify(const uint32_t *__restrict
 	const int cls = n > k ? sel_class(n, path) : -1;
 #pragma unroll
 	for (int q = 0; q < 3; ++q) {
-		const uint64_t m = __ballot(cls == q);
-		if (!m) continue;                                      // uniform
-		const uint32_t tup = wave_reduce_sum<uint32_t>(cls == q ? n : 0u);
-		uint32_t at = 0;
-		if (lane_id() == 0) { at = atomicAdd(&cnt[q], (uint32_t)__popcll(m)); atomicAdd(&cnt[3 + q], tup); }
-		at = (uint32_t)__builtin_amdgcn_readfirstlane((int)at);
-		if (cls == q && q > 0) (q == 1 ? mid_list : heavy_list)[at + (uint32_t)__popcll(m & lanemask_lt())] = (uint32_t)r;
+		const bool in = cls == q;
+		if (!__ballot(in)) continue;                               // uniform
+		const uint32_t slot = wave_claim(&cnt[q], in);
+		const uint32_t tup = wave_reduce_sum<uint32_t>(in ? n : 0u);
+		if (lane_id() == 0) atomicAdd(&cnt[3 + q], tup);
+		if (in && q > 0) (q == 1 ? mid_list : heavy_list)[slot] = (uint32_t)r;
 	}
 }
 
@@ -320,8 +294,7 @@ void select_tuples(spsamd_ctx *c, const spsamd_coo *A, char transpose, int predi
 {
 	if (predicate < SPSAMD_SELECT_TRIL || predicate > SPSAMD_SELECT_ROW_TOPK) throw Error{SPSAMD_EINVAL, "unknown select predicate"};
 	if (select_flags & ~SPSAMD_SELECT_COMPLEMENT) throw Error{SPSAMD_EINVAL, "unknown select_flags"};
-	if (duplicate_policy < 0 || duplicate_policy > 2) throw Error{SPSAMD_EINVAL, "bad duplicate_policy"};
-	if (sink_kind != SPSAMD_SINK_COO && sink_kind != SPSAMD_SINK_DIGEST) throw Error{SPSAMD_EINVAL, "bad sink_kind"};
+	check_sink_args(duplicate_policy, sink_kind);
 	if ((predicate == SPSAMD_SELECT_ABS_GE || predicate == SPSAMD_SELECT_ROW_REL) && !(dparam >= 0))
 		throw Error{SPSAMD_EINVAL, "theta of a value predicate must be >= 0 and not NaN"};
 	if (predicate == SPSAMD_SELECT_ROW_TOPK && iparam < 0) throw Error{SPSAMD_EINVAL, "k of ROW_TOPK must be >= 0"};
@@ -347,7 +320,7 @@ void select_tuples(spsamd_ctx *c, const spsamd_coo *A, char transpose, int predi
 	res->nnz_a = n;
 	if (n == 0) return;
 
-	const uint32_t ntiles = (uint32_t)(((uint64_t)n + SEL_TILE - 1) / SEL_TILE);
+	const uint32_t ntiles = (uint32_t)(((uint64_t)n + WAVE_TILE - 1) / WAVE_TILE);
 	uint8_t *keep = c->arena.get<uint8_t>((size_t)n + 8);
 	uint32_t *tile_count = c->arena.get<uint32_t>((size_t)ntiles + 1), *tile_off = c->arena.get<uint32_t>((size_t)ntiles + 1);
 	SelArgs a;
@@ -392,19 +365,14 @@ void select_tuples(spsamd_ctx *c, const spsamd_coo *A, char transpose, int predi
 		break;
 	}
 	}
-	scan_exclusive_u32_u32(c, tile_count, tile_off, ntiles);
-	const uint32_t total = read_back(c, tile_off + ntiles);
-
-	const CooOut o = coo ? coo_output(c, total) : scratch_output(c, total);
+	uint32_t total;
+	const CooOut o = counted_output(c, tile_count, tile_off, ntiles, coo, &total);
 	if (total) {
 		k_sel_compact<<<dim3(grid_for(ntiles, 4)), dim3(256), 0, st>>>(S.row, S.col, S.val, n, keep, tile_off, o.row, o.col, o.val);
 		SPS_LAUNCH_CHECK();
 	}
-	res->nnz = total;
 	// a subsequence of S: in op(A)'s row order (read permuted: sorted by {1, 0}), indices checked
-	if (coo) publish_coo(c, res, o.row, o.col, o.val, total, permute);
-	else digest_stored(c, res, o.row, o.col, o.val, total, nrow, sink_flags);
-	finish_call(c, res);
+	deliver_stored(c, res, o, total, nrow, coo, permute, sink_flags);
 	SPS_HIP(hipEventElapsedTime(&res->ms_consolidate, c->ev[EV_BEGIN], c->ev[EV_CONSOLIDATED]));
 	SPS_HIP(hipEventElapsedTime(&res->ms_numeric, c->ev[EV_CONSOLIDATED], c->ev[EV_END]));
 }

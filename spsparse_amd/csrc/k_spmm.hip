@@ -60,12 +60,8 @@ __global__ void k_spmm_long_rows(const uint32_t *__restrict__ rowptr, uint64_t n
 {
 	const uint64_t row = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x;
 	const bool is_long = row < nrow && rowptr[row + 1] - rowptr[row] > long_min;
-	const uint64_t m = __ballot(is_long);
-	if (!m) return;
-	uint32_t base = 0;
-	if (lane_id() == 0) base = atomicAdd(count, (uint32_t)__popcll(m));
-	base = __shfl(base, 0, 64);
-	if (is_long) list[base + __popcll(m & lanemask_lt())] = (uint32_t)row;
+	const uint32_t slot = wave_claim(count, is_long);
+	if (is_long) list[slot] = (uint32_t)row;
 }
 
 // ---- lanes: one wave per long row, lane = right-hand side ---------------------------------------------------------

@@ -8,6 +8,12 @@
 
 namespace spsamd {
 
+void check_sink_args(int duplicate_policy, int sink_kind)
+{
+	if (duplicate_policy < 0 || duplicate_policy > 2) throw Error{SPSAMD_EINVAL, "bad duplicate_policy"};
+	if (sink_kind != SPSAMD_SINK_COO && sink_kind != SPSAMD_SINK_DIGEST) throw Error{SPSAMD_EINVAL, "bad sink_kind"};
+}
+
 bool output_set_aliased(const spsamd_ctx *c, int s, const spsamd_coo *const *operands, int n)
 {
 	for (int k = 0; k < n; ++k) {
@@ -41,6 +47,13 @@ CooOut scratch_output(spsamd_ctx *c, size_t total)
 {
 	int32_t *row = c->arena.get<int32_t>(total + 1), *col = c->arena.get<int32_t>(total + 1);
 	return CooOut{row, col, c->arena.get<double>(total + 1)};
+}
+
+CooOut counted_output(spsamd_ctx *c, const uint32_t *counts, uint32_t *offs, size_t n, bool coo, uint32_t *total)
+{
+	scan_exclusive_u32_u32(c, counts, offs, n);
+	*total = read_back(c, offs + n);
+	return coo ? coo_output(c, *total) : scratch_output(c, *total);
 }
 
 void publish_coo(spsamd_ctx *c, spsamd_result *res, const int32_t *orow, const int32_t *ocol, const double *oval, uint64_t total, bool permute)
@@ -106,6 +119,14 @@ void finish_call(spsamd_ctx *c, spsamd_result *res)
 	SPS_HIP(hipEventSynchronize(c->ev[EV_END]));
 	SPS_HIP(hipEventElapsedTime(&res->ms_total, c->ev[EV_BEGIN], c->ev[EV_END]));
 	res->workspace_bytes = c->arena.call_used;
+}
+
+void deliver_stored(spsamd_ctx *c, spsamd_result *res, const CooOut &o, uint32_t total, uint64_t nrow, bool coo, bool permute, int sink_flags)
+{
+	res->nnz = total;
+	if (coo) publish_coo(c, res, o.row, o.col, o.val, total, permute);
+	else digest_stored(c, res, o.row, o.col, o.val, total, nrow, sink_flags);
+	finish_call(c, res);
 }
 
 } // namespace spsamd
