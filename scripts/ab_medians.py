@@ -2,6 +2,7 @@
 """Table of medians of an alternating parent / branch run of the operation benchmarks (developer tool).
 
     python scripts/ab_medians.py DIR --condense ab_bench.jsonl     the four runs of every script, one line per row
+                                     [--scripts add,extract,dense]  (of these scripts only)
     python scripts/ab_medians.py ab_bench.jsonl                    the table
 
 DIR holds bench_<script>_<parent1|branch1|parent2|branch2>.jsonl, the JSON lines of scripts/bench_<script>.py run from two
@@ -21,8 +22,8 @@ SAME = ("tuples_in", "tuples_out", "same_tuples", "same_bits", "nnz_P", "nnz_PtA
 OURS = ("spsamd_", "emult_path", "extract")
 
 
-def condense(d):
-    for s in SCRIPTS:
+def condense(d, scripts=SCRIPTS):
+    for s in scripts:
         runs = []
         for tag in RUNS:
             rows = [json.loads(ln) for ln in open(os.path.join(d, "bench_%s_%s.jsonl" % (s, tag)))]
@@ -42,7 +43,8 @@ def condense(d):
 
 def main():
     src = sys.argv[1]
-    rows = list(condense(src)) if os.path.isdir(src) else [json.loads(ln) for ln in open(src)]
+    scripts = sys.argv[sys.argv.index("--scripts") + 1].split(",") if "--scripts" in sys.argv else SCRIPTS
+    rows = list(condense(src, scripts)) if os.path.isdir(src) else [json.loads(ln) for ln in open(src)]
     if "--condense" in sys.argv:
         with open(sys.argv[sys.argv.index("--condense") + 1], "w") as f:
             f.writelines(json.dumps(r) + "\n" for r in rows)

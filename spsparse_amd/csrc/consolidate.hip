@@ -207,18 +207,17 @@ void consolidate_operand(spsamd_ctx *c, const spsamd_coo *X, int lead, int ref_l
 	}
 
 	int mb = bits_of(out->ncol), Mb = bits_of(out->nrow);
-	uint64_t *keys0 = c->arena.get<uint64_t>(n), *keys1 = c->arena.get<uint64_t>(n);
-	uint32_t *pay0 = c->arena.get<uint32_t>(n), *pay1 = c->arena.get<uint32_t>(n);
-	build_keys(c, major, minor, n, mb, keys0);
+	PairSort sort(c, n);
+	build_keys(c, major, minor, n, mb, sort.keys);
 	// An operand that is STRICTLY in (minor, major) order -- a matrix kept sorted by rows and used with 'T', cfg5's R -- needs
 	// the stable passes over the MAJOR digits only: an LSD sort that skips the low digits leaves ties in input order, which is
 	// the minor order already (Galerkin 256^3, R^T: 3 passes instead of 6).  Strictly: no two tuples share their indices, so
 	// with no value to drop either the sorted tuples ARE the consolidated operand (no flag / compact / merge passes).
 	const int low_bit = (f & 4u) ? 0 : mb;
-	int where = radix_sort_pairs(c, keys0, pay0, keys1, pay1, n, mb + Mb, low_bit);
-	uint64_t *ks = where ? keys1 : keys0;
-	uint32_t *ps = where ? pay1 : pay0;
-	uint64_t *kk = where ? keys0 : keys1;      // the other key buffer is free now
+	sort.run(mb + Mb, low_bit);
+	uint64_t *ks = sort.keys;
+	uint32_t *ps = sort.perm;
+	uint64_t *kk = sort.spare_keys;            // the other key buffer is free now
 	if (!(f & 4u) && !(f & 8u)) {                  // nothing to drop and nothing to merge: the sorted tuples are the consolidated ones
 		out->row = c->arena.get<int32_t>(n);
 		out->col = c->arena.get<int32_t>(n);
@@ -310,11 +309,10 @@ uint32_t *sorted_permutation(spsamd_ctx *c, const spsamd_coo *X, int lead)
 	const int32_t *major = lead == 0 ? d0 : d1;
 	const int32_t *minor = lead == 0 ? d1 : d0;
 	int mb = bits_of(shape[1 - lead]), Mb = bits_of(shape[lead]);
-	uint64_t *keys0 = c->arena.get<uint64_t>(n), *keys1 = c->arena.get<uint64_t>(n);
-	uint32_t *pay0 = c->arena.get<uint32_t>(n), *pay1 = c->arena.get<uint32_t>(n);
-	build_keys(c, major, minor, n, mb, keys0);
-	int where = radix_sort_pairs(c, keys0, pay0, keys1, pay1, n, mb + Mb);
-	return where ? pay1 : pay0;
+	PairSort sort(c, n);
+	build_keys(c, major, minor, n, mb, sort.keys);
+	sort.run(mb + Mb);
+	return sort.perm;
 }
 
 // ------------------------------------------------------------------ dim_beginnings

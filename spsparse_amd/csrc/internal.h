@@ -134,6 +134,22 @@ struct spsamd_ctx {
 
 namespace spsamd {
 
+// While one of these lives, c->stream is a side stream of the context, so that every helper launches there: `which` 0
+// the second stream (ev_side, wm_pending), 1 the third (ev_side2, sort_pending).  On entry the side stream waits for the
+// fork event [0] -- recorded on the main stream here (`record_fork`), or earlier by the caller -- and the pending flag is
+// set; on every way out, an exception included, c->stream is the main stream again and the join event [1] is recorded
+// behind what was launched, for spsamd_ctx::join_side.  Nothing else assigns c->stream after spsamd_ctx_create.
+struct SideScope {
+	SideScope(spsamd_ctx *c, int which, bool record_fork);
+	~SideScope();
+	SideScope(const SideScope &) = delete;
+	SideScope &operator=(const SideScope &) = delete;
+private:
+	spsamd_ctx *c;
+	hipStream_t main, side;
+	hipEvent_t join;
+};
+
 // What each event of spsamd_ctx::ev marks for the multiply.  The stand-alone operations share 0, 1 and 7 and reuse 2 and
 // 3 for stages of their own: k_masked.hip for the begin and end of its numeric kernels, k_stream.hip 2 for its set-up done.
 enum Ev {
@@ -156,7 +172,7 @@ enum Ev2 { EV2_TILES_BEGIN = 0, EV2_TILES_END = 1, EV2_DIRECT_END = 2 };   // th
 void scan_exclusive_u32_i64(spsamd_ctx *c, const uint32_t *in, int64_t *out, size_t n);
 void scan_exclusive_u32_u32(spsamd_ctx *c, const uint32_t *in, uint32_t *out, size_t n);
 void scan_exclusive_u8_u32(spsamd_ctx *c, const uint8_t *in, uint32_t *out, size_t n);
-void scan_exclusive_u16_u32(spsamd_ctx *c, const uint16_t *in, uint32_t *out, size_t n);
+void scan_exclusive_u64_u64(spsamd_ctx *c, const unsigned long long *in, unsigned long long *out, size_t n);
 
 // The same for up to SCAN_BATCH_MAX arrays of one length in three launches (blockIdx.y = array): the symbolic phase
 // scans a dozen per-row counters of the heavy rows, and a launch is worth more than the work at that size.
@@ -172,11 +188,21 @@ struct WordList { const uint32_t *p[WORD_LIST_MAX]; int count = 0;
 	int add64(const void *q) { const int at = add(q); add((const uint32_t *)q + 1); return at; } };
 void read_back_words(spsamd_ctx *c, const WordList &w, uint32_t *host);
 
-// Stable LSD radix sort of (key, payload) pairs on key bits [low_bit, key_bits) (a caller whose input is already in the
-// order of the low bits skips their passes).
-// Returns which of the two buffer pairs holds the result (0: keys0/pay0, 1: keys1/pay1).
-int radix_sort_pairs(spsamd_ctx *c, uint64_t *keys0, uint32_t *pay0, uint64_t *keys1, uint32_t *pay1,
-	size_t n, int key_bits, int low_bit = 0);
+// The frame of every sort by key: the two key and two payload buffers out of the workspace (allocated by the constructor:
+// keys, keys, payloads, payloads, n entries each), the caller's keys in `keys`, then run(): a stable LSD radix sort on key
+// bits [low_bit, key_bits) (a caller whose input is already in the order of the low bits skips their passes).  The
+// payload is the storage position, so what comes out is the sorted keys and the stable permutation that sorts them.
+struct PairSort {
+	uint64_t *keys;          // before run(): the n keys to fill | after: the keys, sorted
+	uint32_t *perm;          // after run(): perm[i] = the input position of sorted key i
+	uint64_t *spare_keys;    // after run(): the other pair of buffers, free for the caller
+	uint32_t *spare_pay;
+	PairSort(spsamd_ctx *c, size_t n);
+	void run(int key_bits, int low_bit = 0);
+private:
+	spsamd_ctx *c;
+	size_t n;
+};
 
 void fill_u32(spsamd_ctx *c, uint32_t *p, uint32_t v, size_t n);
 void fill_zero(spsamd_ctx *c, void *p, size_t bytes);

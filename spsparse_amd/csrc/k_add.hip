@@ -242,13 +242,12 @@ static void add_stream(spsamd_ctx *c, const spsamd_coo *X, int lead, bool force_
 	// one stable radix sort on (major, minor), storage position as payload; the indices come back out of the sorted keys,
 	// so only the value is gathered from storage
 	const int mb = bits_of(shape[1 - lead]), Mb = bits_of(shape[lead]);
-	uint64_t *keys0 = c->arena.get<uint64_t>(n), *keys1 = c->arena.get<uint64_t>(n);
-	uint32_t *pay0 = c->arena.get<uint32_t>(n), *pay1 = c->arena.get<uint32_t>(n);
-	build_keys(c, major, minor, n, mb, keys0);
-	const int where = radix_sort_pairs(c, keys0, pay0, keys1, pay1, n, mb + Mb, low_bit < 0 ? mb : 0);
+	PairSort sort(c, n);
+	build_keys(c, major, minor, n, mb, sort.keys);
+	sort.run(mb + Mb, low_bit < 0 ? mb : 0);
 	int32_t *row = c->arena.get<int32_t>(n), *col = c->arena.get<int32_t>(n);
 	double *val = c->arena.get<double>(n);
-	gather_sorted(c, where ? keys1 : keys0, where ? pay1 : pay0, dv, n, mb, row, col, val);
+	gather_sorted(c, sort.keys, sort.perm, dv, n, mb, row, col, val);
 	out->row = row; out->col = col; out->val = val; out->n = (uint32_t)n;
 	*sorted = true;
 }

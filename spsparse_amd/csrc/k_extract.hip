@@ -526,17 +526,16 @@ void extract_tuples(spsamd_ctx *c, const spsamd_coo *A, char transpose, const in
 	a.map.inv = inv;
 	if (j_repeats) {                                               // J as a CSR by source column
 		map = EXT_MAP_CSR;
-		uint64_t *k0 = c->arena.get<uint64_t>(nC), *k1 = c->arena.get<uint64_t>(nC);
-		uint32_t *p0 = c->arena.get<uint32_t>(nC), *p1 = c->arena.get<uint32_t>(nC);
-		k_ext_list_keys<<<dim3(grid_for(nC)), dim3(256), 0, st>>>(dJ, (uint32_t)nC, k0);
+		PairSort sort(c, nC);
+		k_ext_list_keys<<<dim3(grid_for(nC)), dim3(256), 0, st>>>(dJ, (uint32_t)nC, sort.keys);
 		SPS_LAUNCH_CHECK();
-		const int where = radix_sort_pairs(c, k0, p0, k1, p1, nC, bits_of(ncolS));
+		sort.run(bits_of(ncolS));
 		ConMat jm;
 		jm.row = c->arena.get<int32_t>(nC); jm.nnz = (uint32_t)nC; jm.nrow = ncolS;
-		k_ext_low32<<<dim3(grid_for(nC)), dim3(256), 0, st>>>(where ? k1 : k0, (uint32_t)nC, jm.row);
+		k_ext_low32<<<dim3(grid_for(nC)), dim3(256), 0, st>>>(sort.keys, (uint32_t)nC, jm.row);
 		SPS_LAUNCH_CHECK();
 		a.map.jptr = dense_rowptr(c, jm, 0);
-		a.map.jout = where ? p1 : p0;
+		a.map.jout = sort.perm;
 	}
 
 	// count, scan
@@ -576,14 +575,14 @@ void extract_tuples(spsamd_ctx *c, const spsamd_coo *A, char transpose, const in
 			uint32_t *hoff = c->arena.get<uint32_t>((size_t)nh + 1);
 			scan_exclusive_u32_u32(c, heavy_len, hoff, nh);
 			const int cb = bits_of(nC);
-			uint64_t *k0 = c->arena.get<uint64_t>(th), *k1 = c->arena.get<uint64_t>(th);
-			uint32_t *p0 = c->arena.get<uint32_t>(th), *p1 = c->arena.get<uint32_t>(th), *pos0 = c->arena.get<uint32_t>(th);
-			k_ext_heavy_keys<<<dim3(nh), dim3(256), 0, st>>>(heavy_list, hoff, a.cnt, off, o.col, cb, k0, pos0);
+			PairSort sort(c, th);
+			uint32_t *pos0 = c->arena.get<uint32_t>(th);
+			k_ext_heavy_keys<<<dim3(nh), dim3(256), 0, st>>>(heavy_list, hoff, a.cnt, off, o.col, cb, sort.keys, pos0);
 			SPS_LAUNCH_CHECK();
-			const int where = radix_sort_pairs(c, k0, p0, k1, p1, th, cb + bits_of(nh));
+			sort.run(cb + bits_of(nh));
 			int32_t *tc = c->arena.get<int32_t>(th);
 			double *tv = c->arena.get<double>(th);
-			k_ext_heavy_gather<<<dim3(grid_for(th)), dim3(256), 0, st>>>(where ? k1 : k0, where ? p1 : p0, pos0, o.val, th, cb, tc, tv);
+			k_ext_heavy_gather<<<dim3(grid_for(th)), dim3(256), 0, st>>>(sort.keys, sort.perm, pos0, o.val, th, cb, tc, tv);
 			SPS_LAUNCH_CHECK();
 			k_ext_heavy_scatter<<<dim3(grid_for(th)), dim3(256), 0, st>>>(tc, tv, pos0, th, o.col, o.val);
 			SPS_LAUNCH_CHECK();

@@ -252,13 +252,12 @@ void dense_operand(spsamd_ctx *c, const spsamd_coo *M, int lead, DenseOperand *o
 		rows.row = const_cast<int32_t *>(major);
 	} else {
 		// one stable radix pass set keyed on the output row alone, storage position as payload
-		uint64_t *keys0 = c->arena.get<uint64_t>(n), *keys1 = c->arena.get<uint64_t>(n);
-		uint32_t *pay0 = c->arena.get<uint32_t>(n), *pay1 = c->arena.get<uint32_t>(n);
-		k_row_keys<<<dim3(grid_for(n)), dim3(256), 0, c->stream>>>(major, (uint32_t)n, keys0);
+		PairSort sort(c, n);
+		k_row_keys<<<dim3(grid_for(n)), dim3(256), 0, c->stream>>>(major, (uint32_t)n, sort.keys);
 		SPS_LAUNCH_CHECK();
-		const int where = radix_sort_pairs(c, keys0, pay0, keys1, pay1, n, bits_of(out->nrow));
+		sort.run(bits_of(out->nrow));
 		int32_t *srow = c->arena.get<int32_t>(n);
-		k_gather_rows<<<dim3(grid_for(n)), dim3(256), 0, c->stream>>>(where ? keys1 : keys0, where ? pay1 : pay0, minor, dv, (uint32_t)n, srow, tup);
+		k_gather_rows<<<dim3(grid_for(n)), dim3(256), 0, c->stream>>>(sort.keys, sort.perm, minor, dv, (uint32_t)n, srow, tup);
 		SPS_LAUNCH_CHECK();
 		rows.row = srow;
 		out->sorted = true;

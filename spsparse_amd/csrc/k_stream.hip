@@ -5,7 +5,8 @@
 //
 // Once per call: consolidation of both operands, the scale vectors, B's derived structures (row pointer, packed tuples and --
 // where a row may be heavy -- the column-window index; the window-major copy is built by the first block with a heavy row
-// and kept), the per-row bounds, their scan and the block boundaries.  Per block: the numeric pipeline on a row slice of A.
+// and kept), the per-row bounds, their scan (prims.hip's, 64 bits in and out: this file has no scan kernel of its own) and
+// the block boundaries.  Per block: the numeric pipeline on a row slice of A.
 //
 // Threads: a worker thread computes the blocks in order (the pipeline synchronises with the host between its stages); the
 // calling thread copies each finished block to pinned staging on a copy stream of its own, chunk by chunk, and calls the
@@ -60,82 +61,6 @@ __global__ void k_stream_row_bound(const uint32_t *aptr, const int64_t *pref, ui
 		if (p > *(volatile unsigned long long *)&bs->max_p) atomicMax(&bs->max_p, p);
 		if (h) atomicAdd(&bs->heavy, h);
 	}
-}
-
-// ====================================================================== 64-bit exclusive scan (out: n + 1 entries)
-
-constexpr int SC_NT = 256, SC_IT = 4, SC_TILE = SC_NT * SC_IT;
-
-// exclusive scan of one value per thread over the workgroup; *total: the sum of all
-__device__ __forceinline__ unsigned long long block_exclusive_u64(unsigned long long v, unsigned long long *s_w, unsigned long long *total)
-{
-	unsigned long long inc = v;
-#pragma unroll
-	for (int d = 1; d < 64; d <<= 1) {
-		const unsigned long long o = __shfl_up(inc, d, 64);
-		if ((int)lane_id() >= d) inc += o;
-	}
-	const unsigned w = threadIdx.x >> 6;
-	if (lane_id() == 63) s_w[w] = inc;
-	__syncthreads();
-	unsigned long long before = 0, all = 0;
-	for (unsigned q = 0; q < SC_NT / 64; ++q) { if (q < w) before += s_w[q]; all += s_w[q]; }
-	__syncthreads();
-	*total = all;
-	return before + inc - v;
-}
-
-__global__ __launch_bounds__(SC_NT) void k_scan64_tiles(const unsigned long long *in, uint64_t n, unsigned long long *out, unsigned long long *tsum)
-{
-	__shared__ unsigned long long s_w[SC_NT / 64];
-	const uint64_t base = (uint64_t)blockIdx.x * SC_TILE + (uint64_t)threadIdx.x * SC_IT;
-	unsigned long long x[SC_IT], s = 0;
-#pragma unroll
-	for (int q = 0; q < SC_IT; ++q) { x[q] = base + q < n ? in[base + q] : 0ull; s += x[q]; }
-	unsigned long long total;
-	unsigned long long run = block_exclusive_u64(s, s_w, &total);
-#pragma unroll
-	for (int q = 0; q < SC_IT; ++q) { if (base + q < n) out[base + q] = run; run += x[q]; }
-	if (threadIdx.x == 0) tsum[blockIdx.x] = total;
-}
-
-// one workgroup: the tiles' sums scanned in place (exclusive), tsum[ntile] = the grand total
-__global__ __launch_bounds__(SC_NT) void k_scan64_top(unsigned long long *tsum, uint64_t ntile)
-{
-	__shared__ unsigned long long s_w[SC_NT / 64];
-	unsigned long long carry = 0;
-	for (uint64_t b0 = 0; b0 < ntile; b0 += SC_NT) {
-		const uint64_t t = b0 + threadIdx.x;
-		const unsigned long long v = t < ntile ? tsum[t] : 0ull;
-		unsigned long long total;
-		const unsigned long long ex = block_exclusive_u64(v, s_w, &total);
-		if (t < ntile) tsum[t] = carry + ex;
-		carry += total;
-	}
-	if (threadIdx.x == 0) tsum[ntile] = carry;
-}
-
-__global__ __launch_bounds__(SC_NT) void k_scan64_add(unsigned long long *out, uint64_t n, const unsigned long long *tsum, uint64_t ntile)
-{
-	const uint64_t base = (uint64_t)blockIdx.x * SC_TILE + (uint64_t)threadIdx.x * SC_IT;
-	const unsigned long long add = tsum[blockIdx.x];
-#pragma unroll
-	for (int q = 0; q < SC_IT; ++q) if (base + q < n) out[base + q] += add;
-	if (blockIdx.x == 0 && threadIdx.x == 0) out[n] = tsum[ntile];
-}
-
-static void scan_exclusive_u64(spsamd_ctx *c, const unsigned long long *in, unsigned long long *out, uint64_t n)
-{
-	const uint64_t ntile = (n + SC_TILE - 1) / SC_TILE;
-	unsigned long long *tsum = c->arena.get<unsigned long long>(ntile + 1);
-	if (ntile) {
-		k_scan64_tiles<<<dim3((unsigned)ntile), dim3(SC_NT), 0, c->stream>>>(in, n, out, tsum);
-		SPS_LAUNCH_CHECK();
-	}
-	k_scan64_top<<<dim3(1), dim3(SC_NT), 0, c->stream>>>(tsum, ntile);
-	SPS_LAUNCH_CHECK();
-	k_scan64_add<<<dim3((unsigned)std::max<uint64_t>(ntile, 1)), dim3(SC_NT), 0, c->stream>>>(out, n, tsum, ntile);
-	SPS_LAUNCH_CHECK();
 }
 
 // ====================================================================== block boundaries
@@ -285,7 +210,7 @@ int multiply_stream(spsamd_ctx *c, double C,
 		throw Error{SPSAMD_ECAPACITY, buf};
 	}
 	unsigned long long *S = c->arena.get<unsigned long long>(n + 1);
-	scan_exclusive_u64(c, bound, S, n);
+	scan_exclusive_u64_u64(c, bound, S, n);                 // S[n] = the sum of all bounds
 	uint32_t *next = c->arena.get<uint32_t>(n);
 	k_stream_next<<<dim3(grid_for(n)), dim3(256), 0, s0>>>(S, n, budget, next);
 	SPS_LAUNCH_CHECK();

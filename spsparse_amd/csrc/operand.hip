@@ -165,13 +165,16 @@ void mask_keys(spsamd_ctx *c, const spsamd_coo *M, int lead, uint64_t nrow, uint
 		throw Error{SPSAMD_EINVAL, "pattern operand claims op()'s row order but its (row, col) keys are not in that order"};
 	if (!(f & 6u)) { out->i = r; out->j = cc; out->n = (uint32_t)n; return; }      // in order, no repeats: read in place
 	const int cb = bits_of(ncol), rb = bits_of(nrow);
-	uint64_t *keys0 = c->arena.get<uint64_t>(n);
-	build_keys(c, r, cc, n, cb, keys0);
-	const uint64_t *keys = keys0;
+	const uint64_t *keys;
 	if (f & 2u) {
-		uint64_t *keys1 = c->arena.get<uint64_t>(n);
-		uint32_t *pay0 = c->arena.get<uint32_t>(n), *pay1 = c->arena.get<uint32_t>(n);
-		keys = radix_sort_pairs(c, keys0, pay0, keys1, pay1, n, cb + rb) ? keys1 : keys0;
+		PairSort sort(c, n);
+		build_keys(c, r, cc, n, cb, sort.keys);
+		sort.run(cb + rb);
+		keys = sort.keys;
+	} else {                                         // in order with repeats: the keys as they stand
+		uint64_t *k = c->arena.get<uint64_t>(n);
+		build_keys(c, r, cc, n, cb, k);
+		keys = k;
 	}
 	uint8_t *first = c->arena.get<uint8_t>(n);
 	uint32_t *off = c->arena.get<uint32_t>(n + 1);

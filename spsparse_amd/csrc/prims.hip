@@ -1,10 +1,19 @@
-// prims.hip -- workspace arena, device-wide exclusive scan, stable LSD radix sort.
+// prims.hip -- workspace arena, device-wide exclusive scan, stable LSD radix sort, side-stream scope.
 //
 // These replace, on the device, what the reference gets from the STL on the
 // host: std::stable_sort on a permutation (algorithm.hpp:411-427) and the
 // running offsets of its linear passes.  Hand-written for gfx950 (wave64).
+//
+// Each idiom is written once here and called by the layers above:
+//   scan   one tile-sum body and one tile-write body (scan_tile_sum, scan_tile_write) under every scan_exclusive_* -- u8, u32
+//          and u64 input, u32, i64 and u64 output -- and under the batched scan of the heavy rows' counters
+//   sort   PairSort: the two key and two payload buffers, the sort, and which pair came out; radix_sort_pairs has no
+//          other caller
+//   side   SideScope, beside spsamd_ctx::join_side: the one place after spsamd_ctx_create that points c->stream elsewhere
 #include "internal.h"
 #include "devutil.h"
+
+#include <utility>
 
 namespace spsamd {
 
@@ -138,6 +147,22 @@ void spsamd_ctx::join_side(bool wm, bool sort)
 	if (sort && sort_pending) { sort_pending = false; (void)hipStreamWaitEvent(stream, ev_side2[1], 0); }
 }
 
+spsamd::SideScope::SideScope(spsamd_ctx *c, int which, bool record_fork)
+	: c(c), main(c->stream), side(which ? c->side2 : c->side), join((which ? c->ev_side2 : c->ev_side)[1])
+{
+	const hipEvent_t fork = (which ? c->ev_side2 : c->ev_side)[0];
+	if (record_fork) SPS_HIP(hipEventRecord(fork, main));
+	SPS_HIP(hipStreamWaitEvent(side, fork, 0));
+	(which ? c->sort_pending : c->wm_pending) = true;      // from here on the main stream must wait for the side stream before this call ends, whatever happens
+	c->stream = side;
+}
+
+spsamd::SideScope::~SideScope()
+{
+	c->stream = main;
+	(void)hipEventRecord(join, side);
+}
+
 void *spsamd_ctx::host_staging(size_t bytes)
 {
 	if (bytes > pinned_cap) {
@@ -185,11 +210,15 @@ constexpr int SCAN_NT = 256;
 constexpr int SCAN_ITEMS = 4;     // consecutive elements per thread (8 and 16 measured slower: the strided reads coalesce worse; 2 the same)
 constexpr int SCAN_TILE = SCAN_NT * SCAN_ITEMS;
 
+// The two bodies every scan below is made of, written once: `in` / `out` are ONE array's, however the kernel around
+// them found it (the single-array kernels by their arguments, the batched ones by blockIdx.y).
+
+// *sum = the sum of tile `tile` of in[0, n)
 template <class TIn, class TOut>
-__global__ __launch_bounds__(SCAN_NT) void k_scan_tile_sums(const TIn *in, size_t n, TOut *sums)
+__device__ __forceinline__ void scan_tile_sum(const TIn *in, size_t n, unsigned tile, TOut *sum)
 {
 	__shared__ TOut scratch[SCAN_NT / 64 + 1];
-	size_t base = (size_t)blockIdx.x * SCAN_TILE;
+	size_t base = (size_t)tile * SCAN_TILE;
 	TOut s = 0;
 #pragma unroll
 	for (int q = 0; q < SCAN_ITEMS; ++q) {
@@ -202,17 +231,17 @@ __global__ __launch_bounds__(SCAN_NT) void k_scan_tile_sums(const TIn *in, size_
 	if (threadIdx.x == 0) {
 		TOut t = 0;
 		for (int w = 0; w < SCAN_NT / 64; ++w) t += scratch[w];
-		sums[blockIdx.x] = t;
+		*sum = t;
 	}
 }
 
-// out[i] = tile_off[tile] + exclusive prefix inside the tile; the thread that
-// owns element n-1 also writes out[n] = grand total.
+// out[i] = off + exclusive prefix inside tile `tile` (off: the sum of the tiles before it); the thread that owns element
+// n-1 also writes out[n] = grand total.
 template <class TIn, class TOut>
-__global__ __launch_bounds__(SCAN_NT) void k_scan_tiles(const TIn *in, size_t n, const TOut *tile_off, TOut *out)
+__device__ __forceinline__ void scan_tile_write(const TIn *in, size_t n, unsigned tile, TOut off, TOut *out)
 {
 	__shared__ TOut scratch[SCAN_NT / 64 + 1];
-	size_t base = (size_t)blockIdx.x * SCAN_TILE + (size_t)threadIdx.x * SCAN_ITEMS;
+	size_t base = (size_t)tile * SCAN_TILE + (size_t)threadIdx.x * SCAN_ITEMS;
 	TOut v[SCAN_ITEMS];
 	TOut s = 0;
 #pragma unroll
@@ -221,8 +250,7 @@ __global__ __launch_bounds__(SCAN_NT) void k_scan_tiles(const TIn *in, size_t n,
 		v[q] = i < n ? (TOut)in[i] : (TOut)0;
 		s += v[q];
 	}
-	TOut ex = block_exclusive_scan<TOut, SCAN_NT>(s, scratch, (TOut *)nullptr);
-	TOut run = ex + (tile_off ? tile_off[blockIdx.x] : (TOut)0);
+	TOut run = off + block_exclusive_scan<TOut, SCAN_NT>(s, scratch, (TOut *)nullptr);
 #pragma unroll
 	for (int q = 0; q < SCAN_ITEMS; ++q) {
 		size_t i = base + q;
@@ -232,6 +260,20 @@ __global__ __launch_bounds__(SCAN_NT) void k_scan_tiles(const TIn *in, size_t n,
 			if (i == n - 1) out[n] = run;
 		}
 	}
+}
+
+// ---- one array: the tile sums are scanned by the same two kernels, recursively (one launch where n <= SCAN_TILE) ----
+
+template <class TIn, class TOut>
+__global__ __launch_bounds__(SCAN_NT) void k_scan_tile_sums(const TIn *in, size_t n, TOut *sums)
+{
+	scan_tile_sum(in, n, blockIdx.x, sums + blockIdx.x);
+}
+
+template <class TIn, class TOut>
+__global__ __launch_bounds__(SCAN_NT) void k_scan_tiles(const TIn *in, size_t n, const TOut *tile_off, TOut *out)
+{
+	scan_tile_write(in, n, blockIdx.x, tile_off ? tile_off[blockIdx.x] : (TOut)0, out);
 }
 
 template <class TIn, class TOut>
@@ -257,29 +299,13 @@ static void scan_exclusive(spsamd_ctx *c, const TIn *in, TOut *out, size_t n)
 void scan_exclusive_u32_i64(spsamd_ctx *c, const uint32_t *in, int64_t *out, size_t n) { scan_exclusive<uint32_t, int64_t>(c, in, out, n); }
 void scan_exclusive_u32_u32(spsamd_ctx *c, const uint32_t *in, uint32_t *out, size_t n) { scan_exclusive<uint32_t, uint32_t>(c, in, out, n); }
 void scan_exclusive_u8_u32(spsamd_ctx *c, const uint8_t *in, uint32_t *out, size_t n) { scan_exclusive<uint8_t, uint32_t>(c, in, out, n); }
-void scan_exclusive_u16_u32(spsamd_ctx *c, const uint16_t *in, uint32_t *out, size_t n) { scan_exclusive<uint16_t, uint32_t>(c, in, out, n); }
+void scan_exclusive_u64_u64(spsamd_ctx *c, const unsigned long long *in, unsigned long long *out, size_t n) { scan_exclusive<unsigned long long, unsigned long long>(c, in, out, n); }
 
-// ---- batched: arrays b.in[y] -> b.out[y], y = blockIdx.y ----
+// ---- batched: arrays b.in[y] -> b.out[y], y = blockIdx.y; every array's tile sums scanned by one workgroup ----
 
 __global__ __launch_bounds__(SCAN_NT) void k_scan_tile_sums_batch(ScanBatch b, size_t n, uint32_t *sums, uint32_t ntiles)
 {
-	__shared__ uint32_t scratch[SCAN_NT / 64 + 1];
-	const uint32_t *in = b.in[blockIdx.y];
-	size_t base = (size_t)blockIdx.x * SCAN_TILE;
-	uint32_t s = 0;
-#pragma unroll
-	for (int q = 0; q < SCAN_ITEMS; ++q) {
-		size_t i = base + (size_t)q * SCAN_NT + threadIdx.x;
-		if (i < n) s += in[i];
-	}
-	s = wave_reduce_sum(s);
-	if (lane_id() == 0) scratch[wave_id()] = s;
-	__syncthreads();
-	if (threadIdx.x == 0) {
-		uint32_t t = 0;
-		for (int w = 0; w < SCAN_NT / 64; ++w) t += scratch[w];
-		sums[(size_t)blockIdx.y * ntiles + blockIdx.x] = t;
-	}
+	scan_tile_sum(b.in[blockIdx.y], n, blockIdx.x, sums + (size_t)blockIdx.y * ntiles + blockIdx.x);
 }
 
 // one workgroup per array: exclusive scan of its ntiles tile sums, in place
@@ -301,29 +327,7 @@ __global__ __launch_bounds__(SCAN_NT) void k_scan_sums_batch(uint32_t *sums, uin
 
 __global__ __launch_bounds__(SCAN_NT) void k_scan_tiles_batch(ScanBatch b, size_t n, const uint32_t *tile_off, uint32_t ntiles)
 {
-	__shared__ uint32_t scratch[SCAN_NT / 64 + 1];
-	const uint32_t *in = b.in[blockIdx.y];
-	uint32_t *out = b.out[blockIdx.y];
-	size_t base = (size_t)blockIdx.x * SCAN_TILE + (size_t)threadIdx.x * SCAN_ITEMS;
-	uint32_t v[SCAN_ITEMS];
-	uint32_t s = 0;
-#pragma unroll
-	for (int q = 0; q < SCAN_ITEMS; ++q) {
-		size_t i = base + q;
-		v[q] = i < n ? in[i] : 0u;
-		s += v[q];
-	}
-	uint32_t ex = block_exclusive_scan<uint32_t, SCAN_NT>(s, scratch, (uint32_t *)nullptr);
-	uint32_t run = ex + tile_off[(size_t)blockIdx.y * ntiles + blockIdx.x];
-#pragma unroll
-	for (int q = 0; q < SCAN_ITEMS; ++q) {
-		size_t i = base + q;
-		if (i < n) {
-			out[i] = run;
-			run += v[q];
-			if (i == n - 1) out[n] = run;
-		}
-	}
+	scan_tile_write(b.in[blockIdx.y], n, blockIdx.x, tile_off[(size_t)blockIdx.y * ntiles + blockIdx.x], b.out[blockIdx.y]);
 }
 
 void scan_exclusive_u32_batch(spsamd_ctx *c, const ScanBatch &b, size_t n)
@@ -501,13 +505,30 @@ static int radix_sort_pairs_bits(spsamd_ctx *c, uint64_t *keys0, uint32_t *pay0,
 	return where;
 }
 
-int radix_sort_pairs(spsamd_ctx *c, uint64_t *keys0, uint32_t *pay0, uint64_t *keys1, uint32_t *pay1, size_t n, int key_bits, int low_bit)
+// Stable LSD radix sort of (key, payload) pairs on key bits [low_bit, key_bits); the payload that comes out is the
+// permutation.  Returns which of the two buffer pairs holds the result (0: keys0/pay0, 1: keys1/pay1): PairSort::run
+// below is its one caller and the one place that decodes it.
+static int radix_sort_pairs(spsamd_ctx *c, uint64_t *keys0, uint32_t *pay0, uint64_t *keys1, uint32_t *pay1, size_t n, int key_bits, int low_bit)
 {
 	if (n == 0) return 0;
 	if (low_bit < 0 || low_bit > key_bits) low_bit = 0;
 	// (10-bit digits save a pass on 40-bit keys but each pass is 35 % slower on MI355X -- the counters' LDS leaves two
 	// workgroups per CU instead of three: 1.51 against 1.40 ms for 1.7e7 pairs -- so 8 bits it stays)
 	return radix_sort_pairs_bits<8>(c, keys0, pay0, keys1, pay1, n, key_bits, low_bit);
+}
+
+PairSort::PairSort(spsamd_ctx *c, size_t n) : c(c), n(n)
+{
+	keys = c->arena.get<uint64_t>(n); spare_keys = c->arena.get<uint64_t>(n);
+	perm = c->arena.get<uint32_t>(n); spare_pay = c->arena.get<uint32_t>(n);
+}
+
+void PairSort::run(int key_bits, int low_bit)
+{
+	if (radix_sort_pairs(c, keys, perm, spare_keys, spare_pay, n, key_bits, low_bit)) {
+		std::swap(keys, spare_keys);
+		std::swap(perm, spare_pay);
+	}
 }
 
 } // namespace spsamd

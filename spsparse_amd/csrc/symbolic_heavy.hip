@@ -542,13 +542,10 @@ void heavy_prepare(spsamd_ctx *c, Heavy &hv, const Bins &bins, const RowMeta &m,
 	// before the dense cells' kernel (spsamd_ctx::join_side) -- or, whatever happens, before the call ends (spgemm_once).
 	if (!c->tune.no_wmajor && have_wmajor) { hv.wptr = pb->wptr; hv.btw = pb->btw; }
 	else if (!c->tune.no_wmajor) {
-		SPS_HIP(hipEventRecord(c->ev_side[0], st));
-		SPS_HIP(hipStreamWaitEvent(c->side, c->ev_side[0], 0));
-		c->wm_pending = true;                                       // from here on the main stream must wait for the side stream before this call ends, whatever happens
-		c->stream = c->side;                                        // (the helpers launch on c->stream)
-		try { heavy_window_major(c, hv, B, wshift, wcnt, nwp, pb); } catch (...) { c->stream = st; (void)hipEventRecord(c->ev_side[1], c->side); throw; }
-		c->stream = st;
-		SPS_HIP(hipEventRecord(c->ev_side[1], c->side));
+		{
+			SideScope on_side(c, 0, true);                          // (the inputs are ready now: the fork event is recorded here)
+			heavy_window_major(c, hv, B, wshift, wcnt, nwp, pb);
+		}
 		pb->wptr = hv.wptr; pb->btw = hv.btw;
 	}
 	uint32_t *hubcount = c->arena.get<uint32_t>(1);
@@ -695,41 +692,32 @@ void heavy_cells(spsamd_ctx *c, Heavy &hv, const RowMeta &m, const uint32_t *seg
 // kernel that walks a list.
 void heavy_sort_lists(spsamd_ctx *c, Heavy &hv)
 {
-	hipStream_t st = c->stream;
 	int wbits = 1;                                   // bits of a window index: the cell lists are sorted on as few digits as needed
 	while ((1u << wbits) < hv.nwin) ++wbits;
-	SPS_HIP(hipStreamWaitEvent(c->side2, c->ev_side2[0], 0));       // (recorded after the cells were emitted)
-	c->sort_pending = true;
-	struct OnSide2 {
-		spsamd_ctx *c; hipStream_t main;
-		~OnSide2() { c->stream = main; (void)hipEventRecord(c->ev_side2[1], c->side2); }
-	} on_side2{c, st};
-	c->stream = c->side2;
-	st = c->side2;
+	SideScope on_side2(c, 1, false);                 // (its fork event was recorded after the cells were emitted: heavy_cells)
+	hipStream_t st = c->stream;
 	for (int kd = 0; kd < 2; ++kd) {
 		TileBases &t = kd ? hv.tb2 : hv.tb;
 		const uint32_t nd = kd ? hv.ntile2 : hv.ntile;
 		if (nd < 2) continue;
-		uint64_t *k0 = c->arena.get<uint64_t>(nd), *k1 = c->arena.get<uint64_t>(nd);
-		uint32_t *p0 = c->arena.get<uint32_t>(nd), *p1 = c->arena.get<uint32_t>(nd);
-		k_tile_keys<<<dim3(grid_for(nd)), dim3(256), 0, st>>>(t.tiles, nd, k0);
+		PairSort sort(c, nd);
+		k_tile_keys<<<dim3(grid_for(nd)), dim3(256), 0, st>>>(t.tiles, nd, sort.keys);
 		SPS_LAUNCH_CHECK();
-		int where = radix_sort_pairs(c, k0, p0, k1, p1, nd, wbits);
+		sort.run(wbits);
 		Tile *sorted = c->arena.get<Tile>(nd);
-		k_gather_tiles<<<dim3(grid_for(nd)), dim3(256), 0, st>>>(t.tiles, where ? p1 : p0, nd, sorted);
+		k_gather_tiles<<<dim3(grid_for(nd)), dim3(256), 0, st>>>(t.tiles, sort.perm, nd, sorted);
 		SPS_LAUNCH_CHECK();
 		t.tiles = sorted;
 	}
 	for (int k = 0; k < NCLS; ++k) {
 		uint32_t nd = hv.ncell[k];
 		if (nd < 2) continue;
-		uint64_t *k0 = c->arena.get<uint64_t>(nd), *k1 = c->arena.get<uint64_t>(nd);
-		uint32_t *p0 = c->arena.get<uint32_t>(nd), *p1 = c->arena.get<uint32_t>(nd);
-		k_cell_keys<<<dim3(grid_for(nd)), dim3(256), 0, st>>>(hv.cells[k], nd, k == CLS_DENSE, k0);
+		PairSort sort(c, nd);
+		k_cell_keys<<<dim3(grid_for(nd)), dim3(256), 0, st>>>(hv.cells[k], nd, k == CLS_DENSE, sort.keys);
 		SPS_LAUNCH_CHECK();
-		int where = radix_sort_pairs(c, k0, p0, k1, p1, nd, k == CLS_DENSE ? 16 + wbits : wbits);
+		sort.run(k == CLS_DENSE ? 16 + wbits : wbits);
 		Cell *sorted = c->arena.get<Cell>(nd);
-		k_gather_cells<<<dim3(grid_for(nd)), dim3(256), 0, st>>>(hv.cells[k], where ? p1 : p0, nd, sorted);
+		k_gather_cells<<<dim3(grid_for(nd)), dim3(256), 0, st>>>(hv.cells[k], sort.perm, nd, sorted);
 		SPS_LAUNCH_CHECK();
 		hv.cells[k] = sorted;
 	}
