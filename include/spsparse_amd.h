@@ -225,6 +225,14 @@ const char *spsamd_version(void);
  *                                     (inside the row where B is a prepared handle, else over the whole stream) | 3 every key of
  *                                     op(B) looks up its run in op(A) (default: the cheapest by a byte model, DESIGN.md
  *                                     section 17)
+ *   solve_path      1 | 2             solve_tri: 1 every level of the schedule in a launch of its own | 2 every level whose rows
+ *                                     are all short through the fused runs (one workgroup walking consecutive levels), whatever
+ *                                     its width (default: levels of at most solve_fuse_rows rows fuse)
+ *   solve_row       1 | 2 | 3         solve_tri: every row through the serial (thread per row and rhs) | lanes (wave per row,
+ *                                     lanes across rhs) | fold (wave per row, ordered fold) kernel (default: rows of at most
+ *                                     spmm_long_min tuples serial, the others lanes from 16 right-hand sides on, else fold)
+ *   solve_fuse_rows > 0               solve_tri: the widest level that still counts as thin (default: 256 rows, and at most
+ *                                     2048 (row, rhs) pairs; a set value is taken as given)
  * The environment variables of the same purpose (SPSAMD_W ...) are read once, inside spsamd_ctx_create; nothing reads
  * the environment later.  Unknown names: SPSAMD_EINVAL. */
 int spsamd_ctx_set_tuning(spsamd_ctx *ctx, const char *name, long value);
@@ -579,6 +587,60 @@ int spsamd_emult(spsamd_ctx *ctx, int op, int emult_flags,
 	const spsamd_coo *B, char transpose_B,
 	int duplicate_policy, int zero_nan,
 	int sink_kind, int sink_flags, spsamd_result *result);
+
+/*
+ * Solve T * X = B for X, T the `uplo` triangle of op(A): a sparse triangular solve with nrhs right-hand sides by level
+ * schedule (the counterpart of rocSPARSE / cuSPARSE csrsv and csrsm).  With it a Gauss-Seidel or SOR
+ * sweep ((D + L)^-1 r: LOWER on the whole matrix, no select in front) and an ILU / IC application (LOWER | UNIT, then UPPER)
+ * stay in this library.
+ *   - Operand.  op(A) is taken exactly as spsamd_select takes it, with duplicate_policy and zero_nan: a raw operand is
+ *     consolidated by op()'s rows; an operand whose sort0 names op()'s row order is trusted as stored (duplicates and
+ *     explicit zeros included); a SINK_COO result of this context and a prepared handle of the same transpose are read in
+ *     place.  Call the resulting sequence S.  op(A) must be square (SPSAMD_EDIM); n is its order.
+ *   - Used triangle (rocSPARSE's fill-mode rule).  Under LOWER the tuples with j > i, under UPPER those with j < i, are
+ *     skipped and their values never read; under DIAG_UNIT the tuples with j == i are skipped as well.
+ *   - Every bit of X is defined by this loop, run for each right-hand side r over the rows in ascending i (LOWER) or
+ *     descending i (UPPER):
+ *         acc = B[i * ldb + r];  d = +0.0
+ *         for each used tuple (i, j, v) of row i, in S's order:
+ *             if j == i:  d = d + v                        (the fold of spsamd_reduce's DIAG)
+ *             else:       acc = acc - v * X[j * ldx + r]   (the product rounded, then the subtraction rounded: no FMA)
+ *         X[i * ldx + r] = UNIT ? acc : acc / d            (a true IEEE division, not a multiplication by a reciprocal)
+ *     A NaN result carries the bits x86-64 gives it (mulsd, addsd, subsd, divsd): the left operand's NaN quieted, else the
+ *     right one's, else 0xFFF8000000000000.  A missing or zero diagonal is no error: d stays +-0.0 and the division gives
+ *     what IEEE gives; a row without a used tuple gives B / +0.0 (B under UNIT).
+ *   - B and X are row-major like multiply_dense's arrays: n rows of nrhs values, ldb, ldx >= nrhs, the ld - nrhs trailing
+ *     values of a row never touched; `mem` (SPSAMD_MEM_HOST or SPSAMD_MEM_DEVICE) holds for both.  X == B with ldx == ldb
+ *     solves in place; any other overlap of X with B or with A's arrays, and a device X inside an output set of the
+ *     context, are SPSAMD_EINVAL.  Neither output set is written: a SINK_COO result stays valid and can be A.
+ *   - The schedule: level(i) = 0 for a row without a used off-diagonal tuple, else 1 + the largest level of the rows its
+ *     used off-diagonal tuples name (by pattern: explicit zeros count).  The rows of a level are solved together; a run of
+ *     consecutive thin levels is one launch of one workgroup.  A prepared handle of the same transpose keeps the schedule
+ *     of each (uplo, diag) it was solved with (spsamd_operand_bytes grows once); any other operand is analysed per call.
+ * stats (may be NULL): see the struct.  result (may be NULL): shape0 = shape1 = n, nnz_a = |S|, ms_consolidate, ms_symbolic
+ * (the analysis), ms_numeric, ms_total, workspace_bytes; everything else 0 / NULL.
+ * SPSAMD_EINVAL, with a message and X untouched: A NULL; B or X NULL while nrhs > 0 and n > 0; uplo or diag out of range;
+ * ldb or ldx < nrhs; a bad mem or policy; an index out of bounds; a false sort0; 2^31 or more tuples.  nrhs == 0 or n == 0
+ * returns 0 with nothing touched.  Returns when X is complete.
+ */
+#define SPSAMD_TRI_LOWER 0
+#define SPSAMD_TRI_UPPER 1
+#define SPSAMD_DIAG_NONUNIT 0
+#define SPSAMD_DIAG_UNIT 1
+typedef struct {
+	uint64_t levels, max_level_rows;  /* of the schedule */
+	uint64_t launches;                /* kernel launches of the numeric phase of this call */
+	uint64_t fused_levels;            /* levels served inside a fused run */
+	uint64_t tuples_used;             /* tuples of S in the used triangle, diagonal included unless UNIT */
+	int64_t  zero_pivot;              /* smallest row with d_i == +-0.0 (NONUNIT only), else -1 */
+	uint32_t analysis_reused;         /* 1: the schedule came from a prepared handle */
+	float ms_analysis, ms_solve;
+} spsamd_solve_stats;
+
+int spsamd_solve_tri(spsamd_ctx *ctx, const spsamd_coo *A, char transpose, int uplo, int diag,
+	const double *B, size_t ldb, double *X, size_t ldx, size_t nrhs, int mem,
+	int duplicate_policy, int zero_nan,
+	spsamd_solve_stats *stats /* may be NULL */, spsamd_result *result /* may be NULL */);
 
 /*
  * ret = (C * diag(scalei) * op(A) * diag(scalej) * op(B) * diag(scalek)) restricted to the keys of M  -- a masked product

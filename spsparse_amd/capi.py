@@ -35,6 +35,11 @@ EMULT_TIMES, EMULT_FIRST = 1, 2
 EMULT_COMPLEMENT = 1
 # emult: the merged items per tile of the merge path, and the tuples per wave of the probe and compact kernels
 emult_tile, emult_unit = 2048, 512
+TRI_LOWER, TRI_UPPER = 0, 1
+DIAG_NONUNIT, DIAG_UNIT = 0, 1
+# solve_tri: the default of the solve_fuse_rows knob, the (row, rhs) pairs that also bound a thin level under that default,
+# and the threads of a fused run's one workgroup
+solve_fuse_rows, solve_fuse_work, solve_fused_threads = 256, 2048, 1024
 
 ERRORS = {-1: "EDIM", -2: "EINVAL", -3: "EHIP", -4: "ENOMEM", -5: "ECAPACITY", -6: "ENODEVICE", -7: "EPEER"}
 
@@ -79,6 +84,12 @@ class StreamStats(C.Structure):
                 ("ms_wall", C.c_float)]
 
 
+class SolveStats(C.Structure):
+    _fields_ = [("levels", C.c_uint64), ("max_level_rows", C.c_uint64), ("launches", C.c_uint64),
+                ("fused_levels", C.c_uint64), ("tuples_used", C.c_uint64), ("zero_pivot", C.c_int64),
+                ("analysis_reused", C.c_uint32), ("ms_analysis", C.c_float), ("ms_solve", C.c_float)]
+
+
 class DistStats(C.Structure):
     _fields_ = [("block_nnz_a", C.c_uint64), ("panel_tuples", C.c_uint64), ("remote_tuples", C.c_uint64),
                 ("sent_tuples", C.c_uint64), ("ms_exchange", C.c_float), ("pad_", C.c_float)]
@@ -98,7 +109,7 @@ SYMBOLS = ["spsamd_ctx_create", "spsamd_ctx_destroy", "spsamd_last_error", "spsa
            "spsamd_dist_unique_id", "spsamd_dist_create", "spsamd_dist_destroy", "spsamd_dist_multiply",
            "spsamd_operand_prepare", "spsamd_operand_as_coo", "spsamd_operand_bytes", "spsamd_operand_destroy",
            "spsamd_multiply_dense", "spsamd_add", "spsamd_multiply_stream", "spsamd_multiply_masked",
-           "spsamd_multiply_sampled", "spsamd_select", "spsamd_extract", "spsamd_reduce", "spsamd_emult"]
+           "spsamd_multiply_sampled", "spsamd_select", "spsamd_extract", "spsamd_reduce", "spsamd_emult", "spsamd_solve_tri"]
 
 _lib = None
 
@@ -155,6 +166,8 @@ def load():
                                 C.c_size_t, C.c_int, P(C.c_size_t), P(Result)]
     L.spsamd_emult.argtypes = [C.c_void_p, C.c_int, C.c_int, C.c_double, P(Coo), C.c_char, P(Coo), C.c_char,
                                C.c_int, C.c_int, C.c_int, C.c_int, P(Result)]
+    L.spsamd_solve_tri.argtypes = [C.c_void_p, P(Coo), C.c_char, C.c_int, C.c_int, C.c_void_p, C.c_size_t, C.c_void_p,
+                                   C.c_size_t, C.c_size_t, C.c_int, C.c_int, C.c_int, P(SolveStats), P(Result)]
     L.spsamd_memcpy.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_size_t]
     L.spsamd_consolidate.argtypes = [C.c_void_p, P(Coo), C.c_int, C.c_int, C.c_int, P(Result)]
     L.spsamd_sorted_permutation.argtypes = [C.c_void_p, P(Coo), C.c_int, C.c_void_p]
@@ -454,6 +467,34 @@ class Context:
         self._check(self.L.spsamd_multiply_dense(self.h, C.byref(M), transpose.encode(), px, ldx, py, ldy, nx, mx,
                                                  duplicate_policy, int(handle_nan)))
         return Y
+
+    def solve_tri(self, A, B, uplo=TRI_LOWER, diag=DIAG_NONUNIT, transpose='.', X=None, duplicate_policy=ADD, zero_nan=False,
+                  stats=False, result=None):
+        """spsamd_solve_tri: X with T @ X = B, T the `uplo` triangle of op(A) (the other triangle is skipped; under
+        DIAG_UNIT the diagonal too), bit for bit the serial substitution loop of the header.  A: a Coo struct.  B, X: 2-D
+        float64 numpy arrays (host) or float64 torch tensors on this context's device, rows contiguous; a 1-D B / X is one
+        right-hand side.  X=None allocates it; X=B solves in place.  Returns X, or (X, SolveStats) with stats=True.
+        result: a capi.Result to fill (timings)."""
+        pb, ldb, nb, mb = _dense_arg(B, "B", writable=False)
+        if X is None:
+            if mb == MEM_HOST:
+                X = np.empty(B.shape, dtype=np.float64)
+            else:
+                import torch
+                X = torch.empty(tuple(B.shape), dtype=torch.float64, device=B.device)
+        px, ldx, nx, mx = _dense_arg(X, "X", writable=True)
+        if mx != mb:
+            raise ValueError("B and X must both be host (numpy) or both device (torch) arrays")
+        if nx != nb:
+            raise ValueError("B has %d right-hand sides, X %d" % (nb, nx))
+        n = int(A.shape1 if transpose == 'T' else A.shape0)
+        if _rows(B) != n or _rows(X) != n:
+            raise ValueError("B and X need %d rows" % n)
+        st = SolveStats()
+        self._check(self.L.spsamd_solve_tri(self.h, C.byref(A), transpose.encode(), int(uplo), int(diag), pb, ldb, px, ldx, nb,
+                                            mb, duplicate_policy, int(zero_nan), C.byref(st),
+                                            None if result is None else C.byref(result)))
+        return (X, st) if stats else X
 
     def multiply_sampled(self, M, P, Q, out=None, transpose='.', alpha=1.0, beta=0.0):
         """spsamd_multiply_sampled: out[t] = alpha * (P[i] . Q[j]) (+ beta * v) for every tuple t = (i, j, v) of op(M) in

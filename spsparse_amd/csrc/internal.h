@@ -96,6 +96,9 @@ struct Tuning {
 	int reduce_path = 0;         // reduce: 0 by row length | 1 every row through the short rows' kernel | 2 every row through the long rows' kernel
 	int tile_walk = 0;           // tiles of the heavy rows: 0 claimed from a counter | 1 the static grid-stride walk
 	int emult_path = 0;          // emult: 0 by a byte model | 1 merge | 2 every tuple of op(A) probes op(B) | 3 every key of op(B) probes op(A)
+	int solve_path = 0;          // solve_tri: 0 thin levels fuse | 1 every level a launch of its own | 2 every level of short rows fuses, whatever its width
+	int solve_row = 0;           // solve_tri: 0 by row length (spmm_long_min) | 1 serial | 2 lanes | 3 fold kernel for every row
+	int solve_fuse_rows = 0;     // solve_tri: the widest level that still counts as thin (0: 256 rows and 2048 (row, rhs) pairs)
 #ifdef SPSAMD_ABLATIONS
 	int dbg = 0;
 #endif
@@ -360,6 +363,19 @@ struct __attribute__((packed, aligned(4))) BTup { int32_t col; uint32_t vlo, vhi
 // skips the consolidation of an operand that carries the wanted sort order (algorithm.hpp:360).  Either a VIEW for the
 // duration of one call (pieces in the context's arena; the distributed step hands its panel's row pointer in this way) or a
 // prepared-operand HANDLE of the C ABI (spsamd_operand_prepare: pieces in device memory of their own, built on first use).
+// The level schedule of one (uplo, diag) triangle of an operand (k_solve.hip): the rows listed level
+// by level (ascending inside a level), the levels' bounds in that list and, for the host that plans the launches, copies of
+// the bounds and of each level's longest row.
+struct SolveSchedule {
+	bool built = false;
+	uint32_t levels = 0, max_level_rows = 0;
+	uint64_t tuples_used = 0;
+	int64_t zero_pivot = -1;
+	uint32_t *level_ptr = nullptr;    // device: levels + 1 entries
+	uint32_t *rows = nullptr;         // device: one entry per row of op(A)
+	std::vector<uint32_t> h_level_ptr, h_level_max;
+};
+
 struct Prepared {
 	spsamd_ctx *ctx = nullptr;
 	ConMat m;                         // op(X), consolidated, row-major
@@ -386,6 +402,8 @@ struct Prepared {
 	uint16_t *wcnt = nullptr;         // [nrowb][nwp]      tuples of row k in window w
 	uint32_t *wptr = nullptr;         // [nwin][nrowb] + 1 window-major copy: CSR pointer per window ...
 	BTup *btw = nullptr;              // ... and its tuples
+	// triangular solves
+	SolveSchedule solve[2][2];        // [uplo][diag], each built by the first solve that needs it (handles only)
 	void *alloc(size_t bytes);        // arena memory of the current call (view) or device memory of the handle's own
 	template <class T> T *get(size_t n) { return (T *)alloc(n * sizeof(T)); }
 	void release();
@@ -508,6 +526,12 @@ void extract_tuples(spsamd_ctx *c, const spsamd_coo *A, char transpose, const in
 // SPSAMD_ECAPACITY with *out_nnz = the entries needed and the context's last error set (nothing written).
 int reduce_rows(spsamd_ctx *c, const spsamd_coo *A, char transpose, int op, int post, int duplicate_policy, int zero_nan,
 	int32_t *out_idx, double *out_val, size_t capacity, int mem, size_t *out_nnz, spsamd_result *res);
+
+// ---------------------------------------------------------------- sparse triangular solve (k_solve.hip)
+
+// T * X = B for the `uplo` triangle of op(A): spsamd_solve_tri after the context check
+int solve_tri(spsamd_ctx *c, const spsamd_coo *A, char transpose, int uplo, int diag, const double *B, size_t ldb, double *X,
+	size_t ldx, size_t nrhs, int mem, int duplicate_policy, int zero_nan, spsamd_solve_stats *stats, spsamd_result *res);
 
 // ---------------------------------------------------------------- element-wise product and pattern restriction (k_emult.hip)
 

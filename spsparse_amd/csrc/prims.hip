@@ -137,6 +137,7 @@ void Prepared::release()
 	owned.clear();
 	owned_bytes = 0;
 	slab = nullptr; slab_left = 0;
+	for (auto &u : solve) for (auto &s : u) s = SolveSchedule();
 }
 
 } // namespace spsamd

@@ -34,4 +34,18 @@ __device__ __forceinline__ double ref_add(double a, double b)
 	return r != r ? x86_nan(a, b) : r;
 }
 
+// subsd: a - b, never a + (-b) -- the negation would flip the sign bit of a NaN b that the result then carries
+__device__ __forceinline__ double ref_sub(double a, double b)
+{
+	double r = a - b;
+	return r != r ? x86_nan(a, b) : r;
+}
+
+// divsd: a true IEEE division (0 / 0 and Inf / Inf give the default NaN)
+__device__ __forceinline__ double ref_div(double a, double b)
+{
+	double r = __ddiv_rn(a, b);
+	return r != r ? x86_nan(a, b) : r;
+}
+
 } // namespace spsamd
