@@ -60,76 +60,88 @@ __device__ __forceinline__ uint64_t ref_key(uint64_t key, int minor_bits, int ma
 	return (minor << major_bits) | major;
 }
 
-__global__ void k_gather_flag(const double *val, const uint32_t *perm, const uint64_t *keys, size_t n, int zero_nan,
+// (The sorted keys and positions come in either form of PairSort, SortedKeys.)
+__global__ void k_gather_flag(const double *val, SortedKeys sk, size_t n, int zero_nan,
 	int minor_bits, int major_bits, int swap, double *sval, uint8_t *keep, unsigned long long *first_key)
 {
 	size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
 	if (i >= n) return;
-	double v = val[perm[i]];
+	double v = val[sk.pos(i)];
 	sval[i] = v;
 	keep[i] = (v != 0) ? 1 : 0;
-	if (zero_nan && v != 0 && v == v) atomicMin(first_key, (unsigned long long)ref_key(keys[i], minor_bits, major_bits, swap));
+	if (zero_nan && v != 0 && v == v) atomicMin(first_key, (unsigned long long)ref_key(sk.key(i), minor_bits, major_bits, swap));
 }
 
-__global__ void k_first_pos(const double *sval, const uint32_t *perm, const uint64_t *keys, size_t n,
+__global__ void k_first_pos(const double *sval, SortedKeys sk, size_t n,
 	int minor_bits, int major_bits, int swap, const unsigned long long *first_key, uint32_t *first_pos)
 {
 	size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
 	if (i >= n) return;
 	const double v = sval[i];
-	if (v != 0 && v == v && ref_key(keys[i], minor_bits, major_bits, swap) == *first_key) atomicMin(first_pos, perm[i]);
+	if (v != 0 && v == v && ref_key(sk.key(i), minor_bits, major_bits, swap) == *first_key) atomicMin(first_pos, sk.pos(i));
 }
 
-__global__ void k_apply_first(const double *sval, const uint32_t *perm, const uint64_t *keys, uint8_t *keep, size_t n,
+__global__ void k_apply_first(const double *sval, SortedKeys sk, uint8_t *keep, size_t n,
 	int minor_bits, int major_bits, int swap, const unsigned long long *first_key, const uint32_t *first_pos)
 {
 	size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
 	if (i >= n) return;
 	const double v = sval[i];
 	if (v == v) return;                                  // only NaNs are in question (zeros are dropped anyway)
-	const uint64_t k = ref_key(keys[i], minor_bits, major_bits, swap), fk = *first_key;
-	if (k < fk || (k == fk && perm[i] < *first_pos)) keep[i] = 0;
+	const uint64_t k = ref_key(sk.key(i), minor_bits, major_bits, swap), fk = *first_key;
+	if (k < fk || (k == fk && sk.pos(i) < *first_pos)) keep[i] = 0;
 }
 
-__global__ void k_compact(const uint64_t *keys, const double *sval, const uint8_t *keep, const uint32_t *pos, size_t n,
-	uint64_t *kk, double *kv)
+// A value loaded above is needed HERE: the compiler cannot sink its load behind the branch that follows (it does otherwise,
+// and a thread then waits for one load after the other).  This leans on how the compiler schedules, not on the language:
+// tuned with the clang of ROCm 7.2 (k_merge_runs 186 -> 157 us at 1.7e7 tuples); worth a look at the ISA after a toolchain change.
+template <class T> __device__ __forceinline__ void loaded(T &x) { asm volatile("" : "+v"(x)); }
+
+// One thread per run of equal keys, the one at the run's first position: it walks the run forward once, in sorted (=
+// insertion, the sort is stable) order, and applies the DuplicatePolicy to the tuples consolidate() keeps exactly as
+// algorithm.hpp:306-310 does, left to right.  The merged value goes to the run's first position, with the flag "this run
+// kept something".  Nothing is compacted first and nobody searches backwards: a run of a million explicit zeros costs
+// its one walk.  (Before: the kept tuples were copied side by side, 16 bytes each, so that the run heads could be found
+// among them, and a second scan placed the heads.)
+__global__ void k_merge_runs(SortedKeys sk, double *sval, const uint8_t *keep, size_t n, int policy, uint8_t *head)
 {
 	size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
-	if (i < n && keep[i]) {
-		uint32_t p = pos[i];
-		kk[p] = keys[i];
-		kv[p] = sval[i];
+	if (i >= n) return;
+	// everything a run of one tuple needs is asked for before the first branch (the neighbours at clamped positions, so
+	// that no load hides behind a condition): one round trip for almost every thread instead of four
+	uint64_t key = sk.key(i), prev = sk.key(i ? i - 1 : 0), next = sk.key(i + 1 < n ? i + 1 : i);
+	uint32_t k0 = keep[i];
+	double acc = sval[i];
+	loaded(key); loaded(prev); loaded(next); loaded(k0); loaded(acc);
+	if (i > 0 && prev == key) { head[i] = 0; return; }
+	bool any = k0 != 0, moved = false;                     // moved: the run's value is not the one stored at i
+	for (size_t t = i + 1; t < n && next == key; ++t) {       // (a further tuple of the run: again one round trip)
+		uint32_t kt = keep[t];
+		double v = sval[t];
+		next = sk.key(t + 1 < n ? t + 1 : t);
+		loaded(kt); loaded(v); loaded(next);
+		if (!kt) continue;
+		if (!any) { acc = v; any = true; moved = true; }
+		else if (policy == SPSAMD_ADD) { acc += v; moved = true; }
+		else if (policy == SPSAMD_REPLACE) { acc = v; moved = true; }
 	}
+	head[i] = any ? 1 : 0;
+	if (moved) sval[i] = acc;                              // (only this thread reads the run's values)
 }
 
-__global__ void k_heads(const uint64_t *kk, const uint32_t *nk_ptr, size_t n, uint8_t *head)
-{
-	size_t j = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
-	if (j >= n) return;
-	uint32_t nk = *nk_ptr;
-	head[j] = (j < nk && (j == 0 || kk[j] != kk[j - 1])) ? 1 : 0;
-}
-
-// One thread per distinct index: walks its run of equal keys in sorted (=
-// insertion, the sort is stable) order and applies the DuplicatePolicy
-// exactly as algorithm.hpp:306-310 does, left to right.
-__global__ void k_merge(const uint64_t *kk, const double *kv, const uint8_t *head, const uint32_t *hpos,
-	const uint32_t *nk_ptr, size_t n, int minor_bits, int policy,
+__global__ void k_emit_runs(SortedKeys sk, const double *sval, const uint8_t *head, const uint32_t *hpos, size_t n, int minor_bits,
 	int32_t *row, int32_t *col, double *val)
 {
-	size_t j = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
-	if (j >= n || !head[j]) return;
-	uint32_t nk = *nk_ptr;
-	uint64_t key = kk[j];
-	double acc = kv[j];
-	for (size_t t = j + 1; t < nk && kk[t] == key; ++t) {
-		if (policy == SPSAMD_ADD) acc += kv[t];
-		else if (policy == SPSAMD_REPLACE) acc = kv[t];
-	}
-	uint32_t o = hpos[j];
+	size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
+	if (i >= n) return;
+	uint32_t h = head[i], o = hpos[i];                     // (almost every position is a run's first: all four loads at once)
+	uint64_t key = sk.key(i);
+	double v = sval[i];
+	loaded(h); loaded(o); loaded(key); loaded(v);
+	if (!h) return;
 	row[o] = (int32_t)(key >> minor_bits);
 	col[o] = (int32_t)(key & ((uint64_t(1) << minor_bits) - 1));
-	val[o] = acc;
+	val[o] = v;
 }
 
 __global__ void k_min_key(unsigned long long *first_key, const unsigned long long *global_key)
@@ -207,22 +219,19 @@ void consolidate_operand(spsamd_ctx *c, const spsamd_coo *X, int lead, int ref_l
 	}
 
 	int mb = bits_of(out->ncol), Mb = bits_of(out->nrow);
-	PairSort sort(c, n);
-	build_keys(c, major, minor, n, mb, sort.keys);
+	PairSort sort(c, n, mb + Mb);                 // (the key and the position in one word where they fit: index 2^20 x 2^20, 1.7e7 tuples: 40 + 24 bits)
 	// An operand that is STRICTLY in (minor, major) order -- a matrix kept sorted by rows and used with 'T', cfg5's R -- needs
 	// the stable passes over the MAJOR digits only: an LSD sort that skips the low digits leaves ties in input order, which is
 	// the minor order already (Galerkin 256^3, R^T: 3 passes instead of 6).  Strictly: no two tuples share their indices, so
 	// with no value to drop either the sorted tuples ARE the consolidated operand (no flag / compact / merge passes).
 	const int low_bit = (f & 4u) ? 0 : mb;
-	sort.run(mb + Mb, low_bit);
-	uint64_t *ks = sort.keys;
-	uint32_t *ps = sort.perm;
-	uint64_t *kk = sort.spare_keys;            // the other key buffer is free now
+	sort.run_indices(major, minor, mb, mb + Mb, low_bit);
+	const SortedKeys sk = sort.sorted();
 	if (!(f & 4u) && !(f & 8u)) {                  // nothing to drop and nothing to merge: the sorted tuples are the consolidated ones
 		out->row = c->arena.get<int32_t>(n);
 		out->col = c->arena.get<int32_t>(n);
 		out->val = c->arena.get<double>(n);
-		gather_sorted(c, ks, ps, dv, n, mb, out->row, out->col, out->val);
+		gather_sorted(c, sk, dv, n, mb, out->row, out->col, out->val);
 		out->nnz = (uint32_t)n;
 		return;
 	}
@@ -236,31 +245,25 @@ void consolidate_operand(spsamd_ctx *c, const spsamd_coo *X, int lead, int ref_l
 		SPS_HIP(hipMemsetAsync(first_key, 0xFF, sizeof(unsigned long long), c->stream));
 		fill_u32(c, first_pos, 0xFFFFFFFFu, 1);
 	}
-	k_gather_flag<<<dim3(grid_for(n)), dim3(256), 0, c->stream>>>(dv, ps, ks, n, zero_nan, mb, Mb, swap, sval, keep, first_key);
+	k_gather_flag<<<dim3(grid_for(n)), dim3(256), 0, c->stream>>>(dv, sk, n, zero_nan, mb, Mb, swap, sval, keep, first_key);
 	SPS_LAUNCH_CHECK();
 	if (zero_nan) {
 		// (distributed step: the first kept tuple of the WHOLE matrix may sit in another rank's block)
 		if (global_first_key) { k_min_key<<<dim3(1), dim3(1), 0, c->stream>>>(first_key, global_first_key); SPS_LAUNCH_CHECK(); }
-		k_first_pos<<<dim3(grid_for(n)), dim3(256), 0, c->stream>>>(sval, ps, ks, n, mb, Mb, swap, first_key, first_pos);
+		k_first_pos<<<dim3(grid_for(n)), dim3(256), 0, c->stream>>>(sval, sk, n, mb, Mb, swap, first_key, first_pos);
 		SPS_LAUNCH_CHECK();
-		k_apply_first<<<dim3(grid_for(n)), dim3(256), 0, c->stream>>>(sval, ps, ks, keep, n, mb, Mb, swap, first_key, first_pos);
+		k_apply_first<<<dim3(grid_for(n)), dim3(256), 0, c->stream>>>(sval, sk, keep, n, mb, Mb, swap, first_key, first_pos);
 		SPS_LAUNCH_CHECK();
 	}
-	uint32_t *pos = c->arena.get<uint32_t>(n + 1);
-	scan_exclusive_u8_u32(c, keep, pos, n);
-	double *kv = c->arena.get<double>(n);
-	k_compact<<<dim3(grid_for(n)), dim3(256), 0, c->stream>>>(ks, sval, keep, pos, n, kk, kv);
-	SPS_LAUNCH_CHECK();
-	uint8_t *head = keep;                      // reuse
-	k_heads<<<dim3(grid_for(n)), dim3(256), 0, c->stream>>>(kk, pos + n, n, head);
+	uint8_t *head = c->arena.get<uint8_t>(n);
+	k_merge_runs<<<dim3(grid_for(n)), dim3(256), 0, c->stream>>>(sk, sval, keep, n, duplicate_policy, head);
 	SPS_LAUNCH_CHECK();
 	uint32_t *hpos = c->arena.get<uint32_t>(n + 1);
 	scan_exclusive_u8_u32(c, head, hpos, n);
 	out->row = c->arena.get<int32_t>(n);
 	out->col = c->arena.get<int32_t>(n);
 	out->val = c->arena.get<double>(n);
-	k_merge<<<dim3(grid_for(n)), dim3(256), 0, c->stream>>>(kk, kv, head, hpos, pos + n, n, mb, duplicate_policy,
-		out->row, out->col, out->val);
+	k_emit_runs<<<dim3(grid_for(n)), dim3(256), 0, c->stream>>>(sk, sval, head, hpos, n, mb, out->row, out->col, out->val);
 	SPS_LAUNCH_CHECK();
 	out->nnz = read_back(c, hpos + n);
 }
@@ -297,6 +300,12 @@ void first_kept_key_raw(spsamd_ctx *c, const spsamd_coo *Xdev, int lead, int ref
 	SPS_LAUNCH_CHECK();
 }
 
+__global__ void k_word_pos(SortedKeys sk, size_t n, uint32_t *perm)
+{
+	size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
+	if (i < n) perm[i] = sk.pos(i);
+}
+
 uint32_t *sorted_permutation(spsamd_ctx *c, const spsamd_coo *X, int lead)
 {
 	size_t n = X->nnz;
@@ -309,10 +318,13 @@ uint32_t *sorted_permutation(spsamd_ctx *c, const spsamd_coo *X, int lead)
 	const int32_t *major = lead == 0 ? d0 : d1;
 	const int32_t *minor = lead == 0 ? d1 : d0;
 	int mb = bits_of(shape[1 - lead]), Mb = bits_of(shape[lead]);
-	PairSort sort(c, n);
-	build_keys(c, major, minor, n, mb, sort.keys);
-	sort.run(mb + Mb);
-	return sort.perm;
+	PairSort sort(c, n, mb + Mb);
+	sort.run_indices(major, minor, mb, mb + Mb);
+	if (sort.perm) return sort.perm;
+	uint32_t *perm = c->arena.get<uint32_t>(n);
+	k_word_pos<<<dim3(grid_for(n)), dim3(256), 0, c->stream>>>(sort.sorted(), n, perm);
+	SPS_LAUNCH_CHECK();
+	return perm;
 }
 
 // ------------------------------------------------------------------ dim_beginnings
@@ -349,6 +361,40 @@ void dim_beginnings(spsamd_ctx *c, const ConMat &m, RowList *out)
 	k_row_starts<<<dim3(grid_for(n)), dim3(256), 0, c->stream>>>(m.row, flag, pos, n, out->beg, out->id);
 	SPS_LAUNCH_CHECK();
 	out->nrows = read_back(c, pos + n);
+}
+
+__global__ void k_ptr_flags(const uint32_t *ptr, uint64_t nrow, uint8_t *flag)
+{
+	uint64_t r = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x;
+	if (r < nrow) flag[r] = ptr[r + 1] > ptr[r] ? 1 : 0;
+}
+
+__global__ void k_ptr_starts(const uint32_t *ptr, const uint8_t *flag, const uint32_t *pos, uint64_t nrow, uint32_t *beg, int32_t *id)
+{
+	uint64_t r = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x;
+	if (r >= nrow) return;
+	if (flag[r]) {
+		beg[pos[r]] = ptr[r];
+		id[pos[r]] = (int32_t)r;
+	}
+	if (r == nrow - 1) beg[pos[nrow]] = ptr[nrow];      // sentinel (algorithm.hpp:95-99): the tuple count
+}
+
+void dim_beginnings(spsamd_ctx *c, const ConMat &m, const uint32_t *ptr, RowList *out)
+{
+	const uint64_t nrow = m.nrow;
+	out->nrows = 0;
+	out->beg = c->arena.get<uint32_t>(nrow + 1);
+	out->id = c->arena.get<int32_t>(nrow ? nrow : 1);
+	if (m.nnz == 0) return;
+	uint8_t *flag = c->arena.get<uint8_t>(nrow);
+	uint32_t *pos = c->arena.get<uint32_t>(nrow + 1);
+	k_ptr_flags<<<dim3(grid_for(nrow)), dim3(256), 0, c->stream>>>(ptr, nrow, flag);
+	SPS_LAUNCH_CHECK();
+	scan_exclusive_u8_u32(c, flag, pos, nrow);
+	k_ptr_starts<<<dim3(grid_for(nrow)), dim3(256), 0, c->stream>>>(ptr, flag, pos, nrow, out->beg, out->id);
+	SPS_LAUNCH_CHECK();
+	out->nrows = read_back(c, pos + nrow);
 }
 
 // ------------------------------------------------------------------ dense row pointer

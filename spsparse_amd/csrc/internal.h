@@ -195,14 +195,33 @@ void read_back_words(spsamd_ctx *c, const WordList &w, uint32_t *host);
 // keys, keys, payloads, payloads, n entries each), the caller's keys in `keys`, then run(): a stable LSD radix sort on key
 // bits [low_bit, key_bits) (a caller whose input is already in the order of the low bits skips their passes).  The
 // payload is the storage position, so what comes out is the sorted keys and the stable permutation that sorts them.
+//
+// The one-word form, for a caller that names its key width to the constructor and whose keys are short enough to share a
+// 64-bit word with the position (word_key_bits + bits_of(n) <= 64; index_bits >= 0 says that it was taken): the words are
+// key << index_bits | position, the sort goes over the key's bits alone -- 8 bytes per item and pass instead of 12 -- and
+// there are no payload buffers: sorted() hands both forms to the kernels that read the result.  run_indices() is run() for
+// the key major << minor_bits | minor of an operand's tuples: its first pass reads the two index arrays and puts the key (or
+// the word) together itself, so nobody fills `keys`.
+struct SortedKeys {
+	const uint64_t *w;       // two arrays: the keys | one word: key << ibits | position
+	const uint32_t *perm;    // two arrays: the positions | one word: null
+	int ibits;               // 0 with two arrays
+	__device__ __forceinline__ uint64_t key(size_t i) const { return w[i] >> ibits; }
+	__device__ __forceinline__ uint32_t pos(size_t i) const { return perm ? perm[i] : (uint32_t)(w[i] & ((uint64_t(1) << ibits) - 1)); }
+};
+
 struct PairSort {
 	uint64_t *keys;          // before run(): the n keys to fill | after: the keys, sorted
-	uint32_t *perm;          // after run(): perm[i] = the input position of sorted key i
-	uint64_t *spare_keys;    // after run(): the other pair of buffers, free for the caller
-	uint32_t *spare_pay;
-	PairSort(spsamd_ctx *c, size_t n);
+	uint32_t *perm;          // after run(): perm[i] = the input position of sorted key i (null in the one-word form)
+	int index_bits;          // >= 0: the one-word form and the position's width
+	PairSort(spsamd_ctx *c, size_t n, int word_key_bits = -1);
 	void run(int key_bits, int low_bit = 0);
+	void run_indices(const int32_t *major, const int32_t *minor, int minor_bits, int key_bits, int low_bit = 0);
+	SortedKeys sorted() const { return SortedKeys{keys, perm, index_bits < 0 ? 0 : index_bits}; }
 private:
+	uint64_t *spare_keys;    // the other pair of buffers
+	uint32_t *spare_pay;
+	void sort_from(const void *first, int key_bits, int low_bit);   // first: a KeySrc of prims.hip or null
 	spsamd_ctx *c;
 	size_t n;
 };
@@ -286,8 +305,8 @@ void mask_keys(spsamd_ctx *c, const spsamd_coo *M, int lead, uint64_t nrow, uint
 int bits_of(uint64_t dim);        // bits needed to hold indices 0 .. dim-1
 // keys[i] = major[i] << minor_bits | minor[i]: the sort key of radix_sort_pairs (payload: the storage position) ...
 void build_keys(spsamd_ctx *c, const int32_t *major, const int32_t *minor, size_t n, int minor_bits, uint64_t *keys);
-// ... and tuple i of the sorted operand: its indices out of sorted key i, its value from storage position perm[i]
-void gather_sorted(spsamd_ctx *c, const uint64_t *keys, const uint32_t *perm, const double *val, size_t n, int minor_bits,
+// ... and tuple i of the sorted operand: its indices out of sorted key i, its value from the storage position beside it
+void gather_sorted(spsamd_ctx *c, const SortedKeys &sk, const double *val, size_t n, int minor_bits,
 	int32_t *row, int32_t *col, double *oval);
 
 // The frame of a product op(A) * op(B) (multiply_sparse.hpp:167-169): op(A) rows = A.shape[a0]; op(B) is read by ROWS
@@ -345,6 +364,9 @@ struct RowList {
 	uint32_t nrows = 0;
 };
 void dim_beginnings(spsamd_ctx *c, const ConMat &m, RowList *out);
+// The same from m's dense row pointer (row r holds tuples iff ptr[r + 1] > ptr[r]): three passes over nrow entries
+// instead of nnz.
+void dim_beginnings(spsamd_ctx *c, const ConMat &m, const uint32_t *ptr, RowList *out);
 
 // Stable permutation sorting X by {lead, 1-lead} (device array of X->nnz uint32, arena memory).
 uint32_t *sorted_permutation(spsamd_ctx *c, const spsamd_coo *X, int lead);

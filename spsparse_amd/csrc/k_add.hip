@@ -247,7 +247,7 @@ static void add_stream(spsamd_ctx *c, const spsamd_coo *X, int lead, bool force_
 	sort.run(mb + Mb, low_bit < 0 ? mb : 0);
 	int32_t *row = c->arena.get<int32_t>(n), *col = c->arena.get<int32_t>(n);
 	double *val = c->arena.get<double>(n);
-	gather_sorted(c, sort.keys, sort.perm, dv, n, mb, row, col, val);
+	gather_sorted(c, sort.sorted(), dv, n, mb, row, col, val);
 	out->row = row; out->col = col; out->val = val; out->n = (uint32_t)n;
 	*sorted = true;
 }

@@ -63,16 +63,17 @@ __global__ void __launch_bounds__(256) k_build_keys(const int32_t *__restrict__ 
 	if (i < n) keys[i] = ((uint64_t)(uint32_t)major[i] << minor_bits) | (uint64_t)(uint32_t)minor[i];
 }
 
-__global__ void __launch_bounds__(256) k_gather_sorted(const uint64_t *__restrict__ keys, const uint32_t *__restrict__ perm,
+__global__ void __launch_bounds__(256) k_gather_sorted(SortedKeys sk,
 	const double *__restrict__ val, uint32_t n, int minor_bits, int32_t *__restrict__ row, int32_t *__restrict__ col,
 	double *__restrict__ oval)
 {
 	const uint32_t i = blockIdx.x * blockDim.x + threadIdx.x;
 	if (i >= n) return;
-	const uint64_t k = keys[i];
+	const uint64_t k = sk.key(i);
+	const double v = val[sk.pos(i)];                       // (before the stores: nothing says they do not alias the position array)
 	row[i] = (int32_t)(k >> minor_bits);
 	col[i] = (int32_t)(k & ((uint64_t(1) << minor_bits) - 1));
-	oval[i] = val[perm[i]];
+	oval[i] = v;
 }
 
 // (n < 2^31 tuples: check_operand)
@@ -82,10 +83,10 @@ void build_keys(spsamd_ctx *c, const int32_t *major, const int32_t *minor, size_
 	SPS_LAUNCH_CHECK();
 }
 
-void gather_sorted(spsamd_ctx *c, const uint64_t *keys, const uint32_t *perm, const double *val, size_t n, int minor_bits,
+void gather_sorted(spsamd_ctx *c, const SortedKeys &sk, const double *val, size_t n, int minor_bits,
 	int32_t *row, int32_t *col, double *oval)
 {
-	k_gather_sorted<<<dim3(grid_for(n)), dim3(256), 0, c->stream>>>(keys, perm, val, (uint32_t)n, minor_bits, row, col, oval);
+	k_gather_sorted<<<dim3(grid_for(n)), dim3(256), 0, c->stream>>>(sk, val, (uint32_t)n, minor_bits, row, col, oval);
 	SPS_LAUNCH_CHECK();
 }
 

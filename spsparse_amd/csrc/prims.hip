@@ -373,8 +373,23 @@ constexpr int RS_NW = RS_NT / 64;
 constexpr int RS_ITER = 16;                // 64-item chunks per wave
 constexpr int RS_TILE = RS_NT * RS_ITER;   // 4096 items per workgroup
 
+// Where a pass reads its keys: a key buffer, or (the first pass of PairSort::run_indices) an operand's two index arrays, out
+// of which the key -- and in the one-word form the position under it -- is put together as it is read: no pass that only
+// writes keys (1.7e7 tuples: 50 us).
+struct KeySrc {
+	const uint64_t *keys;
+	const int32_t *major, *minor;
+	int minor_bits, index_bits;
+	__device__ __forceinline__ uint64_t at(size_t i) const
+	{
+		if (keys) return keys[i];
+		const uint64_t k = ((uint64_t)(uint32_t)major[i] << minor_bits) | (uint64_t)(uint32_t)minor[i];
+		return index_bits < 0 ? k : (k << index_bits) | i;
+	}
+};
+
 template <int BITS>
-__global__ __launch_bounds__(RS_NT) void k_rs_hist(const uint64_t *keys, size_t n, int shift, uint32_t *ghist, unsigned nblocks)
+__global__ __launch_bounds__(RS_NT) void k_rs_hist(KeySrc keys, size_t n, int shift, uint32_t *ghist, unsigned nblocks)
 {
 	constexpr int NB = 1 << BITS;
 	__shared__ uint32_t hist[NB];
@@ -384,7 +399,7 @@ __global__ __launch_bounds__(RS_NT) void k_rs_hist(const uint64_t *keys, size_t 
 #pragma unroll 4
 	for (int q = 0; q < RS_ITER; ++q) {
 		size_t i = base + (size_t)q * RS_NT + threadIdx.x;
-		if (i < n) atomicAdd(&hist[(unsigned)(keys[i] >> shift) & (unsigned)(NB - 1)], 1u);
+		if (i < n) atomicAdd(&hist[(unsigned)(keys.at(i) >> shift) & (unsigned)(NB - 1)], 1u);
 	}
 	__syncthreads();
 	for (int d = threadIdx.x; d < NB; d += RS_NT) ghist[(size_t)d * nblocks + blockIdx.x] = hist[d];
@@ -395,8 +410,10 @@ __global__ __launch_bounds__(RS_NT) void k_rs_hist(const uint64_t *keys, size_t 
 // (workgroup, wave, chunk, lane) is the input order.  The tile is first sorted by digit INSIDE the
 // workgroup (LDS), then written out: a digit's items leave as one contiguous run instead of one
 // 12-byte record per lane (the direct scatter ran at 1.2 TB/s of record traffic).
-template <int BITS>
-__global__ __launch_bounds__(RS_NT) void k_rs_scatter(const uint64_t *keys, const uint32_t *pay, size_t n, int shift,
+// PAY = false: keys alone (the one-word form, the position rides in the key's low bits): 8 bytes read and written per item
+// instead of 12 and no s_pay, 37 KB of LDS instead of 53 -- four workgroups per CU instead of three.
+template <int BITS, bool PAY>
+__global__ __launch_bounds__(RS_NT) void k_rs_scatter(KeySrc keys, const uint32_t *pay, size_t n, int shift,
 	const uint32_t *gbase, unsigned nblocks, uint64_t *keys_out, uint32_t *pay_out, int iota_payload)
 {
 	constexpr int NB = 1 << BITS;
@@ -405,7 +422,7 @@ __global__ __launch_bounds__(RS_NT) void k_rs_scatter(const uint64_t *keys, cons
 	__shared__ uint32_t gdelta[NB];                // global position of a digit's run minus its position in the tile
 	__shared__ uint32_t scr[RS_NW + 1];
 	__shared__ uint64_t s_key[RS_TILE];
-	__shared__ uint32_t s_pay[RS_TILE];
+	__shared__ uint32_t s_pay[PAY ? RS_TILE : 1];
 	const unsigned w = wave_id(), lane = lane_id();
 	for (int q = threadIdx.x; q < RS_NW * NB; q += RS_NT) (&wcnt[0][0])[q] = 0;
 	__syncthreads();
@@ -415,7 +432,7 @@ __global__ __launch_bounds__(RS_NT) void k_rs_scatter(const uint64_t *keys, cons
 #pragma unroll
 	for (int q = 0; q < RS_ITER; ++q) {
 		size_t i = wbase + (size_t)q * 64 + lane;
-		key[q] = i < n ? keys[i] : 0;
+		key[q] = i < n ? keys.at(i) : 0;
 		if (i < n) atomicAdd(&wcnt[w][(unsigned)(key[q] >> shift) & (unsigned)(NB - 1)], 1u);
 	}
 	__syncthreads();
@@ -466,7 +483,7 @@ __global__ __launch_bounds__(RS_NT) void k_rs_scatter(const uint64_t *keys, cons
 		old = __shfl(old, leader, 64);
 		if (valid) {
 			s_key[old + rank] = key[q];
-			s_pay[old + rank] = iota_payload ? (uint32_t)i : pay[i];
+			if constexpr (PAY) s_pay[old + rank] = iota_payload ? (uint32_t)i : pay[i];
 		}
 	}
 	__syncthreads();
@@ -475,14 +492,14 @@ __global__ __launch_bounds__(RS_NT) void k_rs_scatter(const uint64_t *keys, cons
 		const uint64_t k = s_key[p];
 		const uint32_t dst = gdelta[(unsigned)(k >> shift) & (unsigned)(NB - 1)] + p;
 		keys_out[dst] = k;
-		pay_out[dst] = s_pay[p];
+		if constexpr (PAY) pay_out[dst] = s_pay[p];
 	}
 }
 
 template <int BITS>
-static int radix_sort_pairs_bits(spsamd_ctx *c, uint64_t *keys0, uint32_t *pay0, uint64_t *keys1, uint32_t *pay1, size_t n, int key_bits, int low_bit)
+static int radix_sort_pairs_bits(spsamd_ctx *c, const KeySrc *first, uint64_t *keys0, uint32_t *pay0, uint64_t *keys1, uint32_t *pay1, size_t n, int key_bits, int low_bit)
 {
-	// payload of the first pass is the identity permutation (iota_payload)
+	// payload of the first pass is the identity permutation (iota_payload); no payload buffers: keys alone
 	constexpr size_t NB = size_t(1) << BITS;
 	int passes = (key_bits - low_bit + BITS - 1) / BITS;
 	unsigned nblocks = (unsigned)((n + RS_TILE - 1) / RS_TILE);
@@ -494,10 +511,12 @@ static int radix_sort_pairs_bits(spsamd_ctx *c, uint64_t *keys0, uint32_t *pay0,
 	if (passes == 0) passes = 1;   // all keys equal: one pass on a zero digit keeps the input order
 	for (int p = 0; p < passes; ++p) {
 		int shift = low_bit + BITS * p;
-		k_rs_hist<BITS><<<dim3(nblocks), dim3(RS_NT), 0, c->stream>>>(ksrc, n, shift, ghist, nblocks);
+		const KeySrc src = p == 0 && first ? *first : KeySrc{ksrc, nullptr, nullptr, 0, -1};
+		k_rs_hist<BITS><<<dim3(nblocks), dim3(RS_NT), 0, c->stream>>>(src, n, shift, ghist, nblocks);
 		SPS_LAUNCH_CHECK();
 		scan_exclusive_u32_u32(c, ghist, gbase, NB * nblocks);
-		k_rs_scatter<BITS><<<dim3(nblocks), dim3(RS_NT), 0, c->stream>>>(ksrc, psrc, n, shift, gbase, nblocks, kdst, pdst, p == 0);
+		if (pay0) k_rs_scatter<BITS, true><<<dim3(nblocks), dim3(RS_NT), 0, c->stream>>>(src, psrc, n, shift, gbase, nblocks, kdst, pdst, p == 0);
+		else k_rs_scatter<BITS, false><<<dim3(nblocks), dim3(RS_NT), 0, c->stream>>>(src, nullptr, n, shift, gbase, nblocks, kdst, nullptr, 0);
 		SPS_LAUNCH_CHECK();
 		uint64_t *tk = ksrc; ksrc = kdst; kdst = tk;
 		uint32_t *tp = psrc; psrc = pdst; pdst = tp;
@@ -507,29 +526,45 @@ static int radix_sort_pairs_bits(spsamd_ctx *c, uint64_t *keys0, uint32_t *pay0,
 }
 
 // Stable LSD radix sort of (key, payload) pairs on key bits [low_bit, key_bits); the payload that comes out is the
-// permutation.  Returns which of the two buffer pairs holds the result (0: keys0/pay0, 1: keys1/pay1): PairSort::run
-// below is its one caller and the one place that decodes it.
-static int radix_sort_pairs(spsamd_ctx *c, uint64_t *keys0, uint32_t *pay0, uint64_t *keys1, uint32_t *pay1, size_t n, int key_bits, int low_bit)
+// permutation (pay0 = pay1 = null: of the keys alone; `first`: where the first pass reads its keys instead of keys0).  Returns which of the two buffer pairs holds the result (0: keys0/pay0,
+// 1: keys1/pay1): PairSort::run below is its one caller and the one place that decodes it.
+static int radix_sort_pairs(spsamd_ctx *c, const KeySrc *first, uint64_t *keys0, uint32_t *pay0, uint64_t *keys1, uint32_t *pay1, size_t n, int key_bits, int low_bit)
 {
 	if (n == 0) return 0;
 	if (low_bit < 0 || low_bit > key_bits) low_bit = 0;
 	// (10-bit digits save a pass on 40-bit keys but each pass is 35 % slower on MI355X -- the counters' LDS leaves two
 	// workgroups per CU instead of three: 1.51 against 1.40 ms for 1.7e7 pairs -- so 8 bits it stays)
-	return radix_sort_pairs_bits<8>(c, keys0, pay0, keys1, pay1, n, key_bits, low_bit);
+	return radix_sort_pairs_bits<8>(c, first, keys0, pay0, keys1, pay1, n, key_bits, low_bit);
 }
 
-PairSort::PairSort(spsamd_ctx *c, size_t n) : c(c), n(n)
+PairSort::PairSort(spsamd_ctx *c, size_t n, int word_key_bits) : c(c), n(n)
 {
+	const int ib = bits_of(n);
+	index_bits = word_key_bits >= 0 && word_key_bits + ib <= 64 ? ib : -1;
 	keys = c->arena.get<uint64_t>(n); spare_keys = c->arena.get<uint64_t>(n);
-	perm = c->arena.get<uint32_t>(n); spare_pay = c->arena.get<uint32_t>(n);
+	perm = spare_pay = nullptr;
+	if (index_bits < 0) { perm = c->arena.get<uint32_t>(n); spare_pay = c->arena.get<uint32_t>(n); }
 }
 
-void PairSort::run(int key_bits, int low_bit)
+void PairSort::sort_from(const void *first, int key_bits, int low_bit)
 {
-	if (radix_sort_pairs(c, keys, perm, spare_keys, spare_pay, n, key_bits, low_bit)) {
+	// one-word form: the key's bits sit above the position's, and a stable sort on them alone leaves the words in the order
+	// the pairs would have.  (low_bit is clamped HERE as well as in radix_sort_pairs: there it would see low_bit + up, which
+	// is in range whatever the caller passed.)
+	const int up = index_bits < 0 ? 0 : index_bits;
+	if (low_bit < 0 || low_bit > key_bits) low_bit = 0;
+	if (radix_sort_pairs(c, (const KeySrc *)first, keys, perm, spare_keys, spare_pay, n, key_bits + up, low_bit + up)) {
 		std::swap(keys, spare_keys);
 		std::swap(perm, spare_pay);
 	}
+}
+
+void PairSort::run(int key_bits, int low_bit) { sort_from(nullptr, key_bits, low_bit); }
+
+void PairSort::run_indices(const int32_t *major, const int32_t *minor, int minor_bits, int key_bits, int low_bit)
+{
+	const KeySrc src{nullptr, major, minor, minor_bits, index_bits};
+	sort_from(&src, key_bits, low_bit);
 }
 
 } // namespace spsamd

@@ -466,11 +466,15 @@ void prepared_row_structure(spsamd_ctx *c, Prepared *p)
 static const RowList &ensure_rowlist(spsamd_ctx *c, Prepared *p)
 {
 	if (p->have_rl) return p->rl;
-	if (!p->owns) dim_beginnings(c, p->m, &p->rl);
+	// from the dense row pointer where that exists and is the shorter of the two: the operand is also the right one, or a
+	// handle, or its longest row was asked for (R-MAT scale 20, A * A: 1.0e6 pointer entries against 1.6e7 tuples)
+	const bool by_ptr = p->rowptr && p->m.nrow + 1 <= (uint64_t)p->m.nnz;
+	auto beginnings = [&](RowList *out) { if (by_ptr) dim_beginnings(c, p->m, p->rowptr, out); else dim_beginnings(c, p->m, out); };
+	if (!p->owns) beginnings(&p->rl);
 	else {
 		// a handle keeps its own copy (the arena's is gone after this call)
 		RowList tmp;
-		dim_beginnings(c, p->m, &tmp);
+		beginnings(&tmp);
 		p->rl.nrows = tmp.nrows;
 		p->rl.beg = p->get<uint32_t>((size_t)tmp.nrows + 1);
 		p->rl.id = p->get<int32_t>(tmp.nrows ? tmp.nrows : 1);
