@@ -635,6 +635,9 @@ typedef struct {
 	int64_t  zero_pivot;              /* smallest row with d_i == +-0.0 (NONUNIT only), else -1 */
 	uint32_t analysis_reused;         /* 1: the schedule came from a prepared handle */
 	float ms_analysis, ms_solve;
+	uint64_t peel_thin_launches;      /* the analysis of this call: launches of the one-workgroup peel (thin frontiers) ... */
+	uint64_t peel_wide_launches;      /* ... and of the level-per-launch peel, those that found an empty frontier included;
+	                                     both 0 when analysis_reused is 1 or no off-diagonal tuple is used */
 } spsamd_solve_stats;
 
 int spsamd_solve_tri(spsamd_ctx *ctx, const spsamd_coo *A, char transpose, int uplo, int diag,

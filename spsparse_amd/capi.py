@@ -38,8 +38,10 @@ emult_tile, emult_unit = 2048, 512
 TRI_LOWER, TRI_UPPER = 0, 1
 DIAG_NONUNIT, DIAG_UNIT = 0, 1
 # solve_tri: the default of the solve_fuse_rows knob, the (row, rhs) pairs that also bound a thin level under that default,
-# and the threads of a fused run's one workgroup
+# and the threads of a fused run's one workgroup; the analysis: the widest frontier the one-workgroup peel takes, and the
+# launches of the wide peel between two looks at the frontier size
 solve_fuse_rows, solve_fuse_work, solve_fused_threads = 256, 2048, 1024
+peel_thin_max, peel_batch = 2048, 16
 
 ERRORS = {-1: "EDIM", -2: "EINVAL", -3: "EHIP", -4: "ENOMEM", -5: "ECAPACITY", -6: "ENODEVICE", -7: "EPEER"}
 
@@ -87,7 +89,8 @@ class StreamStats(C.Structure):
 class SolveStats(C.Structure):
     _fields_ = [("levels", C.c_uint64), ("max_level_rows", C.c_uint64), ("launches", C.c_uint64),
                 ("fused_levels", C.c_uint64), ("tuples_used", C.c_uint64), ("zero_pivot", C.c_int64),
-                ("analysis_reused", C.c_uint32), ("ms_analysis", C.c_float), ("ms_solve", C.c_float)]
+                ("analysis_reused", C.c_uint32), ("ms_analysis", C.c_float), ("ms_solve", C.c_float),
+                ("peel_thin_launches", C.c_uint64), ("peel_wide_launches", C.c_uint64)]
 
 
 class DistStats(C.Structure):

@@ -324,8 +324,8 @@ static bool ranges_overlap(const void *p, uint64_t np, const void *q, uint64_t n
 }
 
 // The schedule of the `uplo` / `diag` triangle of S into `s`: device arrays in workspace memory, or in the handle's own
-// when `hp` is given.
-static void analyse(spsamd_ctx *c, const TriView &t, Prepared *hp, SolveSchedule *s)
+// when `hp` is given.  peel[0] / peel[1]: the k_peel_thin / k_peel_wide launches issued (those that find an empty frontier too).
+static void analyse(spsamd_ctx *c, const TriView &t, Prepared *hp, SolveSchedule *s, uint64_t peel[2])
 {
 	hipStream_t st = c->stream;
 	const uint64_t N = t.n;
@@ -367,6 +367,7 @@ static void analyse(spsamd_ctx *c, const TriView &t, Prepared *hp, SolveSchedule
 			if (n <= PEEL_THIN_MAX) {
 				k_peel_thin<<<dim3(1), dim3(SOLVE_NT), 0, st>>>(cptr, dep, indeg, level, L, f[cur], f[cur ^ 1], &cnt3[ci], cnt3, state, nlev);
 				SPS_LAUNCH_CHECK();
+				++peel[0];
 				uint32_t *h = (uint32_t *)c->host_staging(4 * sizeof(uint32_t));
 				SPS_HIP(hipMemcpyAsync(h, state, 3 * sizeof(uint32_t), hipMemcpyDeviceToHost, st));
 				SPS_HIP(hipStreamSynchronize(st));
@@ -377,6 +378,7 @@ static void analyse(spsamd_ctx *c, const TriView &t, Prepared *hp, SolveSchedule
 				k_peel_wide<<<dim3(wide_grid), dim3(256), 0, st>>>(cptr, dep, indeg, level, L, f[cur], &cnt3[ci], f[cur ^ 1],
 					&cnt3[(ci + 1) % 3], &cnt3[(ci + 2) % 3], nlev);
 				SPS_LAUNCH_CHECK();
+				++peel[1];
 				++L; cur ^= 1; ci = (ci + 1) % 3;
 			}
 		}
@@ -482,8 +484,9 @@ int solve_tri(spsamd_ctx *c, const spsamd_coo *A, char transpose, int uplo, int 
 	SolveSchedule local;
 	SolveSchedule *s = hp && hp->owns ? &hp->solve[uplo][diag] : &local;
 	const bool reused = s->built;
+	uint64_t peel[2] = {0, 0};
 	if (!reused) {
-		try { analyse(c, t, s == &local ? nullptr : hp, s); }
+		try { analyse(c, t, s == &local ? nullptr : hp, s, peel); }
 		catch (...) { *s = SolveSchedule(); throw; }
 	}
 	SPS_HIP(hipEventRecord(c->ev[EV_SYMBOLIC], st));
@@ -540,6 +543,7 @@ int solve_tri(spsamd_ctx *c, const spsamd_coo *A, char transpose, int uplo, int 
 		stats->launches = launches; stats->fused_levels = fused;
 		stats->tuples_used = s->tuples_used; stats->zero_pivot = s->zero_pivot;
 		stats->analysis_reused = reused ? 1u : 0u;
+		stats->peel_thin_launches = peel[0]; stats->peel_wide_launches = peel[1];
 		stats->ms_analysis = res->ms_symbolic; stats->ms_solve = res->ms_numeric;
 	}
 	return SPSAMD_OK;

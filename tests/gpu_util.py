@@ -1,5 +1,6 @@
 """What the GPU test files (tests/test_gpu_*.py, tests/test_*_cpp.py, tests/test_abi.py) share: the context fixture, operands
-as C structs, the bit-for-bit tuple check, the path-knob wrapper, the memory sampler and the g++ line of the C++ tests.
+as C structs, the bit-for-bit tuple check, the path-knob wrapper, the solve wrapper and its bit check, the memory sampler
+and the g++ line of the C++ tests.
 Importing it needs no GPU.  The seeded input makers stay with their tests: no two of them draw the same random stream."""
 import contextlib
 import os
@@ -86,6 +87,49 @@ def forced(ctx, knob, value):
         yield
     finally:
         ctx.set_tuning(knob, 0)
+
+
+# ---- spsamd_solve_tri (tests/test_gpu_solve.py, tests/test_gpu_solve_wide.py)
+
+SENT = -7.5          # what solve() fills X and the padding of B and X with
+
+
+def bits_same(got, want, what):
+    got, want = np.ascontiguousarray(got, np.float64), np.ascontiguousarray(want, np.float64)
+    assert got.shape == want.shape, "%s: shape %r, want %r" % (what, got.shape, want.shape)
+    bad = np.argwhere(got.view(np.int64) != want.view(np.int64))
+    assert bad.size == 0, "%s: %d values differ, first at %r: %r (%#x) vs %r (%#x)" % (
+        what, len(bad), tuple(bad[0]), got[tuple(bad[0])], got.view(np.uint64)[tuple(bad[0])],
+        want[tuple(bad[0])], want.view(np.uint64)[tuple(bad[0])])
+
+
+def solve(ctx, a, B, uplo=0, diag=0, t='.', pol=ar.ADD, zn=False, device=False, in_place=False, pad=1):
+    """One solve through padded buffers (ld = nrhs + pad, the padding sentinel-filled and checked untouched).
+    Returns (X as a host array, stats)."""
+    B = np.ascontiguousarray(B, np.float64)
+    n, nrhs = B.shape
+    ld = nrhs + pad
+    hb = np.full((n, ld), SENT)
+    hb[:, :nrhs] = B
+    hx = hb if in_place else np.full((n, ld), SENT)
+    if device:
+        import torch
+        tb = torch.from_numpy(hb).cuda()
+        tx = tb if in_place else torch.from_numpy(hx).cuda()
+        torch.cuda.synchronize()
+        _, st = ctx.solve_tri(a, tb[:, :nrhs], uplo, diag, t, X=tx[:, :nrhs], duplicate_policy=pol, zero_nan=zn, stats=True)
+        gx, gb = tx.cpu().numpy(), tb.cpu().numpy()
+    else:
+        _, st = ctx.solve_tri(a, hb[:, :nrhs], uplo, diag, t, X=hx[:, :nrhs], duplicate_policy=pol, zero_nan=zn, stats=True)
+        gx, gb = hx, hb
+    assert np.all(gx[:, nrhs:] == SENT), "the padding of X was written"
+    if not in_place:
+        assert np.all(gb[:, nrhs:] == SENT) and np.array_equal(gb[:, :nrhs].view(np.int64), B.view(np.int64)), "B was written"
+    return gx[:, :nrhs].copy(), st
+
+
+def rhs(rng, n, nrhs, special=0.05):
+    return ar._values(rng, n * nrhs, special).reshape(n, nrhs)
 
 
 class PeakMemory:

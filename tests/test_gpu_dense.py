@@ -283,3 +283,70 @@ def test_errors(ctx):
     with pytest.raises(capi.SpsamdError) as e:
         ctx.multiply_dense(bad, X, Y)
     assert e.value.code == EINVAL
+
+
+def test_more_pairs_than_the_serial_grid(ctx):
+    """256 rows per CU and one more, 64 right-hand sides, rows of 0 to 3 tuples: 64 (row, rhs) pairs more than
+    k_spmm_serial's capped grid of 64 workgroups per CU has threads, so its stride loop takes a second trip."""
+    import torch
+    cus = torch.cuda.get_device_properties(0).multi_processor_count
+    nrow, ncol, nrhs = cus * 256 + 1, 3000, 64
+    assert nrow * nrhs > cus * 64 * 256
+    rng = np.random.default_rng(21)
+    i0 = np.repeat(np.arange(nrow), rng.integers(0, 4, nrow)).astype(np.int32)
+    i0[-1] = nrow - 1                                      # the last row, the one past the grid, has a tuple
+    i1 = rng.integers(0, ncol, i0.size).astype(np.int32)
+    v = rng.standard_normal(i0.size)
+    X = rng.standard_normal((ncol, nrhs))
+    Y = rng.standard_normal((nrow, nrhs))
+    got = _apply(ctx, i0, i1, v, (nrow, ncol), X, Y, sort0=0, device=True)
+    _check(got, i0, i1, v, X, Y, '.', dr.ADD, False, "%d rows x %d" % (nrow, nrhs))
+
+
+@pytest.mark.parametrize("large", ["X", "Y"])
+def test_offsets_beyond_2_to_the_32(ctx, large):
+    """rows * ld > 2^32 values in X (the columns of M name its last rows) or in Y (the rows of M are its last rows): about
+    34 GB on the device, col * ldx and row * ldy in 64 bits in the serial, lanes and fold kernels.  Rows of 1 to 150 tuples."""
+    import torch
+    from spsparse_amd import capi
+    dev = torch.device("cuda", 0)
+    big, small, ld, nrhs = (1 << 22) + 8, 64, 1025, 3
+    assert big * ld > 1 << 32
+    rng = np.random.default_rng({"X": 31, "Y": 32}[large])
+    named = np.r_[0, 1, np.arange(big - 40, big)]
+    m = 600
+    far = rng.choice(named, m)
+    far[:150] = big - 1                                    # 150 tuples on the last row of the large array: a long row / column
+    near = rng.integers(0, small, m)
+    near[150:300] = 7                                      # ... and a long row or column on the small side
+    o = rng.permutation(m)
+    far, near = far[o].astype(np.int32), near[o].astype(np.int32)
+    v = rng.standard_normal(m)
+    i0, i1, shape = (near, far, (small, big)) if large == "X" else (far, near, (big, small))
+    M, _keep = capi.host_coo(i0, i1, v, shape)
+    Lh = np.zeros((big, nrhs))
+    Lh[named] = rng.standard_normal((named.size, nrhs))
+    Sh = rng.standard_normal((small, nrhs))
+    Xh, Yh = (Lh, Sh) if large == "X" else (Sh, Lh)
+    want = dr.apply_fast(i0, i1, v, Xh, Yh)
+    assert np.count_nonzero(np.any(want != Yh, axis=1)) >= (40 if large == "Y" else 60)
+    idx = torch.from_numpy(named).to(dev)
+    L = torch.zeros((big, ld), dtype=torch.float64, device=dev)
+    S = torch.empty((small, nrhs), dtype=torch.float64, device=dev)
+    try:
+        for path in (1, 2, 3):
+            L[idx, :nrhs] = torch.from_numpy(Lh[named]).to(dev)
+            S.copy_(torch.from_numpy(Sh))
+            torch.cuda.synchronize()
+            tX, tY = (L[:, :nrhs], S) if large == "X" else (S, L[:, :nrhs])
+            ctx.set_tuning("spmm_path", path)
+            try:
+                ctx.multiply_dense(M, tX, tY)
+            finally:
+                ctx.set_tuning("spmm_path", 0)
+            _check(tY.cpu().numpy(), i0, i1, v, Xh, Yh, '.', dr.ADD, False, "64-bit %s path=%d" % (large, path), want)
+            assert dr.same_bits(tX.cpu().numpy(), Xh), "X was written"
+        assert int(torch.count_nonzero(L[:, nrhs:])) == 0, "the padding of the large array was written"
+    finally:
+        del L
+        torch.cuda.empty_cache()

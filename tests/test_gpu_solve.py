@@ -11,50 +11,11 @@ from spsparse_amd import workloads as wl
 from tests import add_ref as ar
 from tests import select_ref as sel
 from tests import solve_ref as sr
-from tests.gpu_util import coo as _coo, ctx, forced  # noqa: F401
+from tests.gpu_util import SENT, bits_same as _bits_same, coo as _coo, ctx, forced, rhs as _rhs, solve as _solve  # noqa: F401
 
 pytestmark = pytest.mark.gpu
 
-SENT = -7.5
 NRHS = (1, 2, 3, 15, 16, 17, 64, 65)
-
-
-def _bits_same(got, want, what):
-    got, want = np.ascontiguousarray(got, np.float64), np.ascontiguousarray(want, np.float64)
-    assert got.shape == want.shape, "%s: shape %r, want %r" % (what, got.shape, want.shape)
-    bad = np.argwhere(got.view(np.int64) != want.view(np.int64))
-    assert bad.size == 0, "%s: %d values differ, first at %r: %r (%#x) vs %r (%#x)" % (
-        what, len(bad), tuple(bad[0]), got[tuple(bad[0])], got.view(np.uint64)[tuple(bad[0])],
-        want[tuple(bad[0])], want.view(np.uint64)[tuple(bad[0])])
-
-
-def _solve(ctx, a, B, uplo=0, diag=0, t='.', pol=ar.ADD, zn=False, device=False, in_place=False, pad=1):
-    """One solve through padded buffers (ld = nrhs + pad, the padding sentinel-filled and checked untouched).
-    Returns (X as a host array, stats)."""
-    B = np.ascontiguousarray(B, np.float64)
-    n, nrhs = B.shape
-    ld = nrhs + pad
-    hb = np.full((n, ld), SENT)
-    hb[:, :nrhs] = B
-    hx = hb if in_place else np.full((n, ld), SENT)
-    if device:
-        import torch
-        tb = torch.from_numpy(hb).cuda()
-        tx = tb if in_place else torch.from_numpy(hx).cuda()
-        torch.cuda.synchronize()
-        _, st = ctx.solve_tri(a, tb[:, :nrhs], uplo, diag, t, X=tx[:, :nrhs], duplicate_policy=pol, zero_nan=zn, stats=True)
-        gx, gb = tx.cpu().numpy(), tb.cpu().numpy()
-    else:
-        _, st = ctx.solve_tri(a, hb[:, :nrhs], uplo, diag, t, X=hx[:, :nrhs], duplicate_policy=pol, zero_nan=zn, stats=True)
-        gx, gb = hx, hb
-    assert np.all(gx[:, nrhs:] == SENT), "the padding of X was written"
-    if not in_place:
-        assert np.all(gb[:, nrhs:] == SENT) and np.array_equal(gb[:, :nrhs].view(np.int64), B.view(np.int64)), "B was written"
-    return gx[:, :nrhs].copy(), st
-
-
-def _rhs(rng, n, nrhs, special=0.05):
-    return ar._values(rng, n * nrhs, special).reshape(n, nrhs)
 
 
 def test_semantic_fuzz(ctx):

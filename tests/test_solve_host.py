@@ -171,3 +171,103 @@ def test_the_other_triangle_is_ignored():
     assert same(sr.solve_ref(S, n, B, sr.UPPER), sr.solve_ref(tuple(x[up] for x in S), n, B, sr.UPPER))
     poison = (S[0], S[1], np.where(lo, S[2], np.nan))
     assert same(sr.solve_ref(poison, n, B), sr.solve_ref(S, n, B))
+
+
+def test_peel_plan_by_hand():
+    T, K = 8, 4
+    pp = lambda sizes: sr.peel_plan(sizes, T, K)
+    assert pp([]) == (0, 0) and pp([100]) == (0, 0) and pp([3]) == (0, 0)      # one level: no off-diagonal tuple, no peel
+    assert pp([3, 2]) == (1, 0) and pp([1] * 50) == (1, 0)                     # thin to the end: one launch, no batch
+    assert pp([8, 8, 8]) == (1, 0)                                             # thin_max itself is thin
+    assert pp([9, 1]) == (0, 4) and pp([9, 9]) == (0, 4)                       # wide first: a batch, whatever follows in it
+    assert pp([9] * 4) == (0, 4) and pp([9] * 5) == (0, 8)                     # a batch is `batch` levels; the fifth needs another
+    assert pp([9] * 8) == (0, 8) and pp([9] * 9) == (0, 12)
+    assert pp([9] * 4 + [5]) == (1, 4)                                         # thin after a full batch: no batch after it
+    assert pp([9] * 4 + [5, 1, 9]) == (1, 8)                                   # ... unless it widens again
+    assert pp([2, 9]) == (1, 4)                                                # thin hands over at the first wide level
+    assert pp([2, 9, 1, 1, 1, 8, 2]) == (2, 4)                                 # the batch swallows thin levels; the host sees the 8
+    assert pp([2, 9, 1, 1, 1, 9, 2]) == (1, 8)                                 # ... or a 9: wide again, no thin launch between
+    assert pp([1, 9, 9, 9, 9, 8, 1, 1, 1, 1, 1, 9]) == (2, 8)
+    assert sr.peel_plan([2049] * 17, 2048, 16) == (0, 32) and sr.peel_plan([2048] * 17, 2048, 16) == (1, 0)
+
+
+def _lower_levels_ok(A, n, lev, sizes):
+    assert np.array_equal(sr.levels(A, n), lev) and np.array_equal(np.bincount(lev), sizes)
+    assert np.all(np.diff(A[0]) >= 0)
+
+
+def test_builders_have_the_levels_they_claim():
+    rng = np.random.default_rng(21)
+    sizes = [5, 3, 4]
+    for scatter in (False, True):
+        A, n, lev = sr.by_levels(rng, sizes, scatter=scatter)
+        _lower_levels_ok(A, n, lev, sizes)
+        B = rng.standard_normal((n, 2))
+        assert same(sr.solve_fast(A, n, B, lev=lev), sr.solve_ref(A, n, B))
+    A, n, lev = sr.by_levels(rng, [60, 50, 70, 9], scatter=True)
+    assert np.any(np.diff(lev) < 0)                                            # scattered: the levels are not in row order
+    # hubs: a fan of 7 from a lone row, a fan of 6 among 5 rows, a row gathering 9 of 11
+    for sizes, fan, gather, hub_deg in (([1, 7, 3], {0: 7}, None, 7), ([5, 12, 4], {0: 6}, None, 6), ([4, 11, 6, 2], None, {2: 9}, 9)):
+        A, n, lev = sr.by_levels(rng, sizes, fan=fan, gather=gather)
+        _lower_levels_ok(A, n, lev, sizes)
+        off = A[1] < A[0]
+        if fan:
+            dependants = np.bincount(A[1][off], minlength=n)
+            hub = int(np.argmax(dependants))
+            assert dependants[hub] == hub_deg and lev[hub] == 0
+            others = dependants[(lev == 0) & (np.arange(n) != hub)]
+            assert others.size == sizes[0] - 1 and np.all((others >= 1) & (others <= 2))
+        else:
+            indeg = np.bincount(A[0][off], minlength=n)
+            hub = int(np.argmax(indeg))
+            assert indeg[hub] == hub_deg and lev[hub] == 2 and np.unique(A[1][off & (A[0] == hub)]).size == hub_deg
+            assert np.all(lev[A[1][off & (A[0] == hub)]] == 1)
+        B = rng.standard_normal((n, 3))
+        want = sr.solve_ref(A, n, B)
+        assert same(sr.solve_fast(A, n, B, lev=lev), want)
+        U, ulev = sr.mirrored(A, n, lev)
+        assert np.array_equal(sr.levels(U, n, sr.UPPER), ulev) and np.all(U[1] >= U[0]) and np.all(np.diff(U[0]) >= 0)
+        assert same(sr.solve_fast(U, n, B[::-1], sr.UPPER, lev=ulev), want[::-1])       # the same chains, renumbered
+        assert same(sr.solve_ref(U, n, B[::-1], sr.UPPER), want[::-1])
+
+
+def test_pattern_noise_moves_no_level():
+    rng = np.random.default_rng(22)
+    sizes = [9, 9, 9]
+    A, n, lev = sr.by_levels(rng, sizes)
+    drop, nz = (int(x) for x in np.flatnonzero(lev == 1)[:2])
+    N = sr.pattern_noise(rng, A, n, lev, drop, nz)
+    assert np.all(np.diff(N[0]) >= 0) and len(N[2]) > len(A[2]) + n // 2
+    keys = N[0].astype(np.int64) * n + N[1]
+    low = N[1] < N[0]
+    assert np.unique(keys[low]).size < np.count_nonzero(low) and np.any(N[2][low] == 0.0)      # duplicates and explicit zeros
+    assert np.any(N[1] > N[0]) and np.any(np.isnan(N[2][N[1] > N[0]]))
+    assert sr.zero_pivot(N, n) == min(drop, nz) and sr.zero_pivot(N, n, diag=sr.UNIT) == -1
+    B = rng.standard_normal((n, 2))
+    for diag in (sr.NONUNIT, sr.UNIT):
+        assert np.array_equal(sr.levels(N, n, sr.LOWER, diag), lev)                # trusted: by pattern
+        assert same(sr.solve_fast(N, n, B, sr.LOWER, diag, lev=lev), sr.solve_ref(N, n, B, sr.LOWER, diag))
+    assert not np.all(np.isfinite(sr.solve_ref(N, n, B)))
+    U, ulev = sr.mirrored(N, n, lev)
+    assert np.array_equal(sr.levels(U, n, sr.UPPER), ulev)
+    for pol in (ar.LEAVE_ALONE, ar.ADD, ar.REPLACE):                                # raw: merged, zeros dropped, the levels stay
+        o = rng.permutation(len(N[2]))
+        S = sel.operand_S(tuple(x[o] for x in N), '.', pol, False, -1)
+        assert np.array_equal(sr.levels(S, n), lev), pol
+        St = sel.operand_S((N[1][o], N[0][o], N[2][o]), 'T', pol, False, -1)
+        assert all(np.array_equal(x, y) for x, y in zip(S[:2], St[:2]))
+
+
+def test_far_rows():
+    rng = np.random.default_rng(23)
+    A, lev, named = sr.far_rows(rng, 100, 12)
+    assert np.array_equal(sr.levels(A, 100), lev) and lev.max() == 13 and np.array_equal(named, np.r_[0, 1, np.arange(88, 100)])
+    assert np.count_nonzero(A[0] == 99) == 12 and np.all(A[2][A[0] == A[1]] > 0)
+    off = A[0] != A[1]
+    assert np.all(np.isin(A[0][off], named)) and np.all(np.isin(A[1][off], named))
+    B = np.zeros((100, 3))
+    B[named] = rng.standard_normal((named.size, 3))
+    X = sr.solve_ref(A, 100, B)
+    assert same(sr.solve_fast(A, 100, B, lev=lev), X)
+    rest = np.setdiff1d(np.arange(100), named)
+    assert not X[rest].view(np.int64).any() and np.all(X[named] != 0)            # an unnamed row is +0.0 / d = +0.0
