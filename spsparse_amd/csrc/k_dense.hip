@@ -27,7 +27,17 @@ namespace spsamd {
 // stores the same 1 (29.0 -> 28.0 ms on cfg2; the launch is bound by the B reads, not by the accumulator).
 // (Its flag bytes are not swizzled: the remap costs the launch 17 VGPRs, 71 -> 88, which is one wave per SIMD less than its
 // three workgroups per CU need.)
-template <int W, int NT, int MODE, bool PAT>
+// PLAIN (emit_plain, spgemm_dev.h: C = 1, no scale vector) is a fact of the instantiation for the STORE and DIGEST launches
+// without EXACT_PATTERN: no scale is read, nothing is multiplied and no flag is branched on in the scan-out.
+// The scan-out takes a wave's groups in batches (measured on cfg2, profiles/plain/: exchange in batches of 8 22.3 ms, read
+// then store 22.7, all 16 groups at once 22.7 / 23.2, one group at a time with the general emit in line 26.3).
+#ifndef DENSE_SCAN_BATCH
+#define DENSE_SCAN_BATCH 8
+#endif
+#ifndef DENSE_SCAN_XCHG
+#define DENSE_SCAN_XCHG 1
+#endif
+template <int W, int NT, int MODE, bool PAT, bool PLAIN>
 __global__ __launch_bounds__(NT, 4) void k_dense(const Cell *cells, uint32_t ncell, const uint32_t *xb, RowMeta m,
 	const uint32_t *widx, uint64_t kstride, uint64_t wstride, uint32_t narrow, EmitParams ep, SinkParams sk, uint32_t *claim_ctr)
 {
@@ -38,6 +48,9 @@ __global__ __launch_bounds__(NT, 4) void k_dense(const Cell *cells, uint32_t nce
 	constexpr int R = DENSE_R;
 	constexpr int NWORD = W / 64;            // bitmap words of one batch (W items)
 	constexpr int WPL = NWORD / 64;          // words per lane of the per-wave copy
+	constexpr int SB = DENSE_SCAN_BATCH < GPW ? DENSE_SCAN_BATCH : GPW;     // groups of one scan-out batch
+	static_assert(GPW % SB == 0, "whole batches");
+	static_assert(!PLAIN || (!PAT && MODE != MODE_COUNT), "PLAIN: STORE and DIGEST without EXACT_PATTERN");
 	__shared__ double acc[MODE == MODE_COUNT ? 1 : W + 64];      // + one dump slot per lane: tuples past the end of a segment's last item land there
 	__shared__ __attribute__((aligned(16))) uint8_t ctouch[MODE == MODE_COUNT ? W : 16];     // COUNT: the touched columns
 	__shared__ uint32_t s_cpref[NT + 1];     // compacted segments: exclusive ITEM prefix (+ total)
@@ -62,7 +75,7 @@ __global__ __launch_bounds__(NT, 4) void k_dense(const Cell *cells, uint32_t nce
 	if (MODE == MODE_COUNT) { for (int q = tid; q < W / 16; q += NT) reinterpret_cast<uint4 *>(ctouch)[q] = make_uint4(0, 0, 0, 0); }
 	else for (int q = tid; q < W + 64; q += NT) acc[q] = CLEAN;
 	for (int q = tid; q < NWORD; q += NT) s_bmask[q] = 0ull;
-	const bool plain = ep.C == 1.0 && !ep.si_pos && !ep.sk_pos;    // uniform: the emitted value is the sum itself
+	const bool plain = PLAIN || (PAT && emit_plain(ep));            // uniform: the emitted value is the sum itself (without EXACT_PATTERN the launcher sends a plain call to PLAIN)
 	const unsigned long long laneK = (unsigned long long)lane * 0x9E3779B97F4A7C15ull;
 	unsigned long long d_cnt = 0, d_hash = 0; double d_sum = 0;     // DIGEST, whole launch
 	PatAcc pat; pat_init(pat);
@@ -143,7 +156,8 @@ __global__ __launch_bounds__(NT, 4) void k_dense(const Cell *cells, uint32_t nce
 		const uint32_t w = cell.wa;
 		const uint32_t beg = cell.beg, end = cell.end;
 		const int32_t rowid = cell.rowid;
-		const double a_scale = row_scale(ep, rowid);
+		double a_scale = 1.0;
+		if constexpr (!PLAIN) a_scale = row_scale(ep, rowid);
 		const uint32_t wbase = w << WSHIFT;
 		uint32_t lo = nlo, len = nlen; double a = na;               // chunk 0, prefetched
 		rec1 = cell_from_pend(pend2);
@@ -360,8 +374,8 @@ __global__ __launch_bounds__(NT, 4) void k_dense(const Cell *cells, uint32_t nce
 		// mix64's product evaluated as X0 + lane * K with the group's X0 kept in scalar registers.
 		const double pthr = PAT ? pat_threshold(&s_pat, pnseg) : -1.0;
 		const uint32_t pbeg = beg, pend = end;
-		double v[GPW];
-		uint64_t nzmask[GPW];
+		double v[MODE == MODE_STORE ? GPW : 1];                     // (the COO store alone needs a group's value and ballot past the group)
+		uint64_t nzmask[MODE == MODE_STORE ? GPW : 1];
 		uint32_t wcount = 0;
 		constexpr unsigned long long MIXK = 0x9E3779B97F4A7C15ull;
 		unsigned long long X0 = ((((unsigned long long)(uint32_t)rowid) << 32) | (unsigned long long)(wbase + wv * GPW * 64u)) * MIXK;   // uniform
@@ -393,22 +407,43 @@ __global__ __launch_bounds__(NT, 4) void k_dense(const Cell *cells, uint32_t nce
 			}
 			wcount = (uint32_t)wave_reduce_sum((unsigned long long)cnt);
 		} else {
+		// In batches of SB groups: a batch's slots are all exchanged with the clean value (read and clean in one LDS operation,
+		// as k_bm_tiles' emission does; DENSE_SCAN_XCHG 0: all read, then all cleaned with stores) before the first of them is
+		// looked at, so the wave waits for LDS once per batch and not once per group; the zero test, ballot, count, hash and
+		// sum -- and in the general instantiation emit_value's global loads -- then run on registers.
+		auto slot_of = [&](int gi) -> uint32_t {                    // group gi of this wave, this lane's slot (a permutation of the group's 64 slots: conflict-free)
+			const int grp = wv * GPW + gi;
+			return grp * 64 + (lane ^ (uint32_t)__builtin_amdgcn_readfirstlane((int)dense_swz((uint32_t)grp)));
+		};
+		double xs[SB];
 #pragma unroll
 		for (int gi = 0; gi < GPW; ++gi) {
-			int grp = wv * GPW + gi;
-			const uint32_t ps = grp * 64 + (lane ^ (uint32_t)__builtin_amdgcn_readfirstlane((int)dense_swz((uint32_t)grp)));     // (a permutation of the group's 64 slots: conflict-free)
-			double x = acc[ps];
-			acc[ps] = CLEAN;
-			bool ok;
-			if (MODE != MODE_COUNT && PAT) {
-				const bool touched = __double_as_longlong(x) != (long long)0x8000000000000000ull;
-				x = pat_fix_wave(touched && !(fabs(x) > pthr), x, (int32_t)(wbase + grp * 64 + lane), m, pbeg, pend);
+			if (gi % SB == 0) {                                         // (compile time: the loop is unrolled)
+#if DENSE_SCAN_XCHG
+				unsigned long long *acc64 = reinterpret_cast<unsigned long long *>(acc);
+#pragma unroll
+				for (int q = 0; q < SB; ++q) xs[q] = __longlong_as_double((long long)atomicExch(&acc64[slot_of(gi + q)], (unsigned long long)__double_as_longlong(CLEAN)));
+#else
+#pragma unroll
+				for (int q = 0; q < SB; ++q) xs[q] = acc[slot_of(gi + q)];
+#pragma unroll
+				for (int q = 0; q < SB; ++q) acc[slot_of(gi + q)] = CLEAN;
+#endif
+				// (left to itself the scheduler moves each group's arithmetic up behind its own request and waits there with
+				// lgkmcnt(0): the round trip per group again)
+				__builtin_amdgcn_sched_barrier(0);
 			}
-			if (plain) ok = x != 0;
-			else ok = emit_value(ep, a_scale, (int32_t)(wbase + grp * 64 + lane), x, &x);
-			v[gi] = x;
-			nzmask[gi] = __ballot(ok);
-			wcount += (uint32_t)__popcll(nzmask[gi]);
+			const int grp = wv * GPW + gi;
+			const int32_t col = (int32_t)(wbase + grp * 64 + lane);
+			double x = xs[gi % SB];
+			if (PAT) {
+				const bool touched = __double_as_longlong(x) != (long long)0x8000000000000000ull;
+				x = pat_fix_wave(touched && !(fabs(x) > pthr), x, col, m, pbeg, pend);
+			}
+			const bool ok = emit_test<PLAIN>(plain, ep, a_scale, col, x);
+			const uint64_t mk = __ballot(ok);
+			wcount += (uint32_t)__popcll(mk);
+			if (MODE == MODE_STORE) { v[gi] = x; nzmask[gi] = mk; }
 			if (MODE == MODE_DIGEST) {
 				unsigned long long h = X0 + laneK;
 				h ^= h >> 29;
@@ -486,10 +521,14 @@ void launch_heavy_dense(spsamd_ctx *c, const Heavy &hv, const RowMeta &m0, const
 	// cells in flight, fewer L2 hits; with the claimed XCD parts: 23.5 / 20.8 / 20.9)
 	if (grid >= 64) grid &= ~7u;
 	const SinkParams &sks = stamps_sink(c, sk, grid);
-	auto go = [&](auto w, auto nt, auto pat) {
-		k_dense<decltype(w)::value, decltype(nt)::value, MODE, decltype(pat)::value><<<dim3(grid), dim3(decltype(nt)::value), 0, c->stream>>>(hv.cells[CLS_DENSE], hv.ncell[CLS_DENSE], hv.xb[CLS_DENSE], m, widx, kstride, wstride, narrow, ep, sks, claim);
+	auto go = [&](auto w, auto nt, auto pat, auto pln) {
+		k_dense<decltype(w)::value, decltype(nt)::value, MODE, decltype(pat)::value, decltype(pln)::value><<<dim3(grid), dim3(decltype(nt)::value), 0, c->stream>>>(hv.cells[CLS_DENSE], hv.ncell[CLS_DENSE], hv.xb[CLS_DENSE], m, widx, kstride, wstride, narrow, ep, sks, claim);
 	};
-	auto go_pat = [&](auto w, auto nt) { if (ep.pattern) go(w, nt, std::true_type{}); else go(w, nt, std::false_type{}); };
+	auto go_pat = [&](auto w, auto nt) {
+		if (ep.pattern) return go(w, nt, std::true_type{}, std::false_type{});
+		if constexpr (MODE != MODE_COUNT) { if (emit_plain(ep)) return go(w, nt, std::false_type{}, std::true_type{}); }
+		go(w, nt, std::false_type{}, std::false_type{});
+	};
 	if (hv.W == 8192) go_pat(std::integral_constant<int, 8192>{}, std::integral_constant<int, 512>{});
 	else go_pat(std::integral_constant<int, 16384>{}, std::integral_constant<int, 1024>{});
 	SPS_LAUNCH_CHECK();

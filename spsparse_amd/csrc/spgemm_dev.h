@@ -125,6 +125,20 @@ __device__ __forceinline__ bool col_allowed(const EmitParams &p, int32_t col)
 	return q >= 0 && p.sk_val[q] != 0;
 }
 
+// "Plain": C = 1 and no scale vector, the reference's default call.  The emitted value then IS the sum (sum * 1 * 1 * 1,
+// multiply_sparse.hpp:242, is the same bits) and no column is skipped.  k_dense has instantiations that know it at compile
+// time (PLAIN: its launcher asks here); elsewhere it is a uniform flag of the launch.
+__host__ __device__ __forceinline__ bool emit_plain(const EmitParams &p) { return p.C == 1.0 && !p.si_pos && !p.sk_pos; }
+
+// What an emission asks: is the sum emitted, and as which value (v is replaced).  PLAIN: no scale is read and nothing is
+// multiplied; otherwise `plain` is the launch's flag.
+template <bool PLAIN>
+__device__ __forceinline__ bool emit_test(bool plain, const EmitParams &p, double a_scale, int32_t col, double &v)
+{
+	if constexpr (PLAIN) return v != 0;
+	else return plain ? v != 0 : emit_value(p, a_scale, col, v, &v);
+}
+
 // ---- SPSAMD_SINK_EXACT_PATTERN: the index set of the reference, at arrival-order speed -----------------
 // Hash and dense cells add their products with LDS atomics in arrival order.  The VALUES then differ from the
 // reference's ascending-k sums by rounding only (north star: 1e-12), but the test `sum == 0` that decides whether a
