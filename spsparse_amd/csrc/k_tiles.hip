@@ -27,7 +27,9 @@ __global__ __launch_bounds__(TILE2_NT, 4) void k_hash_tiles2(const Tile *tiles, 
 	__shared__ uint16_t s_cnt[MODE == MODE_STORE ? 16 * ((T / 2 + NT - 1) / NT) * (NT / 64) : 1];
 	__shared__ TileX<NT, NWORD> X;
 	__shared__ uint32_t scr32[NW + 1];
-	__shared__ uint32_t s_nocc;
+	__shared__ uint32_t s_nocc[2];           // occupied slots of a cell.  Two counters taken in turn: every wave reads a cell's count behind the cell's first
+	// barrier and the DIGEST emission has no barrier of its own, so thread 0 resets the count a cell later, behind that cell's first barrier
+	// (reset right after its own emission it could reach a wave that had not read the count yet: that wave then emitted nothing and left its slots)
 	__shared__ PatCell s_pat;
 	__shared__ unsigned long long s_u64[2 * NW];
 	__shared__ double s_f64[NW];
@@ -38,11 +40,11 @@ __global__ __launch_bounds__(TILE2_NT, 4) void k_hash_tiles2(const Tile *tiles, 
 	for (int q = tid; q < T; q += NT) { h_key[q] = -1; if (MODE != MODE_COUNT) h_val[q] = 0.0; }
 	if (tid < 64) h_key[T + tid] = -1;
 	for (int q = tid; q < NWORD; q += NT) X.bmask[q] = 0ull;
-	if (tid == 0) s_nocc = 0;
+	if (tid < 2) s_nocc[tid] = 0;
 	PatAcc pat; pat_init(pat);
 	if (tid == 0) pat_reset(&s_pat);
 	DigestAcc dacc{0, 0, 0.0};
-	uint32_t flip = 0;
+	uint32_t flip = 0, oflip = 0;                                   // (oflip: the counter of the current cell)
 	const char *bbase = reinterpret_cast<const char *>(m.btup);
 	STAMP_BEGIN();
 	TileWalk<BoundsRowMajor, true> walk;
@@ -114,7 +116,7 @@ __global__ __launch_bounds__(TILE2_NT, 4) void k_hash_tiles2(const Tile *tiles, 
 				}
 				if (nnew) {                                                 // uniform: one LDS fetch-add per wave and step
 					uint32_t base = 0;
-					if (lane == 0) base = lds_add_rtn_u32(&s_nocc, nnew);
+					if (lane == 0) base = lds_add_rtn_u32(&s_nocc[oflip], nnew);
 					base = (uint32_t)__builtin_amdgcn_readfirstlane((int)base);
 #pragma unroll
 					for (int u = 0; u < R; ++u) {
@@ -127,7 +129,9 @@ __global__ __launch_bounds__(TILE2_NT, 4) void k_hash_tiles2(const Tile *tiles, 
 			STAMP(3);
 			lds_barrier();                                          // the cell's products are in the table
 			STAMP(4);
-			const uint32_t nocc = s_nocc;
+			const uint32_t nocc = s_nocc[oflip];
+			if (tid == 0) s_nocc[oflip ^ 1u] = 0;                   // the previous cell's count: every wave read it before that cell's last barrier; the next cell adds to it behind this one's
+			oflip ^= 1u;
 			// the next cell's first block: lookup and B request issued now, consumed after the emission
 			if (c + 1 < tile.ncells) {                              // uniform
 				tile_lookup(X, tab, nzc, (i1 >> 6) + wv, X.cellI[c + 2], pbp, pnv, pav);
@@ -144,9 +148,8 @@ __global__ __launch_bounds__(TILE2_NT, 4) void k_hash_tiles2(const Tile *tiles, 
 			const double pthr = PAT ? pat_threshold(&s_pat, tile.end - tile.beg) : -1.0;
 			hash_emit<T, NT, MODE, PAT>(nocc, rowid, seg, ep, sk, h_key, h_val, occ, s_sort, scr32, dacc, s_cnt, colbase, colbits, m, tile.beg, tile.end, pthr);
 			if (PAT) { lds_barrier(); if (tid == 0) pat_reset(&s_pat); }
-			if (tid == 0) s_nocc = 0;
 			STAMP(6);
-			lds_barrier();                                          // table clean, counter reset: next cell may insert
+			lds_barrier();                                          // table clean, the other counter reset: next cell may insert
 			STAMP(7);
 		}
 		for (int q = tid; q < NWORD; q += NT) X.bmask[q] = 0ull;     // (every wave is past its last lookup: the cell loop ends with a barrier)

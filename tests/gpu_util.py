@@ -1,5 +1,5 @@
 """What the GPU test files (tests/test_gpu_*.py, tests/test_*_cpp.py, tests/test_abi.py) share: the context fixture, operands
-as C structs, the bit-for-bit tuple check, the path-knob wrapper, the solve wrapper and its bit check, the memory sampler
+as C structs, the bit-for-bit tuple check, the exact digest check, the path-knob wrappers, the solve wrapper and its bit check, the memory sampler
 and the g++ line of the C++ tests.
 Importing it needs no GPU.  The seeded input makers stay with their tests: no two of them draw the same random stream."""
 import contextlib
@@ -87,6 +87,30 @@ def forced(ctx, knob, value):
         yield
     finally:
         ctx.set_tuning(knob, 0)
+
+
+class Knobs:
+    """Several tuning knobs for the calls inside; all of them back to 0 (their defaults) afterwards."""
+
+    def __init__(self, ctx, knobs):
+        self.ctx, self.knobs = ctx, knobs
+
+    def __enter__(self):
+        for k, v in self.knobs.items():
+            self.ctx.set_tuning(k, v)
+
+    def __exit__(self, *exc):
+        for k in self.knobs:
+            self.ctx.set_tuning(k, 0)
+
+
+def check_digest(res, want, what):
+    """A digest result against the digest of the oracle's tuples: count, hash and value sum, all exact (for values whose
+    sums are exact in any order)."""
+    from oracle import binding as orc
+    cnt, vsum, h = orc.digest(*want[:3])
+    assert (res.nnz, res.hash) == (cnt, h), "%s: digest sink: nnz %d hash %x, want %d %x" % (what, res.nnz, res.hash, cnt, h)
+    assert res.sum == vsum, "%s: digest sink: sum %r, want %r" % (what, res.sum, vsum)
 
 
 # ---- spsamd_solve_tri (tests/test_gpu_solve.py, tests/test_gpu_solve_wide.py)

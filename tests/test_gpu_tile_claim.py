@@ -15,7 +15,7 @@ import pytest
 
 from oracle import binding as orc
 from spsparse_amd import workloads as wl
-from tests.gpu_util import ctx  # noqa: F401  (fixture)
+from tests.gpu_util import Knobs as _Knobs, ctx  # noqa: F401  (ctx: fixture)
 
 pytestmark = pytest.mark.gpu
 
@@ -55,21 +55,6 @@ def _check_digest(res, tuples):
     cnt, s_, h = orc.digest(*tuples[:3])
     assert res.nnz == cnt and res.hash == h
     assert abs(res.sum - s_) <= DIGEST_REL * abs(s_)
-
-
-class _Knobs:
-    """Tuning knobs for the calls inside; all of them back to 0 (their defaults) afterwards."""
-
-    def __init__(self, ctx, knobs):
-        self.ctx, self.knobs = ctx, knobs
-
-    def __enter__(self):
-        for k, v in self.knobs.items():
-            self.ctx.set_tuning(k, v)
-
-    def __exit__(self, *exc):
-        for k in self.knobs:
-            self.ctx.set_tuning(k, 0)
 
 
 # ---- few tiles
