@@ -233,6 +233,16 @@ const char *spsamd_version(void);
  *                                     spmm_long_min tuples serial, the others lanes from 16 right-hand sides on, else fold)
  *   solve_fuse_rows > 0               solve_tri: the widest level that still counts as thin (default: 256 rows, and at most
  *                                     2048 (row, rhs) pairs; a set value is taken as given)
+ *   factor_path     1 | 2             factor_ilu0: 1 every level of the schedule in launches of its own | 2 every level whose
+ *                                     rows are all serial-class through the fused runs, whatever its width (default: such
+ *                                     levels of at most factor_fuse_rows rows fuse)
+ *   factor_row      1 | 2 | 3         factor_ilu0: every row with a lower tuple through the serial (a thread per row) | wave (a
+ *                                     wave per row, the row staged in LDS) | block (a workgroup per row, the row in memory)
+ *                                     kernel wherever that kernel can hold the row; a row too long for the wave kernel's LDS
+ *                                     copy falls to the block kernel (default: by the row's work and length)
+ *   factor_fuse_rows > 0              factor_ilu0: the widest level that still counts as thin (256 rows)
+ *   factor_serial_work > 0            factor_ilu0: rows of at most this many lookups are serial-class (64)
+ *   factor_lds_row  1..4096           factor_ilu0: the longest row (tuples) of the wave kernel's LDS copy (256)
  * The environment variables of the same purpose (SPSAMD_W ...) are read once, inside spsamd_ctx_create; nothing reads
  * the environment later.  Unknown names: SPSAMD_EINVAL. */
 int spsamd_ctx_set_tuning(spsamd_ctx *ctx, const char *name, long value);
@@ -644,6 +654,62 @@ int spsamd_solve_tri(spsamd_ctx *ctx, const spsamd_coo *A, char transpose, int u
 	const double *B, size_t ldb, double *X, size_t ldx, size_t nrhs, int mem,
 	int duplicate_policy, int zero_nan,
 	spsamd_solve_stats *stats /* may be NULL */, spsamd_result *result /* may be NULL */);
+
+/*
+ * ret = F, the incomplete LU factorisation of op(A) on its own pattern, ILU(0), by level schedule (the counterpart of
+ * rocSPARSE / cuSPARSE csrilu0, as spsamd_solve_tri is of csrsv).  F holds L strictly below the
+ * diagonal (its unit diagonal is implied) and U on and above it, so the application U^-1 L^-1 r is
+ * spsamd_solve_tri(F, LOWER, UNIT), then spsamd_solve_tri(F, UPPER, NONUNIT).
+ *   - Operand.  op(A) is taken exactly as spsamd_select takes it, with duplicate_policy and zero_nan: a raw operand is
+ *     consolidated by op()'s rows; an operand whose sort0 names op()'s row order is trusted as stored; a SINK_COO result of
+ *     this context and a prepared handle of the same transpose are read in place.  Call the resulting sequence S.  op(A)
+ *     must be square (SPSAMD_EDIM); n is its order.
+ *   - S must be strictly ascending in its (row, col) key: no duplicate key, columns ascending inside a row.  This is checked
+ *     on the device for every kind of operand, chained results included (a select of a trusted operand may descend inside a
+ *     row).  A violation is SPSAMD_EINVAL; the message names the first offending position, and nothing is written.  Explicit
+ *     zeros of a trusted operand are pattern.
+ *   - Result.  S's keys, all of them, in S's order, with the values f this loop defines:
+ *         f_t = value of tuple t of S, for every t
+ *         for i = 0 .. n-1:
+ *           for each tuple t = (i, k) of row i with k < i, in ascending k:
+ *               f_t = f_t / p_k           p_k: f of row k's diagonal tuple (final, since k < i); +0.0 if row k stores none
+ *               for each tuple s = (k, j) of row k with j > k:
+ *                   if row i stores a tuple u = (i, j):   f_u = f_u - f_t * f_s
+ *     The product is rounded, then the subtraction (no FMA); the division is a true IEEE division, not a multiplication by
+ *     a reciprocal; a NaN result carries the bits x86-64 gives it (mulsd, subsd, divsd: the left operand's NaN quieted, else
+ *     the right one's, else 0xFFF8000000000000; f_t is the left operand of the product).  Every f_u is one serial chain -- its
+ *     updates in ascending k, then (for j < i) one division -- so every value is defined bit for bit.  Nothing is dropped by
+ *     value: an f of 0.0, Inf or NaN is stored.  A missing or zero pivot is no error: the division gives what IEEE gives.
+ *   - The schedule is that of spsamd_solve_tri's LOWER triangle (off-diagonal tuples by pattern).  A prepared handle of the
+ *     same transpose uses and keeps the LOWER / NONUNIT schedule, so a factorisation after a Gauss-Seidel solve on the same
+ *     handle, or the reverse, analyses nothing (spsamd_operand_bytes grows once).  Level 0 (the rows without a lower tuple)
+ *     has no work: it is never launched, and not counted in fused_levels.
+ * Sinks as for spsamd_emult: SINK_COO (fetchable, chainable as a MEM_DEVICE sort0 = 0 operand -- sort0 = 1 with
+ * SINK_PERMUTE), SINK_DIGEST (+ ROWSTATS); SINK_ORDERED and SINK_EXACT_PATTERN are accepted and change nothing.  The operand
+ * may live in the context's current output set: F goes to the other set.
+ * stats (may be NULL): see the struct.  result: shape, nnz (= |S|), nnz_a (= |S|), products (= lookups), ms_consolidate,
+ * ms_symbolic (the row pass and the analysis), ms_numeric, ms_total, workspace_bytes; everything else 0 / NULL.
+ * SPSAMD_EINVAL, with a message and nothing written: A or result NULL; a bad policy or sink; an index out of bounds; a false
+ * sort0; 2^31 or more tuples; the ordering rule above.  n == 0 or an empty S: an empty result of op(A)'s shape.  Returns
+ * when the result is complete.
+ */
+typedef struct {
+	uint64_t levels, max_level_rows;  /* of the schedule */
+	uint64_t launches;                /* kernel launches of the numeric phase of this call */
+	uint64_t fused_levels;            /* levels (from level 1 on) served inside a fused run */
+	uint64_t lookups;                 /* sum over the lower tuples (i, k) of the tuples of row k right of its diagonal: the work */
+	uint64_t updates;                 /* the lookups that found a tuple in row i: the subtractions performed */
+	int64_t  zero_pivot;              /* smallest row whose final p_i is +-0.0, a row without a stored diagonal included (a NaN
+	                                     pivot is not one), else -1 */
+	int64_t  missing_diag;            /* smallest row that stores no diagonal, else -1 */
+	uint64_t rows_serial, rows_wave, rows_block;   /* rows with at least one lower tuple, by the kernel that served them */
+	uint32_t analysis_reused;         /* 1: the schedule came from a prepared handle */
+	float ms_analysis, ms_factor;
+} spsamd_factor_stats;
+
+int spsamd_factor_ilu0(spsamd_ctx *ctx, const spsamd_coo *A, char transpose,
+	int duplicate_policy, int zero_nan, int sink_kind, int sink_flags,
+	spsamd_factor_stats *stats /* may be NULL */, spsamd_result *result);
 
 /*
  * ret = (C * diag(scalei) * op(A) * diag(scalej) * op(B) * diag(scalek)) restricted to the keys of M  -- a masked product

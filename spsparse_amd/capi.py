@@ -42,6 +42,9 @@ DIAG_NONUNIT, DIAG_UNIT = 0, 1
 # launches of the wide peel between two looks at the frontier size
 solve_fuse_rows, solve_fuse_work, solve_fused_threads = 256, 2048, 1024
 peel_thin_max, peel_batch = 2048, 16
+# factor_ilu0: the defaults of the factor_fuse_rows, factor_serial_work and factor_lds_row knobs, and the most the last
+# may ask for
+factor_fuse_rows, factor_serial_work, factor_lds_row, factor_lds_row_max = 256, 64, 256, 4096
 
 ERRORS = {-1: "EDIM", -2: "EINVAL", -3: "EHIP", -4: "ENOMEM", -5: "ECAPACITY", -6: "ENODEVICE", -7: "EPEER"}
 
@@ -93,6 +96,14 @@ class SolveStats(C.Structure):
                 ("peel_thin_launches", C.c_uint64), ("peel_wide_launches", C.c_uint64)]
 
 
+class FactorStats(C.Structure):
+    _fields_ = [("levels", C.c_uint64), ("max_level_rows", C.c_uint64), ("launches", C.c_uint64),
+                ("fused_levels", C.c_uint64), ("lookups", C.c_uint64), ("updates", C.c_uint64),
+                ("zero_pivot", C.c_int64), ("missing_diag", C.c_int64),
+                ("rows_serial", C.c_uint64), ("rows_wave", C.c_uint64), ("rows_block", C.c_uint64),
+                ("analysis_reused", C.c_uint32), ("ms_analysis", C.c_float), ("ms_factor", C.c_float)]
+
+
 class DistStats(C.Structure):
     _fields_ = [("block_nnz_a", C.c_uint64), ("panel_tuples", C.c_uint64), ("remote_tuples", C.c_uint64),
                 ("sent_tuples", C.c_uint64), ("ms_exchange", C.c_float), ("pad_", C.c_float)]
@@ -112,7 +123,8 @@ SYMBOLS = ["spsamd_ctx_create", "spsamd_ctx_destroy", "spsamd_last_error", "spsa
            "spsamd_dist_unique_id", "spsamd_dist_create", "spsamd_dist_destroy", "spsamd_dist_multiply",
            "spsamd_operand_prepare", "spsamd_operand_as_coo", "spsamd_operand_bytes", "spsamd_operand_destroy",
            "spsamd_multiply_dense", "spsamd_add", "spsamd_multiply_stream", "spsamd_multiply_masked",
-           "spsamd_multiply_sampled", "spsamd_select", "spsamd_extract", "spsamd_reduce", "spsamd_emult", "spsamd_solve_tri"]
+           "spsamd_multiply_sampled", "spsamd_select", "spsamd_extract", "spsamd_reduce", "spsamd_emult", "spsamd_solve_tri",
+           "spsamd_factor_ilu0"]
 
 _lib = None
 
@@ -171,6 +183,7 @@ def load():
                                C.c_int, C.c_int, C.c_int, C.c_int, P(Result)]
     L.spsamd_solve_tri.argtypes = [C.c_void_p, P(Coo), C.c_char, C.c_int, C.c_int, C.c_void_p, C.c_size_t, C.c_void_p,
                                    C.c_size_t, C.c_size_t, C.c_int, C.c_int, C.c_int, P(SolveStats), P(Result)]
+    L.spsamd_factor_ilu0.argtypes = [C.c_void_p, P(Coo), C.c_char, C.c_int, C.c_int, C.c_int, C.c_int, P(FactorStats), P(Result)]
     L.spsamd_memcpy.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_size_t]
     L.spsamd_consolidate.argtypes = [C.c_void_p, P(Coo), C.c_int, C.c_int, C.c_int, P(Result)]
     L.spsamd_sorted_permutation.argtypes = [C.c_void_p, P(Coo), C.c_int, C.c_void_p]
@@ -498,6 +511,18 @@ class Context:
                                             mb, duplicate_policy, int(zero_nan), C.byref(st),
                                             None if result is None else C.byref(result)))
         return (X, st) if stats else X
+
+    def factor_ilu0(self, A, transpose='.', duplicate_policy=ADD, zero_nan=False, sink=SINK_COO, flags=0, stats=False):
+        """spsamd_factor_ilu0: F = ILU(0) of op(A) on its own pattern, bit for bit the row-wise loop of the header -- L
+        strictly below the diagonal (unit diagonal implied), U on and above it, S's keys in S's order.  A: a Coo struct
+        whose op() is square and strictly ascending in (row, col) once taken.  Returns the Result like emult (chain it with
+        result_operand, or prepare it and apply solve_tri(LOWER, UNIT) then solve_tri(UPPER, NONUNIT)), or
+        (Result, FactorStats) with stats=True."""
+        res, st = Result(), FactorStats()
+        rc = self.L.spsamd_factor_ilu0(self.h, C.byref(A), transpose.encode(), duplicate_policy, int(zero_nan), sink, flags,
+                                       C.byref(st), C.byref(res))
+        self._check(rc)
+        return (res, st) if stats else res
 
     def multiply_sampled(self, M, P, Q, out=None, transpose='.', alpha=1.0, beta=0.0):
         """spsamd_multiply_sampled: out[t] = alpha * (P[i] . Q[j]) (+ beta * v) for every tuple t = (i, j, v) of op(M) in

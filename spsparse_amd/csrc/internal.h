@@ -99,6 +99,11 @@ struct Tuning {
 	int solve_path = 0;          // solve_tri: 0 thin levels fuse | 1 every level a launch of its own | 2 every level of short rows fuses, whatever its width
 	int solve_row = 0;           // solve_tri: 0 by row length (spmm_long_min) | 1 serial | 2 lanes | 3 fold kernel for every row
 	int solve_fuse_rows = 0;     // solve_tri: the widest level that still counts as thin (0: 256 rows and 2048 (row, rhs) pairs)
+	int factor_path = 0;         // factor_ilu0: 0 thin levels fuse | 1 every level in launches of its own | 2 every level of serial-class rows fuses, whatever its width
+	int factor_row = 0;          // factor_ilu0: 0 by the row's work and length | 1 serial | 2 wave | 3 block kernel for every row it can hold
+	int factor_fuse_rows = 0;    // factor_ilu0: the widest level that still counts as thin (0: 256)
+	int factor_serial_work = 0;  // factor_ilu0: the most lookups of a serial-class row (0: 64)
+	int factor_lds_row = 0;      // factor_ilu0: the longest row of the wave kernel's LDS copy (0: 256; at most 4096)
 #ifdef SPSAMD_ABLATIONS
 	int dbg = 0;
 #endif
@@ -396,6 +401,9 @@ struct SolveSchedule {
 	uint32_t *level_ptr = nullptr;    // device: levels + 1 entries
 	uint32_t *rows = nullptr;         // device: one entry per row of op(A)
 	std::vector<uint32_t> h_level_ptr, h_level_max;
+	// spsamd_factor_ilu0 on the LOWER / NONUNIT schedule (k_factor.hip): each level's largest row work (lookups, saturated)
+	bool have_work = false;
+	std::vector<uint32_t> h_level_work;
 };
 
 struct Prepared {
@@ -554,6 +562,26 @@ int reduce_rows(spsamd_ctx *c, const spsamd_coo *A, char transpose, int op, int 
 // T * X = B for the `uplo` triangle of op(A): spsamd_solve_tri after the context check
 int solve_tri(spsamd_ctx *c, const spsamd_coo *A, char transpose, int uplo, int diag, const double *B, size_t ldb, double *X,
 	size_t ldx, size_t nrhs, int mem, int duplicate_policy, int zero_nan, spsamd_solve_stats *stats, spsamd_result *res);
+
+// One triangle of S as the analysis and the solve kernels read it
+struct TriView {
+	const uint32_t *ptr;                       // dense row pointer of S
+	const int32_t *col;
+	const double *val;
+	uint64_t n;                                // order of op(A)
+	int upper, unit;
+};
+// The schedule of the `uplo` / `diag` triangle of S into `s`: device arrays in workspace memory, or in the handle's own
+// when `hp` is given.  peel[0] / peel[1]: the k_peel_thin / k_peel_wide launches issued (those that find an empty frontier too).
+void analyse(spsamd_ctx *c, const TriView &t, Prepared *hp, SolveSchedule *s, uint64_t peel[2]);
+constexpr int SOLVE_NT = 1024;                 // threads of the one workgroup of a fused run (k_solve_fused, k_fac_fused) and of k_peel_thin
+constexpr uint32_t SOLVE_FUSE_ROWS = 256;      // default of the solve_fuse_rows knob: the flat end of the measured sweep
+
+// ---------------------------------------------------------------- ILU(0) factorisation (k_factor.hip)
+
+// F = ILU(0) of op(A) into the sink: spsamd_factor_ilu0 after its null checks
+void factor_ilu0(spsamd_ctx *c, const spsamd_coo *A, char transpose, int duplicate_policy, int zero_nan, int sink_kind,
+	int sink_flags, spsamd_factor_stats *stats, spsamd_result *res);
 
 // ---------------------------------------------------------------- element-wise product and pattern restriction (k_emult.hip)
 

@@ -33,20 +33,10 @@
 
 namespace spsamd {
 
-constexpr int SOLVE_NT = 1024;                 // threads of the one workgroup of k_solve_fused and k_peel_thin
-constexpr uint32_t SOLVE_FUSE_ROWS = 256;      // default of the solve_fuse_rows knob: the flat end of the measured sweep
 constexpr uint64_t SOLVE_FUSE_WORK = 2048;     // ... under which a thin level also has at most this many (row, rhs) pairs: two strides of the workgroup
 constexpr uint32_t PEEL_THIN_MAX = 2048;       // frontier rows up to which the peel stays inside one workgroup
 constexpr int PEEL_BATCH = 16;                 // wide frontiers: launches between two looks at the frontier size
 constexpr int SOLVE_FOLD_RHS = 16;             // right-hand sides per pass of k_solve_fold (LDS: 16 x 65 doubles)
-
-struct TriView {
-	const uint32_t *ptr;                       // dense row pointer of S
-	const int32_t *col;
-	const double *val;
-	uint64_t n;                                // order of op(A)
-	int upper, unit;
-};
 
 // 0: skipped (the other triangle; the diagonal under UNIT) | 1: off-diagonal, used | 2: diagonal, used
 __device__ __forceinline__ int tri_class(int32_t i, int32_t j, int upper, int unit)
@@ -323,9 +313,8 @@ static bool ranges_overlap(const void *p, uint64_t np, const void *q, uint64_t n
 	return p && q && np && nq && (const char *)p < (const char *)q + nq && (const char *)q < (const char *)p + np;
 }
 
-// The schedule of the `uplo` / `diag` triangle of S into `s`: device arrays in workspace memory, or in the handle's own
-// when `hp` is given.  peel[0] / peel[1]: the k_peel_thin / k_peel_wide launches issued (those that find an empty frontier too).
-static void analyse(spsamd_ctx *c, const TriView &t, Prepared *hp, SolveSchedule *s, uint64_t peel[2])
+// (declared in internal.h: spsamd_factor_ilu0 schedules by the LOWER triangle's levels as well)
+void analyse(spsamd_ctx *c, const TriView &t, Prepared *hp, SolveSchedule *s, uint64_t peel[2])
 {
 	hipStream_t st = c->stream;
 	const uint64_t N = t.n;
