@@ -712,6 +712,63 @@ int spsamd_factor_ilu0(spsamd_ctx *ctx, const spsamd_coo *A, char transpose,
 	spsamd_factor_stats *stats /* may be NULL */, spsamd_result *result);
 
 /*
+ * A greedy multi-colour ordering of op(A)'s graph by independent sets.  Rows of one colour share
+ * no tuple, so P*A*P^T for the permutation `perm` has at most `ncolors` levels in spsamd_solve_tri's and
+ * spsamd_factor_ilu0's schedules; the colour classes also serve multi-colour Gauss-Seidel and coarsening.
+ *   - Operand.  op(A) is structural, taken exactly as spsamd_multiply_masked takes M: val is never read and may be NULL,
+ *     duplicate keys count once, explicit zeros count; host, device, a chained SINK_COO result of this context (read in
+ *     place) and a prepared handle are accepted; sort0 only lets the call skip the sort, and a false one is rejected.
+ *     There is no duplicate_policy / zero_nan: a colouring of a superset of a pattern is proper for the pattern.  op(A)
+ *     must be square (SPSAMD_EDIM); n is its order, K its sorted unique key set.
+ *   - Graph.  N(i) = { j != i : (i, j) in K or (j, i) in K }; under SPSAMD_COLOR_SYMMETRIC the caller states that the
+ *     pattern is symmetric and N(i) = { j != i : (i, j) in K } -- row i alone, no symmetrisation pass.  deg(i) = |N(i)|.
+ *     Without the flag the graph of A^T is the graph of A: `transpose` changes nothing in the output.
+ *   - Order.  key(v) = (order == SPSAMD_COLOR_ORDER_DEGREE ? deg(v) : 0) << 32 | h(v), with 32-bit wrapping arithmetic in
+ *         h = v + seed * 0x9E3779B9;  h ^= h >> 16;  h *= 0x85EBCA6B;  h ^= h >> 13;  h *= 0xC2B2AE35;  h ^= h >> 16
+ *     u precedes v when key(u) > key(v).  Every step of h is invertible, so h is a bijection of the index and keys never tie.
+ *   - Every output is defined by this loop:
+ *         color[v] = -1 for all v
+ *         for v in descending key:   color[v] = the smallest c >= 0 that no u in N(v) with color[u] >= 0 holds
+ *         round(v) = 0 if no u in N(v) precedes v, else 1 + max round(u) over those u
+ *     An isolated vertex gets colour 0.  ncolors = 1 + the largest colour (0 for n = 0), rounds = 1 + the largest round
+ *     (0 for n = 0), adjacency = the sum of deg.  The device runs the loop as a Jones-Plassmann sweep, synchronous in
+ *     rounds -- vertex v is coloured in round(v) -- which returns exactly the loop's colours: all of these are functions
+ *     of K, order, seed and the flag only, never of timing or of a tuning knob.
+ *   - color (required) gets n colours.  perm (may be NULL) gets the n vertices ascending in (colour, index): the list to
+ *     hand to spsamd_extract as both rows and cols for P*A*P^T, new index r being old vertex perm[r].  color_ptr (may be
+ *     NULL) gets ncolors + 1 entries: color_ptr[c] is the first position of colour c in perm, color_ptr[ncolors] = n.
+ *     The buffers are the caller's; `mem` (SPSAMD_MEM_HOST or SPSAMD_MEM_DEVICE) holds for all three.  color_ptr with
+ *     ptr_capacity < ncolors + 1: nothing is written, *out_ncolors gets the count and the call returns SPSAMD_ECAPACITY;
+ *     a capacity of n + 1 always suffices.
+ *   - conflicts = the keys (i, j) of K with i != j and color[i] == color[j], counted after the sweep.  Always 0 without the
+ *     flag; with it, non-zero exactly where a false promise of symmetry mattered -- the call still succeeds.
+ * Workspace only, like spsamd_reduce: neither output set of the context is written, so a chained result stays valid and
+ * can be A.  SPSAMD_EINVAL, with a message and nothing written: A, color or out_ncolors NULL; an order, flag or mem
+ * outside the above; buffers that overlap each other or A's arrays; a device buffer inside an output set of the context;
+ * an index out of bounds; a false sort0; 2^31 or more tuples.  n == 0 returns 0 with *out_ncolors = 0.
+ * stats (may be NULL): see the struct.  result (may be NULL): shape, nnz_a (= |K|), ms_consolidate (the intake of K),
+ * ms_symbolic (the adjacency), ms_numeric (the sweep, perm and delivery), ms_total, workspace_bytes; everything else
+ * 0 / NULL.  Returns when the buffers are complete.
+ */
+#define SPSAMD_COLOR_ORDER_HASH    0   /* visit by hashed index */
+#define SPSAMD_COLOR_ORDER_DEGREE  1   /* largest degree first, hash among equal degrees */
+#define SPSAMD_COLOR_SYMMETRIC     1   /* color_flags: the caller states that the pattern is symmetric */
+
+typedef struct {
+	uint64_t ncolors, rounds;         /* of the colouring */
+	uint64_t adjacency, max_degree;   /* the sum and the largest of deg */
+	uint64_t conflicts;               /* see above */
+	uint64_t launches;                /* round-kernel launches of the sweep of this call (a fused run is one) */
+	uint64_t fused_rounds;            /* rounds served inside the fused run: the tail of the sweep, one workgroup */
+	uint64_t rows_thread, rows_wave;  /* vertices of degree >= 1 by the kernel class that coloured them */
+	float ms_adjacency, ms_color;
+} spsamd_color_stats;
+
+int spsamd_color(spsamd_ctx *ctx, const spsamd_coo *A, char transpose, int order, uint32_t seed, int color_flags,
+	int32_t *color, int32_t *perm, int32_t *color_ptr, size_t ptr_capacity, int mem,
+	size_t *out_ncolors, spsamd_color_stats *stats /* may be NULL */, spsamd_result *result /* may be NULL */);
+
+/*
  * ret = (C * diag(scalei) * op(A) * diag(scalej) * op(B) * diag(scalek)) restricted to the keys of M  -- a masked product
  * (SDDMM-style sampling of a sparse product: (L*L) o L counts triangles).  The result is exactly those tuples of
  *     spsparse::multiply(ret, C, scalei, A, transpose_A, scalej, B, transpose_B, scalek, duplicate_policy, zero_nan)

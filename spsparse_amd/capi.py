@@ -45,6 +45,10 @@ peel_thin_max, peel_batch = 2048, 16
 # factor_ilu0: the defaults of the factor_fuse_rows, factor_serial_work and factor_lds_row knobs, and the most the last
 # may ask for
 factor_fuse_rows, factor_serial_work, factor_lds_row, factor_lds_row_max = 256, 64, 256, 4096
+# color: the orders, the flag, and the defaults of the color_fuse_rows and color_wave_deg knobs
+COLOR_ORDER_HASH, COLOR_ORDER_DEGREE = 0, 1
+COLOR_SYMMETRIC = 1
+color_fuse_rows, color_wave_deg, color_fused_threads = 1024, 16, 1024
 
 ERRORS = {-1: "EDIM", -2: "EINVAL", -3: "EHIP", -4: "ENOMEM", -5: "ECAPACITY", -6: "ENODEVICE", -7: "EPEER"}
 
@@ -104,6 +108,12 @@ class FactorStats(C.Structure):
                 ("analysis_reused", C.c_uint32), ("ms_analysis", C.c_float), ("ms_factor", C.c_float)]
 
 
+class ColorStats(C.Structure):
+    _fields_ = [("ncolors", C.c_uint64), ("rounds", C.c_uint64), ("adjacency", C.c_uint64), ("max_degree", C.c_uint64),
+                ("conflicts", C.c_uint64), ("launches", C.c_uint64), ("fused_rounds", C.c_uint64),
+                ("rows_thread", C.c_uint64), ("rows_wave", C.c_uint64), ("ms_adjacency", C.c_float), ("ms_color", C.c_float)]
+
+
 class DistStats(C.Structure):
     _fields_ = [("block_nnz_a", C.c_uint64), ("panel_tuples", C.c_uint64), ("remote_tuples", C.c_uint64),
                 ("sent_tuples", C.c_uint64), ("ms_exchange", C.c_float), ("pad_", C.c_float)]
@@ -124,7 +134,7 @@ SYMBOLS = ["spsamd_ctx_create", "spsamd_ctx_destroy", "spsamd_last_error", "spsa
            "spsamd_operand_prepare", "spsamd_operand_as_coo", "spsamd_operand_bytes", "spsamd_operand_destroy",
            "spsamd_multiply_dense", "spsamd_add", "spsamd_multiply_stream", "spsamd_multiply_masked",
            "spsamd_multiply_sampled", "spsamd_select", "spsamd_extract", "spsamd_reduce", "spsamd_emult", "spsamd_solve_tri",
-           "spsamd_factor_ilu0"]
+           "spsamd_factor_ilu0", "spsamd_color"]
 
 _lib = None
 
@@ -184,6 +194,8 @@ def load():
     L.spsamd_solve_tri.argtypes = [C.c_void_p, P(Coo), C.c_char, C.c_int, C.c_int, C.c_void_p, C.c_size_t, C.c_void_p,
                                    C.c_size_t, C.c_size_t, C.c_int, C.c_int, C.c_int, P(SolveStats), P(Result)]
     L.spsamd_factor_ilu0.argtypes = [C.c_void_p, P(Coo), C.c_char, C.c_int, C.c_int, C.c_int, C.c_int, P(FactorStats), P(Result)]
+    L.spsamd_color.argtypes = [C.c_void_p, P(Coo), C.c_char, C.c_int, C.c_uint32, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p,
+                               C.c_size_t, C.c_int, P(C.c_size_t), P(ColorStats), P(Result)]
     L.spsamd_memcpy.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_size_t]
     L.spsamd_consolidate.argtypes = [C.c_void_p, P(Coo), C.c_int, C.c_int, C.c_int, P(Result)]
     L.spsamd_sorted_permutation.argtypes = [C.c_void_p, P(Coo), C.c_int, C.c_void_p]
@@ -523,6 +535,46 @@ class Context:
                                        C.byref(st), C.byref(res))
         self._check(rc)
         return (res, st) if stats else res
+
+    def color(self, A, order=COLOR_ORDER_HASH, seed=0, flags=0, transpose='.', out=None, stats=False, result=None):
+        """spsamd_color: the greedy multi-colour ordering of op(A)'s graph, exactly the serial loop of the header.  A: a Coo
+        struct whose op() is square (only its keys are read).  Without out: returns numpy int32 arrays (color, perm,
+        color_ptr) -- perm the vertices ascending in (colour, index), the list to hand to extract as rows and cols;
+        color_ptr the ncolors + 1 bounds of the colours in perm.  With out: contiguous 1-D int32 torch tensors on this
+        context's device, (color, perm, color_ptr) with perm and color_ptr possibly None, that receive the result; the
+        colour count is returned, and a color_ptr that is too small raises SpsamdError with code -5.  stats=True appends
+        a ColorStats to what is returned.  result: a capi.Result to fill (timings)."""
+        n = int(A.shape1 if transpose == 'T' else A.shape0)
+        cnt, st = C.c_size_t(0), ColorStats()
+        rp = None if result is None else C.byref(result)
+
+        def call(pc, pp, pq, cap, mem):
+            return self.L.spsamd_color(self.h, C.byref(A), transpose.encode(), int(order), int(seed) & 0xFFFFFFFF, int(flags),
+                                       pc, pp, pq, cap, mem, C.byref(cnt), C.byref(st), rp)
+
+        if out is not None:
+            oc, op, oq = out
+            ptrs, sizes = [], []
+            for t, name in ((oc, "out color"), (op, "out perm"), (oq, "out color_ptr")):
+                if t is None:
+                    if name == "out color":
+                        raise ValueError("out color is required")
+                    ptrs.append(None)
+                    sizes.append(0)
+                    continue
+                _p, nt, mt, _k = _index_list(t, name)
+                if mt != MEM_DEVICE and nt:
+                    raise ValueError("%s must be a device tensor" % name)
+                ptrs.append(t.data_ptr())
+                sizes.append(nt)
+            if sizes[0] < n or (op is not None and sizes[1] < n):
+                raise ValueError("out color and out perm need %d entries" % n)
+            self._check(call(ptrs[0], ptrs[1], ptrs[2], sizes[2], MEM_DEVICE))
+            return (int(cnt.value), st) if stats else int(cnt.value)
+        color, perm, ptr = np.empty(max(n, 1), np.int32), np.empty(max(n, 1), np.int32), np.empty(n + 1, np.int32)
+        self._check(call(color.ctypes.data, perm.ctypes.data, ptr.ctypes.data, n + 1, MEM_HOST))
+        got = (color[:n].copy(), perm[:n].copy(), ptr[:cnt.value + 1].copy())
+        return got + (st,) if stats else got
 
     def multiply_sampled(self, M, P, Q, out=None, transpose='.', alpha=1.0, beta=0.0):
         """spsamd_multiply_sampled: out[t] = alpha * (P[i] . Q[j]) (+ beta * v) for every tuple t = (i, j, v) of op(M) in

@@ -104,6 +104,10 @@ struct Tuning {
 	int factor_fuse_rows = 0;    // factor_ilu0: the widest level that still counts as thin (0: 256)
 	int factor_serial_work = 0;  // factor_ilu0: the most lookups of a serial-class row (0: 64)
 	int factor_lds_row = 0;      // factor_ilu0: the longest row of the wave kernel's LDS copy (0: 256; at most 4096)
+	int color_path = 0;          // color: 0 the thin tail of the sweep fuses | 1 every round in launches of its own | 2 every round fuses, whatever its width
+	int color_row = 0;           // color: 0 by degree | 1 thread | 2 wave kernel for every vertex
+	int color_fuse_rows = 0;     // color: the widest worklist that still counts as thin (0: 1024)
+	int color_wave_deg = 0;      // color: the largest degree of a thread-class vertex (0: 16)
 #ifdef SPSAMD_ABLATIONS
 	int dbg = 0;
 #endif
@@ -557,6 +561,11 @@ void extract_tuples(spsamd_ctx *c, const spsamd_coo *A, char transpose, const in
 int reduce_rows(spsamd_ctx *c, const spsamd_coo *A, char transpose, int op, int post, int duplicate_policy, int zero_nan,
 	int32_t *out_idx, double *out_val, size_t capacity, int mem, size_t *out_nnz, spsamd_result *res);
 
+// The checks of caller-owned output buffers (reduce, solve_tri, color; defined in k_reduce.hip): do two byte ranges overlap (a null or empty one never does);
+// does a device range touch an output set of the context?
+bool ranges_overlap(const void *p, uint64_t np, const void *q, uint64_t nq);
+bool in_output_sets(const spsamd_ctx *c, const void *p, uint64_t bytes);
+
 // ---------------------------------------------------------------- sparse triangular solve (k_solve.hip)
 
 // T * X = B for the `uplo` triangle of op(A): spsamd_solve_tri after the context check
@@ -582,6 +591,14 @@ constexpr uint32_t SOLVE_FUSE_ROWS = 256;      // default of the solve_fuse_rows
 // F = ILU(0) of op(A) into the sink: spsamd_factor_ilu0 after its null checks
 void factor_ilu0(spsamd_ctx *c, const spsamd_coo *A, char transpose, int duplicate_policy, int zero_nan, int sink_kind,
 	int sink_flags, spsamd_factor_stats *stats, spsamd_result *res);
+
+// ---------------------------------------------------------------- multi-colour ordering (k_color.hip)
+
+// the greedy colouring of op(A)'s graph into the caller's buffers: spsamd_color after its null checks.  Returns SPSAMD_OK,
+// or SPSAMD_ECAPACITY with *out_ncolors = the colours and the context's last error set (nothing written).
+int color_graph(spsamd_ctx *c, const spsamd_coo *A, char transpose, int order, uint32_t seed, int color_flags, int32_t *color,
+	int32_t *perm, int32_t *color_ptr, size_t ptr_capacity, int mem, size_t *out_ncolors, spsamd_color_stats *stats,
+	spsamd_result *res);
 
 // ---------------------------------------------------------------- element-wise product and pattern restriction (k_emult.hip)
 

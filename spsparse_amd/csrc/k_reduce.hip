@@ -326,12 +326,12 @@ static void run_long(spsamd_ctx *c, int op, const RedArgs &a, const uint32_t *li
 	}
 }
 
-static bool ranges_overlap(const void *p, uint64_t np, const void *q, uint64_t nq)
+bool ranges_overlap(const void *p, uint64_t np, const void *q, uint64_t nq)
 {
 	return p && q && np && nq && (const char *)p < (const char *)q + nq && (const char *)q < (const char *)p + np;
 }
 
-static bool in_output_sets(const spsamd_ctx *c, const void *p, uint64_t bytes)
+bool in_output_sets(const spsamd_ctx *c, const void *p, uint64_t bytes)
 {
 	if (!p || !bytes) return false;
 	for (const auto &s : c->out) if (s.holds(p) || s.holds((const char *)p + bytes - 1)) return true;

@@ -308,11 +308,6 @@ __global__ void __launch_bounds__(64) k_solve_fold(SolveArgs a, uint32_t lo)
 
 // ---------------------------------------------------------------- host
 
-static bool ranges_overlap(const void *p, uint64_t np, const void *q, uint64_t nq)
-{
-	return p && q && np && nq && (const char *)p < (const char *)q + nq && (const char *)q < (const char *)p + np;
-}
-
 // (declared in internal.h: spsamd_factor_ilu0 schedules by the LOWER triangle's levels as well)
 void analyse(spsamd_ctx *c, const TriView &t, Prepared *hp, SolveSchedule *s, uint64_t peel[2])
 {
