@@ -243,6 +243,10 @@ const char *spsamd_version(void);
  *   factor_fuse_rows > 0              factor_ilu0: the widest level that still counts as thin (256 rows)
  *   factor_serial_work > 0            factor_ilu0: rows of at most this many lookups are serial-class (64)
  *   factor_lds_row  1..4096           factor_ilu0: the longest row (tuples) of the wave kernel's LDS copy (256)
+ *   pcg_check_every > 0               solve_pcg: iterations enqueued between two reads of the device state (8, DESIGN.md
+ *                                     section 23)
+ *   pcg_fuse        1                 solve_pcg: every vector operation and every dot product in a launch of its own
+ *                                     (default: a dot's first level rides in the kernel that produces its vector)
  * The environment variables of the same purpose (SPSAMD_W ...) are read once, inside spsamd_ctx_create; nothing reads
  * the environment later.  Unknown names: SPSAMD_EINVAL. */
 int spsamd_ctx_set_tuning(spsamd_ctx *ctx, const char *name, long value);
@@ -767,6 +771,87 @@ typedef struct {
 int spsamd_color(spsamd_ctx *ctx, const spsamd_coo *A, char transpose, int order, uint32_t seed, int color_flags,
 	int32_t *color, int32_t *perm, int32_t *color_ptr, size_t ptr_capacity, int mem,
 	size_t *out_ncolors, spsamd_color_stats *stats /* may be NULL */, spsamd_result *result /* may be NULL */);
+
+/*
+ * Solve op(A) x = b by preconditioned conjugate gradients, one right-hand side, the whole loop on the device (DESIGN.md
+ * section 23).  It is what the preconditioner stack is for: spsamd_factor_ilu0's result (after spsamd_color + spsamd_extract
+ * or not) is M, spsamd_solve_tri's level schedules are built at most once per call, the scalars never visit the host.
+ *   - Operands.  op(A) and op(M) are taken exactly as spsamd_solve_tri takes its operand, duplicate_policy and zero_nan
+ *     included: a raw operand is consolidated by op()'s rows; an operand whose sort0 names op()'s row order is trusted as
+ *     stored; a SINK_COO result of this context and a prepared handle of the same transpose are read in place.  Call the
+ *     resulting sequences S (of A) and F (of M).  Both must be square and of one order n (SPSAMD_EDIM).  M is given under
+ *     SPSAMD_PRECOND_LU and only then.
+ *   - b and x are n doubles in `mem` (SPSAMD_MEM_HOST or SPSAMD_MEM_DEVICE, for both).  x holds x0 on entry and the iterate
+ *     at the stop on return.  x may not overlap b, A's or M's arrays, nor lie in an output set of the context (SPSAMD_EINVAL).
+ *     Neither output set is written: A is usually a chained result and M the spsamd_factor_ilu0 result in the other set.
+ *   - Every value returned -- x, hist, iterations, reason, bb, rr0, rr -- is defined by the loop below, bit for bit.
+ *     Products and sums are rounded separately (no FMA), divisions are true IEEE divisions, and a NaN result carries the
+ *     bits x86-64 gives it (the left operand's NaN quieted, else the right one's, else 0xFFF8000000000000).
+ *       dot(u, w):  t[e] = u[e] * w[e] for e < n;  return fold(t, n)            (the fold of nothing is +0.0)
+ *       fold(t, m): for each chunk g of 1024 consecutive elements (the last may be short):
+ *                      for lane l = 0 .. 63:  a_l = +0.0;  for k = 0 .. 15:  e = 1024 g + 64 k + l;  if e < m:  a_l = a_l + t[e]
+ *                      for s = 32, 16, 8, 4, 2, 1:  for l < s:  a_l = a_l + a_{l+s}       (a_l is the left operand)
+ *                      t'[g] = a_0
+ *                   with c = ceil(m / 1024) chunks:  c == 1 ? t'[0] : fold(t', c)
+ *       q = A p:    q_i = acc after  acc = +0.0;  acc = acc + v * p_j  over row i's tuples (i, j, v) of S in S's order
+ *                   (spsamd_multiply_dense with ADD into +0.0, handle_nan off)
+ *       z = M^-1 r: NONE  z = r  |  JACOBI  z_i = r_i / d_i, d the DIAG fold of spsamd_reduce over S (+0.0 without a
+ *                   diagonal tuple)  |  LU  the loops of spsamd_solve_tri on F: LOWER | UNIT on r, then UPPER | NONUNIT
+ *       usable(v):  v is finite and not +-0.0
+ *
+ *       bb = dot(b, b);  thresh = (tol * tol) * bb
+ *       q = A x;  r_i = b_i - q_i;  rr = dot(r, r);  k = 0;  hist[0] = rr;  rr0 = rr
+ *       loop:
+ *           if rr <= thresh:   stop CONVERGED          (a NaN compares false)
+ *           if k == max_iter:  stop MAXITER
+ *           z = M^-1 r;  rz' = dot(r, z)
+ *           if k == 0:  p = z          else:  beta = rz' / rz;  p_i = z_i + beta * p_i
+ *           rz = rz'
+ *           if not usable(rz):  stop BREAKDOWN
+ *           q = A p;  pq = dot(p, q)
+ *           if not usable(pq):  stop BREAKDOWN
+ *           alpha = rz / pq
+ *           x_i = x_i + alpha * p_i;   r_i = r_i - alpha * q_i
+ *           rr = dot(r, r);  k = k + 1;  hist[k] = rr
+ *     At a stop x is the iterate after k iterations.  hist_host (host memory, may be NULL) gets hist[k] for
+ *     k <= min(iterations, hist_capacity - 1).  The stop is relative: sqrt(rr) <= tol * sqrt(bb), on the recursive residual.
+ *   - The host enqueues pcg_check_every iterations (knob, default 8), then reads the device state once.  Every kernel that
+ *     writes x, r, p, k, hist or a scalar reads the state first and does nothing after the stop, so the knob changes
+ *     launches and readbacks, never a returned bit; so does pcg_fuse (0: the dots' first level is fused into the kernels
+ *     that produce the vectors | 1: every vector operation and every dot a launch of its own).
+ * stats (may be NULL): see the struct.  result (may be NULL): shape0 = shape1 = n, nnz_a = |S|, nnz_b = |F|, ms_consolidate
+ * (the intake of A and M), ms_symbolic (row forms, diagonal, schedules, bb and the first residual), ms_numeric (the
+ * iterations), ms_total, workspace_bytes; everything else 0 / NULL.
+ * SPSAMD_EINVAL, with a message and x untouched: A NULL; b or x NULL while n > 0; tol negative, NaN or Inf; M non-NULL
+ * without PRECOND_LU or NULL with it; precond, mem or a policy out of range; the overlaps above; an index out of bounds; a
+ * false sort0; 2^31 or more tuples.  n == 0 returns 0 with iterations = 0, reason = CONVERGED and hist[0] = +0.0.  Returns
+ * when x is complete.
+ */
+#define SPSAMD_PRECOND_NONE   0   /* z = r */
+#define SPSAMD_PRECOND_JACOBI 1   /* z_i = r_i / d_i, d the DIAG fold of spsamd_reduce over S (a true division) */
+#define SPSAMD_PRECOND_LU     2   /* z = solve_tri(F, UPPER, NONUNIT, solve_tri(F, LOWER, UNIT, r)); F = the operand M */
+
+#define SPSAMD_PCG_CONVERGED  0
+#define SPSAMD_PCG_MAXITER    1
+#define SPSAMD_PCG_BREAKDOWN  2
+
+typedef struct {
+	uint64_t iterations;       /* k at the stop */
+	int32_t  reason;           /* SPSAMD_PCG_* */
+	double   bb, rr0, rr;      /* dot(b,b), dot(r,r) before the first and after the last iteration */
+	uint64_t launches;         /* kernel launches (and fills) of the iteration phase, those enqueued after the stop included */
+	uint64_t readbacks;        /* host reads of the device state during the iteration phase */
+	uint32_t analyses;         /* level schedules built by this call (0 .. 2) */
+	float ms_setup, ms_iterate;
+} spsamd_pcg_stats;
+
+int spsamd_solve_pcg(spsamd_ctx *ctx, const spsamd_coo *A, char transpose,
+	int precond, const spsamd_coo *M /* PRECOND_LU only, else NULL */, char transpose_M,
+	const double *b, double *x /* in: x0, out: the iterate at the stop */, int mem,
+	double tol, uint64_t max_iter,
+	double *hist_host /* may be NULL */, size_t hist_capacity,
+	int duplicate_policy, int zero_nan,
+	spsamd_pcg_stats *stats /* may be NULL */, spsamd_result *result /* may be NULL */);
 
 /*
  * ret = (C * diag(scalei) * op(A) * diag(scalej) * op(B) * diag(scalek)) restricted to the keys of M  -- a masked product

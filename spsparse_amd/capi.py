@@ -49,6 +49,11 @@ factor_fuse_rows, factor_serial_work, factor_lds_row, factor_lds_row_max = 256, 
 COLOR_ORDER_HASH, COLOR_ORDER_DEGREE = 0, 1
 COLOR_SYMMETRIC = 1
 color_fuse_rows, color_wave_deg, color_fused_threads = 1024, 16, 1024
+# solve_pcg: the preconditioners, the stop reasons, the default of the pcg_check_every knob and the elements of one chunk of
+# the dot products' fold
+PRECOND_NONE, PRECOND_JACOBI, PRECOND_LU = 0, 1, 2
+PCG_CONVERGED, PCG_MAXITER, PCG_BREAKDOWN = 0, 1, 2
+pcg_check_every, pcg_chunk = 8, 1024
 
 ERRORS = {-1: "EDIM", -2: "EINVAL", -3: "EHIP", -4: "ENOMEM", -5: "ECAPACITY", -6: "ENODEVICE", -7: "EPEER"}
 
@@ -114,6 +119,12 @@ class ColorStats(C.Structure):
                 ("rows_thread", C.c_uint64), ("rows_wave", C.c_uint64), ("ms_adjacency", C.c_float), ("ms_color", C.c_float)]
 
 
+class PcgStats(C.Structure):
+    _fields_ = [("iterations", C.c_uint64), ("reason", C.c_int32), ("bb", C.c_double), ("rr0", C.c_double), ("rr", C.c_double),
+                ("launches", C.c_uint64), ("readbacks", C.c_uint64), ("analyses", C.c_uint32),
+                ("ms_setup", C.c_float), ("ms_iterate", C.c_float)]
+
+
 class DistStats(C.Structure):
     _fields_ = [("block_nnz_a", C.c_uint64), ("panel_tuples", C.c_uint64), ("remote_tuples", C.c_uint64),
                 ("sent_tuples", C.c_uint64), ("ms_exchange", C.c_float), ("pad_", C.c_float)]
@@ -134,7 +145,7 @@ SYMBOLS = ["spsamd_ctx_create", "spsamd_ctx_destroy", "spsamd_last_error", "spsa
            "spsamd_operand_prepare", "spsamd_operand_as_coo", "spsamd_operand_bytes", "spsamd_operand_destroy",
            "spsamd_multiply_dense", "spsamd_add", "spsamd_multiply_stream", "spsamd_multiply_masked",
            "spsamd_multiply_sampled", "spsamd_select", "spsamd_extract", "spsamd_reduce", "spsamd_emult", "spsamd_solve_tri",
-           "spsamd_factor_ilu0", "spsamd_color"]
+           "spsamd_factor_ilu0", "spsamd_color", "spsamd_solve_pcg"]
 
 _lib = None
 
@@ -196,6 +207,8 @@ def load():
     L.spsamd_factor_ilu0.argtypes = [C.c_void_p, P(Coo), C.c_char, C.c_int, C.c_int, C.c_int, C.c_int, P(FactorStats), P(Result)]
     L.spsamd_color.argtypes = [C.c_void_p, P(Coo), C.c_char, C.c_int, C.c_uint32, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p,
                                C.c_size_t, C.c_int, P(C.c_size_t), P(ColorStats), P(Result)]
+    L.spsamd_solve_pcg.argtypes = [C.c_void_p, P(Coo), C.c_char, C.c_int, P(Coo), C.c_char, C.c_void_p, C.c_void_p, C.c_int,
+                                   C.c_double, C.c_uint64, C.c_void_p, C.c_size_t, C.c_int, C.c_int, P(PcgStats), P(Result)]
     L.spsamd_memcpy.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_size_t]
     L.spsamd_consolidate.argtypes = [C.c_void_p, P(Coo), C.c_int, C.c_int, C.c_int, P(Result)]
     L.spsamd_sorted_permutation.argtypes = [C.c_void_p, P(Coo), C.c_int, C.c_void_p]
@@ -575,6 +588,38 @@ class Context:
         self._check(call(color.ctypes.data, perm.ctypes.data, ptr.ctypes.data, n + 1, MEM_HOST))
         got = (color[:n].copy(), perm[:n].copy(), ptr[:cnt.value + 1].copy())
         return got + (st,) if stats else got
+
+    def solve_pcg(self, A, b, x=None, precond=PRECOND_NONE, M=None, transpose='.', transpose_M='.', tol=1e-8, max_iter=1000,
+                  hist_capacity=None, duplicate_policy=ADD, zero_nan=False, result=None):
+        """spsamd_solve_pcg: op(A) x = b by preconditioned conjugate gradients, bit for bit the loop of the header.  A, M:
+        Coo structs (M with PRECOND_LU and only then: the spsamd_factor_ilu0 result, chained or prepared).  b, x: 1-D
+        contiguous float64 numpy arrays (host) or float64 torch tensors on this context's device, n values each; x holds
+        x0 and receives the iterate at the stop (x=None: a zero start, allocated here).  hist_capacity: the entries of the
+        history to bring back (None: max_iter + 1; 0: none).  Returns (x, hist, PcgStats): hist a float64 numpy array of
+        min(iterations + 1, hist_capacity) values of dot(r, r).  result: a capi.Result to fill (timings)."""
+        pb, _ldb, nb, mb = _dense_arg(b, "b", writable=False)
+        if x is None:
+            if mb == MEM_HOST:
+                x = np.zeros(b.shape, dtype=np.float64)
+            else:
+                import torch
+                x = torch.zeros(tuple(b.shape), dtype=torch.float64, device=b.device)
+        px, _ldx, nx, mx = _dense_arg(x, "x", writable=True)
+        if mx != mb:
+            raise ValueError("b and x must both be host (numpy) or both device (torch) arrays")
+        n = int(A.shape1 if transpose == 'T' else A.shape0)
+        if b.ndim != 1 or x.ndim != 1 or nb != 1 or nx != 1 or _rows(b) != n or _rows(x) != n:
+            raise ValueError("b and x must be 1-D arrays of %d values" % n)
+        if n > 1 and (_ldb != 1 or _ldx != 1):
+            raise ValueError("b and x must be contiguous")
+        cap = int(max_iter) + 1 if hist_capacity is None else int(hist_capacity)
+        hist = np.empty(max(cap, 1), np.float64)
+        st = PcgStats()
+        self._check(self.L.spsamd_solve_pcg(self.h, C.byref(A), transpose.encode(), int(precond),
+                                            None if M is None else C.byref(M), transpose_M.encode(), pb, px, mb, float(tol),
+                                            int(max_iter), hist.ctypes.data if cap else None, cap, duplicate_policy,
+                                            int(zero_nan), C.byref(st), None if result is None else C.byref(result)))
+        return x, hist[:min(int(st.iterations) + 1, cap)].copy(), st
 
     def multiply_sampled(self, M, P, Q, out=None, transpose='.', alpha=1.0, beta=0.0):
         """spsamd_multiply_sampled: out[t] = alpha * (P[i] . Q[j]) (+ beta * v) for every tuple t = (i, j, v) of op(M) in

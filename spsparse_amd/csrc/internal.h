@@ -108,6 +108,8 @@ struct Tuning {
 	int color_row = 0;           // color: 0 by degree | 1 thread | 2 wave kernel for every vertex
 	int color_fuse_rows = 0;     // color: the widest worklist that still counts as thin (0: 1024)
 	int color_wave_deg = 0;      // color: the largest degree of a thread-class vertex (0: 16)
+	int pcg_check_every = 0;     // solve_pcg: iterations enqueued between two reads of the device state (0: 8)
+	int pcg_fuse = 0;            // solve_pcg: 0 dots fused into the kernels that produce their vectors | 1 every vector operation and every dot a launch of its own
 #ifdef SPSAMD_ABLATIONS
 	int dbg = 0;
 #endif
@@ -506,6 +508,15 @@ void dense_operand(spsamd_ctx *c, const spsamd_coo *M, int lead, DenseOperand *o
 // Y[i * ldy + r] (op)= op(M)(i, j) * X[j * ldx + r] in storage order, X and Y device memory
 void spmm_dense(spsamd_ctx *c, const DenseOperand &m, const double *X, uint64_t ldx, double *Y, uint64_t ldy, uint32_t nrhs,
 	int policy, bool handle_nan);
+// out[t] = (minor[t], val[t]) packed, for a caller that has op(M)'s tuples in row order already
+void pack_tuples(spsamd_ctx *c, const int32_t *minor, const double *val, uint32_t n, BTup *out);
+// The long rows' half of spmm_dense for a caller that applies one operand many times (spsamd_solve_pcg): the rows of more
+// than long_min tuples listed once (workspace memory; returns how many) ...
+uint32_t spmm_long_list(spsamd_ctx *c, const uint32_t *rowptr, uint64_t nrow, uint32_t long_min, uint32_t **list, uint32_t **count);
+// ... and Y[i] += op(M)(i, j) * X[j] in storage order for the listed rows alone (ADD, handle_nan off): one launch of the wave
+// kernel spmm_dense would choose, nothing allocated
+void spmm_long_rows(spsamd_ctx *c, const DenseOperand &m, const uint32_t *list, const uint32_t *count, const double *X, uint64_t ldx,
+	double *Y, uint64_t ldy, uint32_t nrhs);
 
 // ---------------------------------------------------------------- sparse addition (k_add.hip)
 
@@ -565,6 +576,9 @@ int reduce_rows(spsamd_ctx *c, const spsamd_coo *A, char transpose, int op, int 
 // does a device range touch an output set of the context?
 bool ranges_overlap(const void *p, uint64_t np, const void *q, uint64_t nq);
 bool in_output_sets(const spsamd_ctx *c, const void *p, uint64_t bytes);
+// The DIAG fold (post NONE, dense form) of an operand already taken: ptr / col / val are S's dense row pointer and tuples,
+// d gets nrow values in device memory, +0.0 where a row stores no diagonal.  Workspace of the current call; nrow > 0.
+void reduce_diag_dense(spsamd_ctx *c, const uint32_t *ptr, const int32_t *col, const double *val, uint64_t nrow, double *d);
 
 // ---------------------------------------------------------------- sparse triangular solve (k_solve.hip)
 
@@ -583,8 +597,20 @@ struct TriView {
 // The schedule of the `uplo` / `diag` triangle of S into `s`: device arrays in workspace memory, or in the handle's own
 // when `hp` is given.  peel[0] / peel[1]: the k_peel_thin / k_peel_wide launches issued (those that find an empty frontier too).
 void analyse(spsamd_ctx *c, const TriView &t, Prepared *hp, SolveSchedule *s, uint64_t peel[2]);
+// The numeric phase alone, on a schedule of t's triangle: T * X = B over device arrays (X may be B).  Returns the launches
+// issued; *fused_levels (may be null) the levels served inside fused runs.
+uint64_t solve_levels(spsamd_ctx *c, const TriView &t, const SolveSchedule &s, const double *B, uint64_t ldb, double *X,
+	uint64_t ldx, uint32_t nrhs, uint64_t *fused_levels);
 constexpr int SOLVE_NT = 1024;                 // threads of the one workgroup of a fused run (k_solve_fused, k_fac_fused) and of k_peel_thin
 constexpr uint32_t SOLVE_FUSE_ROWS = 256;      // default of the solve_fuse_rows knob: the flat end of the measured sweep
+
+// ---------------------------------------------------------------- preconditioned conjugate gradients (k_krylov.hip)
+
+// A x = b by the loop of the header: spsamd_solve_pcg after the context check
+int solve_pcg(spsamd_ctx *c, const spsamd_coo *A, char transpose, int precond, const spsamd_coo *M, char transpose_M,
+	const double *b, double *x, int mem, double tol, uint64_t max_iter, double *hist_host, size_t hist_capacity,
+	int duplicate_policy, int zero_nan, spsamd_pcg_stats *stats, spsamd_result *res);
+constexpr int PCG_CHECK_EVERY = 8;             // default of the pcg_check_every knob: the measured sweep is flat from 4 on, and 8 bounds the work after the stop
 
 // ---------------------------------------------------------------- ILU(0) factorisation (k_factor.hip)
 

@@ -1,0 +1,512 @@
+// k_krylov.hip -- A x = b by preconditioned conjugate gradients, the whole loop on the device (spsamd_solve_pcg,
+// include/spsparse_amd.h).
+//
+// S = op(A) and F = op(M) as consolidate_operand() hands them over (row-major; consolidated, or trusted as stored).  Every
+// returned bit is defined by the loop of the header: products and sums rounded one by one (x86fp.h), the operator and the
+// preconditioner as serial chains in S's / F's order, and every dot product in ONE reduction shape, whatever the launch
+// geometry:
+//     level 0   chunk g = elements [1024 g, 1024 g + 1024): lane l adds t[1024 g + 64 k + l], k = 0 .. 15, to +0.0 in that
+//               order; then a butterfly over the lanes (s = 32 .. 1: a_l = a_l + a_{l+s}); the partial is a_0
+//     level 1+  the same over the partials, until one value is left
+// A wave owns a chunk, so level 0 needs no LDS and no barrier: 16 coalesced loads per lane and six shuffles.  The kernels
+// that produce a vector in chunk order (the Jacobi division, the serial SpMV, the x / r update, the residual) produce the
+// level-0 partials of the dot that follows in the same pass; behind the level-scheduled solves of k_solve.hip k_pcg_dot runs
+// alone.  Rows above spmm_long_min are left to k_spmm.hip's wave kernel (their list is made once per call); the fused SpMV
+// still covers every short row, and k_pcg_dot_rows then redoes the partials of the few chunks that hold a long row.
+// Levels 1 and up, the scalar that depends on the dot and the stop tests are one workgroup, k_pcg_finish.
+//
+// The scalars, k, the history and the state word live in device memory (PcgState).  The host enqueues pcg_check_every
+// iterations and reads the state once; every kernel of this file that writes x, r, p, k, the history or a scalar reads the
+// state first and does nothing unless it is RUNNING.  q and z are scratch of the loop and may be overwritten after the stop
+// (k_spmm.hip and k_solve.hip know nothing of the state); nothing returned depends on them.  No kernel reads what another
+// workgroup wrote in the same launch: every dependency between workgroups is a kernel boundary.
+#include "internal.h"
+#include "devutil.h"
+#include "x86fp.h"
+
+#include <algorithm>
+#include <cstring>
+
+namespace spsamd {
+
+constexpr int PCG_CHUNK = 1024;                // elements of a level-0 chunk: 16 per lane of one wave
+constexpr int PCG_NT = 256;                    // four waves, a chunk each
+constexpr int PCG_FINISH_NT = 1024;            // the one workgroup of k_pcg_finish
+constexpr int32_t PCG_RUNNING = -1;            // PcgState::state; from 0 on: SPSAMD_PCG_*
+
+struct PcgState {
+	double bb, thresh, rr0, rr, rz, pq, alpha, beta;
+	unsigned long long k, max_iter, hist_cap;
+	int32_t state, pad;
+};
+
+__device__ __forceinline__ bool pcg_usable(double v) { return v == v && mag_of(v) != 0x7FF0000000000000ull && v != 0.0; }
+
+// The partial of chunk g of t[0 .. n), t[e] = term(e) (called once per element of the chunk, by the lane that owns it):
+// valid in lane 0.  Every lane of the wave calls it.
+template <class Term>
+__device__ __forceinline__ double chunk_partial(uint64_t g, uint64_t n, Term term)
+{
+	const uint64_t base = g * PCG_CHUNK + lane_id();
+	double t[PCG_CHUNK / 64];
+#pragma unroll
+	for (int k = 0; k < PCG_CHUNK / 64; ++k) {
+		const uint64_t e = base + (uint64_t)k * 64;
+		t[k] = e < n ? term(e) : 0.0;
+	}
+	double a = 0.0;
+#pragma unroll
+	for (int k = 0; k < PCG_CHUNK / 64; ++k)
+		if (base + (uint64_t)k * 64 < n) a = ref_add(a, t[k]);
+#pragma unroll
+	for (int s = 32; s >= 1; s >>= 1) {
+		const double o = __shfl_down(a, s, 64);
+		if (lane_id() < (unsigned)s) a = ref_add(a, o);              // a_l is the left operand
+	}
+	return a;
+}
+
+// the chunk of this wave, or false past the last one
+__device__ __forceinline__ bool my_chunk(uint64_t n, uint64_t *g)
+{
+	*g = (uint64_t)blockIdx.x * (PCG_NT / 64) + wave_id();
+	return *g * PCG_CHUNK < n;
+}
+
+__device__ __forceinline__ bool stopped(const PcgState *st) { return st && st->state != PCG_RUNNING; }
+
+// ---------------------------------------------------------------- level 0: the vector kernels
+
+__global__ void __launch_bounds__(PCG_NT) k_pcg_dot(const double *u, const double *w, uint64_t n, double *__restrict__ part, const PcgState *st)
+{
+	uint64_t g;
+	if (stopped(st) || !my_chunk(n, &g)) return;
+	const double a = chunk_partial(g, n, [&](uint64_t e) { return ref_mul(u[e], w[e]); });
+	if (lane_id() == 0) part[g] = a;
+}
+
+// r = b - q (the set-up's residual)
+template <bool DOT>
+__global__ void __launch_bounds__(PCG_NT) k_pcg_residual(const double *__restrict__ b, const double *__restrict__ q, double *__restrict__ r,
+	uint64_t n, double *__restrict__ part)
+{
+	uint64_t g;
+	if (!my_chunk(n, &g)) return;
+	const double a = chunk_partial(g, n, [&](uint64_t e) { const double v = ref_sub(b[e], q[e]); r[e] = v; return DOT ? ref_mul(v, v) : 0.0; });
+	if (DOT && lane_id() == 0) part[g] = a;
+}
+
+// z = r / d, and the partials of dot(r, z)
+template <bool DOT>
+__global__ void __launch_bounds__(PCG_NT) k_pcg_jacobi(const double *__restrict__ r, const double *__restrict__ d, double *__restrict__ z,
+	uint64_t n, double *__restrict__ part, const PcgState *st)
+{
+	uint64_t g;
+	if (stopped(st) || !my_chunk(n, &g)) return;
+	const double a = chunk_partial(g, n, [&](uint64_t e) { const double re = r[e], v = ref_div(re, d[e]); z[e] = v; return DOT ? ref_mul(re, v) : 0.0; });
+	if (DOT && lane_id() == 0) part[g] = a;
+}
+
+// q_i = the serial chain of row i over S, and the partials of dot(in, q).  A row of more than long_min tuples gets +0.0: the
+// wave kernel of k_spmm.hip adds its chain in the next launch, and the partial of its chunk is redone after that
+// (k_pcg_dot_rows).  A lane walks the 16 rows 64 apart that the fold gives it.
+template <bool DOT>
+__global__ void __launch_bounds__(PCG_NT) k_pcg_spmv(const uint32_t *__restrict__ ptr, const int32_t *__restrict__ col, const double *__restrict__ val,
+	const double *__restrict__ in, double *__restrict__ q, uint64_t n, uint32_t long_min, double *__restrict__ part, const PcgState *st)
+{
+	uint64_t g;
+	if (stopped(st) || !my_chunk(n, &g)) return;
+	const double a = chunk_partial(g, n, [&](uint64_t i) {
+		double acc = 0.0;
+		const uint32_t b = ptr[i], e = ptr[i + 1];
+		if (e - b <= long_min)
+			for (uint32_t k = b; k < e; ++k) acc = ref_add(acc, ref_mul(val[k], in[(uint32_t)col[k]]));
+		q[i] = acc;
+		return DOT ? ref_mul(in[i], acc) : 0.0;
+	});
+	if (DOT && lane_id() == 0) part[g] = a;
+}
+
+// The partials of dot(u, w) for the chunks that hold a listed row, a wave per listed row (two rows of one chunk store the
+// same value twice)
+__global__ void __launch_bounds__(64) k_pcg_dot_rows(const double *u, const double *w, uint64_t n, const uint32_t *__restrict__ list,
+	const uint32_t *__restrict__ count, double *part, const PcgState *st)
+{
+	if (stopped(st)) return;
+	const uint32_t m = *count;
+	for (uint32_t r = blockIdx.x; r < m; r += gridDim.x) {               // uniform
+		const uint64_t g = list[r] / PCG_CHUNK;
+		const double a = chunk_partial(g, n, [&](uint64_t e) { return ref_mul(u[e], w[e]); });
+		if (lane_id() == 0) part[g] = a;
+	}
+}
+
+// p = z (k == 0), else p = z + beta p.  No fold here, so nothing fixes which lane owns which element: VEC takes two
+// neighbouring elements per thread in 16-byte loads and stores (z and p 16-byte aligned), the odd last element alone.
+template <bool VEC>
+__global__ void __launch_bounds__(256) k_pcg_direction(const double *__restrict__ z, double *__restrict__ p, uint64_t n, const PcgState *st)
+{
+	if (stopped(st)) return;
+	const uint64_t t = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x;
+	const bool first = st->k == 0;
+	const double beta = st->beta;
+	if (VEC) {
+		const uint64_t e = 2 * t;
+		if (e + 1 < n) {
+			const double2 zz = *reinterpret_cast<const double2 *>(z + e);
+			double2 pp = zz;
+			if (!first) {
+				pp = *reinterpret_cast<const double2 *>(p + e);
+				pp.x = ref_add(zz.x, ref_mul(beta, pp.x));
+				pp.y = ref_add(zz.y, ref_mul(beta, pp.y));
+			}
+			*reinterpret_cast<double2 *>(p + e) = pp;
+		} else if (e < n) p[e] = first ? z[e] : ref_add(z[e], ref_mul(beta, p[e]));
+	} else if (t < n) p[t] = first ? z[t] : ref_add(z[t], ref_mul(beta, p[t]));
+}
+
+// WHAT 0: x += alpha p, r -= alpha q and the partials of dot(r, r) | 1: x += alpha p alone | 2: r -= alpha q alone
+template <int WHAT>
+__global__ void __launch_bounds__(PCG_NT) k_pcg_update(double *__restrict__ x, const double *__restrict__ p, double *__restrict__ r,
+	const double *__restrict__ q, uint64_t n, double *__restrict__ part, const PcgState *st)
+{
+	uint64_t g;
+	if (stopped(st) || !my_chunk(n, &g)) return;
+	const double alpha = st->alpha;
+	const double a = chunk_partial(g, n, [&](uint64_t e) {
+		if (WHAT != 2) x[e] = ref_add(x[e], ref_mul(alpha, p[e]));
+		if (WHAT == 1) return 0.0;
+		const double v = ref_sub(r[e], ref_mul(alpha, q[e]));
+		r[e] = v;
+		return WHAT == 0 ? ref_mul(v, v) : 0.0;
+	});
+	if (WHAT == 0 && lane_id() == 0) part[g] = a;
+}
+
+__global__ void k_pcg_init(PcgState *st, unsigned long long max_iter, unsigned long long hist_cap)
+{
+	PcgState s = {};
+	s.max_iter = max_iter; s.hist_cap = hist_cap; s.state = PCG_RUNNING;
+	*st = s;
+}
+
+// ---------------------------------------------------------------- levels 1 and up, the scalars, the stop tests
+
+enum { FIN_BB = 0, FIN_RR0 = 1, FIN_RZ = 2, FIN_PQ = 3, FIN_RR = 4 };
+
+// fold(part, c0) for c0 >= 2 by the whole workgroup: a wave per chunk, a barrier between two levels; b0 / b1 take the
+// levels' partials in turn (ceil(c0 / 1024) entries each).  The value comes back in every thread.
+__device__ double block_fold(const double *part, uint64_t m, double *b0, double *b1, double *s_out)
+{
+	const double *src = part;
+	double *dst = b0;
+	for (;;) {                                                       // uniform
+		const uint64_t c = (m + PCG_CHUNK - 1) / PCG_CHUNK;
+		for (uint64_t g = wave_id(); g < c; g += PCG_FINISH_NT / 64) {
+			const double a = chunk_partial(g, m, [&](uint64_t e) { return src[e]; });
+			if (lane_id() == 0) { if (c == 1) *s_out = a; else dst[g] = a; }
+		}
+		__syncthreads();                                             // this level's partials are complete, and visible to the workgroup
+		if (c == 1) break;
+		src = dst; dst = dst == b0 ? b1 : b0; m = c;
+	}
+	return *s_out;
+}
+
+// part == nullptr (FIN_RZ under PRECOND_NONE): z is r, and dot(r, z) has the bits of rr
+template <int KIND>
+__global__ void __launch_bounds__(PCG_FINISH_NT) k_pcg_finish(const double *part, uint64_t c0, double *b0, double *b1, PcgState *st,
+	double *__restrict__ hist, double tol2)
+{
+	__shared__ double s_out;
+	const bool idle = KIND >= FIN_RZ && st->state != PCG_RUNNING;
+	__syncthreads();                                                 // every thread has read the state before thread 0 may set it
+	if (idle) return;                                                // uniform
+	double v = 0.0;
+	if (part) v = c0 == 0 ? 0.0 : c0 == 1 ? part[0] : block_fold(part, c0, b0, b1, &s_out);
+	if (threadIdx.x != 0) return;
+	if (KIND == FIN_BB) { st->bb = v; st->thresh = ref_mul(tol2, v); return; }
+	if (KIND == FIN_RZ) {
+		const double rz = part ? v : st->rr;
+		if (st->k != 0) st->beta = ref_div(rz, st->rz);
+		st->rz = rz;
+		if (!pcg_usable(rz)) st->state = SPSAMD_PCG_BREAKDOWN;
+		return;
+	}
+	if (KIND == FIN_PQ) {
+		st->pq = v;
+		if (!pcg_usable(v)) st->state = SPSAMD_PCG_BREAKDOWN;
+		else st->alpha = ref_div(st->rz, v);
+		return;
+	}
+	unsigned long long k = 0;
+	if (KIND == FIN_RR0) st->rr0 = v;
+	else { k = st->k + 1; st->k = k; }
+	st->rr = v;
+	if (k < st->hist_cap) hist[k] = v;
+	if (v <= st->thresh) st->state = SPSAMD_PCG_CONVERGED;               // (a NaN compares false)
+	else if (k == st->max_iter) st->state = SPSAMD_PCG_MAXITER;
+}
+
+// ---------------------------------------------------------------- host
+
+namespace {
+
+struct Pcg {
+	spsamd_ctx *c;
+	uint64_t n, c0;
+	bool unfused;
+	double *part, *b0, *b1, *hist;
+	PcgState *st;
+	uint64_t launches = 0;
+	unsigned chunk_grid() const { return (unsigned)((c0 + PCG_NT / 64 - 1) / (PCG_NT / 64)); }
+
+	void dot(const double *u, const double *w, const PcgState *pred)
+	{
+		if (!c0) return;
+		k_pcg_dot<<<dim3(chunk_grid()), dim3(PCG_NT), 0, c->stream>>>(u, w, n, part, pred);
+		SPS_LAUNCH_CHECK();
+		++launches;
+	}
+	template <int KIND> void finish(bool have_part, double tol2 = 0.0)
+	{
+		k_pcg_finish<KIND><<<dim3(1), dim3(PCG_FINISH_NT), 0, c->stream>>>(have_part ? part : nullptr, c0, b0, b1, st, hist, tol2);
+		SPS_LAUNCH_CHECK();
+		++launches;
+	}
+};
+
+// S with what the SpMV needs
+struct PcgOperator {
+	const uint32_t *ptr = nullptr;
+	const int32_t *col = nullptr;
+	const double *val = nullptr;
+	uint32_t long_min = 0xFFFFFFFFu; // rows of more tuples go to the wave kernel of k_spmm.hip
+	uint32_t nlong = 0;              // how many there are; then: their list and its length on the device, S's packed tuples in m
+	const uint32_t *list = nullptr, *count = nullptr;
+	DenseOperand m;
+};
+
+} // namespace
+
+// q = S in (+ the partials of dot(in, q) where `dot`).  Nothing is allocated here: it runs once per iteration.
+static void pcg_spmv(Pcg &k, const PcgOperator &op, const double *in, double *q, bool dot, const PcgState *pred)
+{
+	spsamd_ctx *c = k.c;
+	const bool fused = dot && !k.unfused;
+	if (fused) k_pcg_spmv<true><<<dim3(k.chunk_grid()), dim3(PCG_NT), 0, c->stream>>>(op.ptr, op.col, op.val, in, q, k.n, op.long_min, k.part, pred);
+	else k_pcg_spmv<false><<<dim3(k.chunk_grid()), dim3(PCG_NT), 0, c->stream>>>(op.ptr, op.col, op.val, in, q, k.n, op.long_min, k.part, pred);
+	SPS_LAUNCH_CHECK();
+	++k.launches;
+	if (op.nlong) {
+		spmm_long_rows(c, op.m, op.list, op.count, in, 1, q, 1, 1);
+		++k.launches;
+	}
+	if (!dot) return;
+	if (!fused || op.nlong > k.c0) k.dot(in, q, pred);                  // (more long rows than chunks: every chunk once instead)
+	else if (op.nlong) {
+		k_pcg_dot_rows<<<dim3(std::min<unsigned>(op.nlong, (unsigned)c->num_cu * 8)), dim3(64), 0, c->stream>>>(in, q, k.n, op.list, op.count, k.part, pred);
+		SPS_LAUNCH_CHECK();
+		++k.launches;
+	}
+}
+
+static const uint32_t *taken_rowptr(spsamd_ctx *c, ConMat &S, Prepared *hp, uint64_t n)
+{
+	if (hp) { prepared_row_structure(c, hp); return hp->rowptr; }
+	if (!S.nnz) return get_zeroed<uint32_t>(c, n + 1);
+	S.nrow = n;
+	return dense_rowptr(c, S, 0);
+}
+
+static void check_vector_overlap(spsamd_ctx *c, const spsamd_coo *X, const char *name, const double *x, uint64_t bytes)
+{
+	const OperandView view = operand_view(c, X);
+	const uint64_t n = view.coo.nnz;
+	if (n >= (uint64_t(1) << 31)) throw Error{SPSAMD_EINVAL, std::string(name) + " has 2^31 or more tuples"};
+	const void *arr[3] = {view.coo.idx0, view.coo.idx1, view.coo.val};
+	for (int k = 0; k < 3; ++k)
+		if (ranges_overlap(x, bytes, arr[k], n * (k == 2 ? 8 : 4))) throw Error{SPSAMD_EINVAL, std::string("x overlaps the arrays of ") + name};
+}
+
+int solve_pcg(spsamd_ctx *c, const spsamd_coo *A, char transpose, int precond, const spsamd_coo *M, char transpose_M,
+	const double *b, double *x, int mem, double tol, uint64_t max_iter, double *hist_host, size_t hist_capacity,
+	int duplicate_policy, int zero_nan, spsamd_pcg_stats *stats, spsamd_result *res)
+{
+	if (precond < SPSAMD_PRECOND_NONE || precond > SPSAMD_PRECOND_LU) throw Error{SPSAMD_EINVAL, "precond must be SPSAMD_PRECOND_NONE, _JACOBI or _LU"};
+	if (mem != SPSAMD_MEM_HOST && mem != SPSAMD_MEM_DEVICE) throw Error{SPSAMD_EINVAL, "mem of b and x must be SPSAMD_MEM_HOST or SPSAMD_MEM_DEVICE"};
+	if (!(tol >= 0.0) || tol - tol != 0.0) throw Error{SPSAMD_EINVAL, "tol must be finite and not negative"};
+	if ((precond == SPSAMD_PRECOND_LU) != (M != nullptr)) throw Error{SPSAMD_EINVAL, "M goes with SPSAMD_PRECOND_LU, and only with it"};
+	if (duplicate_policy < 0 || duplicate_policy > 2) throw Error{SPSAMD_EINVAL, "bad duplicate_policy"};
+	const int lead = transpose == 'T' ? 1 : 0, lead_m = transpose_M == 'T' ? 1 : 0;
+	const uint64_t n = A->shape0;
+	if (A->shape0 != A->shape1) throw Error{SPSAMD_EDIM, "op(A) must be square"};
+	if (M && (M->shape0 != M->shape1 || M->shape0 != n)) throw Error{SPSAMD_EDIM, "op(M) must be square and of op(A)'s order"};
+	if (n && (!b || !x)) throw Error{SPSAMD_EINVAL, "null b or x"};
+	const uint64_t vbytes = n * sizeof(double);
+	if (ranges_overlap(x, vbytes, b, vbytes)) throw Error{SPSAMD_EINVAL, "x and b overlap"};
+	check_vector_overlap(c, A, "A", x, vbytes);
+	if (M) check_vector_overlap(c, M, "M", x, vbytes);
+	if (mem == SPSAMD_MEM_DEVICE && in_output_sets(c, x, vbytes)) throw Error{SPSAMD_EINVAL, "x lies in an output set of the context"};
+
+	std::memset(res, 0, sizeof(*res));
+	if (stats) std::memset(stats, 0, sizeof(*stats));
+	res->shape0 = res->shape1 = n;
+	if (!n) {                                                        // every dot is the fold of nothing: rr = +0.0 <= thresh
+		if (hist_host && hist_capacity) hist_host[0] = 0.0;
+		return SPSAMD_OK;
+	}
+
+	SPS_HIP(hipSetDevice(c->device));
+	c->arena.reset();
+	hipStream_t st = c->stream;
+	SPS_HIP(hipEventRecord(c->ev[EV_BEGIN], st));
+	ConMat S, F;
+	Prepared *hpa = nullptr, *hpm = nullptr;
+	consolidate_operand(c, A, lead, lead, duplicate_policy, zero_nan, &S, &hpa);
+	if (M) consolidate_operand(c, M, lead_m, lead_m, duplicate_policy, zero_nan, &F, &hpm);
+	SPS_HIP(hipEventRecord(c->ev[EV_CONSOLIDATED], st));
+	res->nnz_a = S.nnz;
+	res->nnz_b = M ? F.nnz : 0;
+
+	Pcg k;
+	k.c = c; k.n = n; k.c0 = (n + PCG_CHUNK - 1) / PCG_CHUNK; k.unfused = c->tune.pcg_fuse == 1;
+	const uint64_t c1 = (k.c0 + PCG_CHUNK - 1) / PCG_CHUNK;
+	k.part = c->arena.get<double>(k.c0); k.b0 = c->arena.get<double>(c1); k.b1 = c->arena.get<double>(c1);
+	k.st = c->arena.get<PcgState>(1);
+	const uint64_t hcap = !hist_host ? 0 : std::min<uint64_t>(hist_capacity, max_iter == ~0ull ? max_iter : max_iter + 1);
+	k.hist = hcap ? c->arena.get<double>(hcap) : nullptr;
+
+	// ---- the operator: S's row pointer; the long rows' list and the packed rows of k_spmm.hip only where there is a long row
+	PcgOperator op;
+	op.ptr = taken_rowptr(c, S, hpa, n);
+	op.col = S.col; op.val = S.val;
+	if (S.nnz) {
+		const int path = c->tune.spmm_path;
+		op.long_min = path == 1 ? 0xFFFFFFFFu : path >= 2 ? 0u : c->tune.spmm_long_min > 0 ? (uint32_t)c->tune.spmm_long_min : 64u;
+		uint32_t *list = nullptr, *count = nullptr;
+		if (path != 1) op.nlong = spmm_long_list(c, op.ptr, n, op.long_min, &list, &count);
+		if (op.nlong) {
+			op.list = list; op.count = count;
+			op.m.rowptr = op.ptr; op.m.nrow = op.m.ncol = n; op.m.nnz = S.nnz;
+			if (hpa) op.m.tup = prepared_btup(c, hpa);
+			else { BTup *t = c->arena.get<BTup>(S.nnz); pack_tuples(c, S.col, S.val, S.nnz, t); op.m.tup = t; }
+		}
+	}
+
+	// ---- the preconditioner
+	double *diag = nullptr;
+	TriView tl = {}, tu = {};
+	SolveSchedule local[2], *sched[2] = {nullptr, nullptr};
+	uint32_t analyses = 0;
+	if (precond == SPSAMD_PRECOND_JACOBI) {
+		diag = c->arena.get<double>(n);
+		if (S.nnz) reduce_diag_dense(c, op.ptr, S.col, S.val, n, diag);
+		else fill_zero(c, diag, vbytes);
+	} else if (precond == SPSAMD_PRECOND_LU) {
+		tl.ptr = taken_rowptr(c, F, hpm, n);
+		tl.col = F.col; tl.val = F.val; tl.n = n; tl.upper = 0; tl.unit = 1;
+		tu = tl; tu.upper = 1; tu.unit = 0;
+		const TriView *tv[2] = {&tl, &tu};
+		for (int s = 0; s < 2; ++s) {
+			const bool kept = hpm && hpm->owns;
+			sched[s] = kept ? &hpm->solve[s == 0 ? SPSAMD_TRI_LOWER : SPSAMD_TRI_UPPER][s == 0 ? SPSAMD_DIAG_UNIT : SPSAMD_DIAG_NONUNIT] : &local[s];
+			if (sched[s]->built) continue;
+			uint64_t peel[2] = {0, 0};
+			try { analyse(c, *tv[s], kept ? hpm : nullptr, sched[s], peel); }
+			catch (...) { *sched[s] = SolveSchedule(); throw; }
+			++analyses;
+		}
+	}
+
+	// ---- the vectors
+	const double *db = to_device(c, b, n, mem);
+	double *dx = x;
+	if (mem == SPSAMD_MEM_HOST) { dx = c->arena.get<double>(n); SPS_HIP(hipMemcpyAsync(dx, x, vbytes, hipMemcpyHostToDevice, st)); }
+	double *r = c->arena.get<double>(n), *p = c->arena.get<double>(n), *q = c->arena.get<double>(n);
+	double *z = precond == SPSAMD_PRECOND_NONE ? r : c->arena.get<double>(n);
+	const bool vec = (((uintptr_t)z | (uintptr_t)p) & 15u) == 0;
+
+	// ---- bb, thresh; r = b - A x, rr0, hist[0], the stop tests before the first iteration
+	k_pcg_init<<<dim3(1), dim3(1), 0, st>>>(k.st, max_iter, hcap);
+	SPS_LAUNCH_CHECK();
+	k.dot(db, db, nullptr);
+	k.finish<FIN_BB>(true, tol * tol);
+	pcg_spmv(k, op, dx, q, false, nullptr);
+	if (k.unfused) {
+		k_pcg_residual<false><<<dim3(k.chunk_grid()), dim3(PCG_NT), 0, st>>>(db, q, r, n, k.part);
+		SPS_LAUNCH_CHECK();
+		k.dot(r, r, nullptr);
+	} else {
+		k_pcg_residual<true><<<dim3(k.chunk_grid()), dim3(PCG_NT), 0, st>>>(db, q, r, n, k.part);
+		SPS_LAUNCH_CHECK();
+	}
+	k.finish<FIN_RR0>(true);
+	SPS_HIP(hipEventRecord(c->ev[EV_SYMBOLIC], st));
+
+	// ---- the iterations, pcg_check_every of them between two reads of the state
+	const uint64_t every = c->tune.pcg_check_every > 0 ? (uint64_t)c->tune.pcg_check_every : (uint64_t)PCG_CHECK_EVERY;
+	k.launches = 0;
+	uint64_t readbacks = 0, enqueued = 0;
+	PcgState hs;
+	for (;;) {
+		hs = read_back(c, k.st);
+		++readbacks;
+		if (hs.state != PCG_RUNNING) break;
+		const uint64_t batch = std::min<uint64_t>(every, max_iter - enqueued);   // (RUNNING: k < max_iter, and k <= enqueued)
+		for (uint64_t it = 0; it < batch; ++it) {
+			// z = M^-1 r, rz' = dot(r, z), beta, rz
+			if (precond == SPSAMD_PRECOND_JACOBI) {
+				if (k.unfused) k_pcg_jacobi<false><<<dim3(k.chunk_grid()), dim3(PCG_NT), 0, st>>>(r, diag, z, n, k.part, k.st);
+				else k_pcg_jacobi<true><<<dim3(k.chunk_grid()), dim3(PCG_NT), 0, st>>>(r, diag, z, n, k.part, k.st);
+				SPS_LAUNCH_CHECK();
+				++k.launches;
+				if (k.unfused) k.dot(r, z, k.st);
+			} else if (precond == SPSAMD_PRECOND_LU) {
+				k.launches += solve_levels(c, tl, *sched[0], r, 1, z, 1, 1, nullptr);
+				k.launches += solve_levels(c, tu, *sched[1], z, 1, z, 1, 1, nullptr);
+				k.dot(r, z, k.st);
+			}
+			k.finish<FIN_RZ>(precond != SPSAMD_PRECOND_NONE);
+			if (vec) k_pcg_direction<true><<<dim3(grid_for((n + 1) / 2)), dim3(256), 0, st>>>(z, p, n, k.st);
+			else k_pcg_direction<false><<<dim3(grid_for(n)), dim3(256), 0, st>>>(z, p, n, k.st);
+			SPS_LAUNCH_CHECK();
+			++k.launches;
+			// q = A p, pq = dot(p, q), alpha
+			pcg_spmv(k, op, p, q, true, k.st);
+			k.finish<FIN_PQ>(true);
+			// x += alpha p, r -= alpha q, rr = dot(r, r), k, hist, the stop tests
+			if (k.unfused) {
+				k_pcg_update<1><<<dim3(k.chunk_grid()), dim3(PCG_NT), 0, st>>>(dx, p, r, q, n, k.part, k.st);
+				SPS_LAUNCH_CHECK();
+				k_pcg_update<2><<<dim3(k.chunk_grid()), dim3(PCG_NT), 0, st>>>(dx, p, r, q, n, k.part, k.st);
+				SPS_LAUNCH_CHECK();
+				k.launches += 2;
+				k.dot(r, r, k.st);
+			} else {
+				k_pcg_update<0><<<dim3(k.chunk_grid()), dim3(PCG_NT), 0, st>>>(dx, p, r, q, n, k.part, k.st);
+				SPS_LAUNCH_CHECK();
+				++k.launches;
+			}
+			k.finish<FIN_RR>(true);
+		}
+		enqueued += batch;
+	}
+
+	if (mem == SPSAMD_MEM_HOST) SPS_HIP(hipMemcpyAsync(x, dx, vbytes, hipMemcpyDeviceToHost, st));
+	const uint64_t nh = std::min<uint64_t>(hs.k + 1, hcap);
+	if (nh) SPS_HIP(hipMemcpyAsync(hist_host, k.hist, nh * sizeof(double), hipMemcpyDeviceToHost, st));
+	finish_call(c, res);
+	SPS_HIP(hipEventElapsedTime(&res->ms_consolidate, c->ev[EV_BEGIN], c->ev[EV_CONSOLIDATED]));
+	SPS_HIP(hipEventElapsedTime(&res->ms_symbolic, c->ev[EV_CONSOLIDATED], c->ev[EV_SYMBOLIC]));
+	SPS_HIP(hipEventElapsedTime(&res->ms_numeric, c->ev[EV_SYMBOLIC], c->ev[EV_END]));
+	if (stats) {
+		stats->iterations = hs.k; stats->reason = hs.state;
+		stats->bb = hs.bb; stats->rr0 = hs.rr0; stats->rr = hs.rr;
+		stats->launches = k.launches; stats->readbacks = readbacks; stats->analyses = analyses;
+		stats->ms_setup = res->ms_consolidate + res->ms_symbolic; stats->ms_iterate = res->ms_numeric;
+	}
+	return SPSAMD_OK;
+}
+
+} // namespace spsamd

@@ -338,6 +338,52 @@ bool in_output_sets(const spsamd_ctx *c, const void *p, uint64_t bytes)
 	return false;
 }
 
+// The folds of reduce_rows in two steps, shared with reduce_diag_dense.  ctr: 40 zeroed words ([0..3] the classes, [4] DIAG's
+// rows, [8..39] the bins).  Step one counts the rows by class, folds the short rows (under reduce_path 2 there are none:
+// the dense result and DIAG's marks are zeroed instead) unless the caller defers that until it has seen the counters, and
+// brings the first eight counters to h.
+static void fold_short_rows(spsamd_ctx *c, int op, const RedArgs &a, uint32_t *ctr, uint32_t *h, bool zero_dense, bool defer_short)
+{
+	hipStream_t st = c->stream;
+	k_red_classify<false><<<dim3(grid_for(a.nrow)), dim3(256), 0, st>>>(a.ptr, a.nrow, a.path, ctr, ctr + 8, nullptr);
+	SPS_LAUNCH_CHECK();
+	if (a.path == 2) {
+		if (zero_dense) fill_zero(c, a.dval, a.nrow * sizeof(double));
+		if (op == SPSAMD_REDUCE_DIAG) fill_zero(c, a.has, a.nrow);
+	} else if (!defer_short) run_short(c, op, a);
+	SPS_HIP(hipMemcpyAsync(h, ctr, 8 * sizeof(uint32_t), hipMemcpyDeviceToHost, st));
+	SPS_HIP(hipStreamSynchronize(st));
+}
+
+// Step two: the nlong (= h[1]) long rows listed bin by bin, longest first, and folded.
+static void fold_long_rows(spsamd_ctx *c, int op, const RedArgs &a, uint32_t *ctr, uint32_t nlong)
+{
+	if (!nlong) return;
+	hipStream_t st = c->stream;
+	uint32_t *list = c->arena.get<uint32_t>((size_t)nlong + 1);
+	k_red_binscan<<<dim3(1), dim3(64), 0, st>>>(ctr + 8);
+	SPS_LAUNCH_CHECK();
+	k_red_classify<true><<<dim3(grid_for(a.nrow)), dim3(256), 0, st>>>(a.ptr, a.nrow, a.path, ctr, ctr + 8, list);
+	SPS_LAUNCH_CHECK();
+	run_long(c, op, a, list, nlong);
+}
+
+// (declared in internal.h: spsamd_solve_pcg's Jacobi preconditioner) the DIAG fold of a taken operand, dense, by the two
+// steps above: d[i] = +0.0 and then every diagonal tuple of row i added in S's order
+void reduce_diag_dense(spsamd_ctx *c, const uint32_t *ptr, const int32_t *col, const double *val, uint64_t nrow, double *d)
+{
+	RedArgs a;
+	a.ptr = ptr; a.col = col; a.val = val; a.nrow = nrow; a.post = SPSAMD_POST_NONE;
+	a.path = c->tune.reduce_path == 1 || c->tune.reduce_path == 2 ? c->tune.reduce_path : 0;
+	a.dval = d;
+	a.has = c->arena.get<uint8_t>(nrow + 8);
+	uint32_t *ctr = get_zeroed<uint32_t>(c, 40);
+	a.nz = ctr + 4;
+	uint32_t *h = (uint32_t *)c->host_staging(8 * sizeof(uint32_t));
+	fold_short_rows(c, SPSAMD_REDUCE_DIAG, a, ctr, h, true, false);
+	fold_long_rows(c, SPSAMD_REDUCE_DIAG, a, ctr, h[1]);
+}
+
 int reduce_rows(spsamd_ctx *c, const spsamd_coo *A, char transpose, int op, int post, int duplicate_policy, int zero_nan,
 	int32_t *out_idx, double *out_val, size_t capacity, int mem, size_t *out_nnz, spsamd_result *res)
 {
@@ -411,9 +457,9 @@ int reduce_rows(spsamd_ctx *c, const spsamd_coo *A, char transpose, int op, int 
 	};
 
 	uint64_t count = 0;
-	k_red_classify<false><<<dim3(grid_for(nrow)), dim3(256), 0, st>>>(ptr, nrow, path, ctr, ctr + 8, nullptr);
-	SPS_LAUNCH_CHECK();
 	if (op == SPSAMD_REDUCE_COUNT) {
+		k_red_classify<false><<<dim3(grid_for(nrow)), dim3(256), 0, st>>>(ptr, nrow, path, ctr, ctr + 8, nullptr);
+		SPS_LAUNCH_CHECK();
 		k_red_rowcount<<<dim3(grid_for(nrow)), dim3(256), 0, st>>>(a);
 		SPS_LAUNCH_CHECK();
 		read_counters();
@@ -423,25 +469,14 @@ int reduce_rows(spsamd_ctx *c, const spsamd_coo *A, char transpose, int op, int 
 		// the size of a sparse result is known before any fold, except DIAG's; elsewhere the short rows' kernel runs
 		// while the host waits for the counters
 		const bool early = sparse && !diag;
-		if (path == 2) {
-			if (!sparse) fill_zero(c, a.dval, nrow * sizeof(double));
-			if (diag) fill_zero(c, a.has, nrow);
-		} else if (!early) run_short(c, op, a);
-		read_counters();
+		fold_short_rows(c, op, a, ctr, h, !sparse, early);
 		count = (uint64_t)h[0] + h[1];
 		if (early && capacity < count) return too_small(count);
 		if (path != 2 && early) run_short(c, op, a);
 		const uint32_t nlong = h[1];
 		res->rows_light = h[0]; res->rows_heavy = nlong;
 		res->tuples_light = h[2]; res->tuples_heavy = h[3];
-		if (nlong) {
-			uint32_t *list = c->arena.get<uint32_t>((size_t)nlong + 1);
-			k_red_binscan<<<dim3(1), dim3(64), 0, st>>>(ctr + 8);
-			SPS_LAUNCH_CHECK();
-			k_red_classify<true><<<dim3(grid_for(nrow)), dim3(256), 0, st>>>(ptr, nrow, path, ctr, ctr + 8, list);
-			SPS_LAUNCH_CHECK();
-			run_long(c, op, a, list, nlong);
-		}
+		fold_long_rows(c, op, a, ctr, nlong);
 		if (diag) {
 			count = read_back(c, a.nz);
 			if (sparse && capacity < count) return too_small(count);

@@ -415,6 +415,52 @@ void analyse(spsamd_ctx *c, const TriView &t, Prepared *hp, SolveSchedule *s, ui
 	s->built = true;
 }
 
+// (declared in internal.h: spsamd_solve_pcg applies a factor's two triangles every iteration on schedules it got once)
+uint64_t solve_levels(spsamd_ctx *c, const TriView &t, const SolveSchedule &s, const double *B, uint64_t ldb, double *X,
+	uint64_t ldx, uint32_t nrhs, uint64_t *fused_levels)
+{
+	hipStream_t st = c->stream;
+	SolveArgs a;
+	a.t = t; a.rows = s.rows; a.level_ptr = s.level_ptr; a.nrhs = nrhs;
+	a.B = B; a.ldb = ldb; a.X = X; a.ldx = ldx;
+	const int path = c->tune.solve_path == 1 || c->tune.solve_path == 2 ? c->tune.solve_path : 0;
+	const int rowk = c->tune.solve_row >= 1 && c->tune.solve_row <= 3 ? c->tune.solve_row : 0;
+	// serial rows: up to long_min tuples (0 in a forced wave kernel: only the empty rows are serial)
+	a.long_min = rowk == 1 ? 0xFFFFFFFFu : rowk >= 2 ? 0u : c->tune.spmm_long_min > 0 ? (uint32_t)c->tune.spmm_long_min : 64u;
+	const bool lanes = rowk == 2 || (rowk == 0 && nrhs >= 16);
+	// (a set knob is taken as given; the default also bounds a thin level's work, which grows with nrhs)
+	const uint32_t fuse_rows = c->tune.solve_fuse_rows > 0 ? (uint32_t)c->tune.solve_fuse_rows
+		: (uint32_t)std::min<uint64_t>(SOLVE_FUSE_ROWS, std::max<uint64_t>(SOLVE_FUSE_WORK / nrhs, 1));
+	const uint32_t *lp = s.h_level_ptr.data(), *lmax = s.h_level_max.data();
+	auto thin = [&](uint32_t l) { return path != 1 && lmax[l] <= a.long_min && (path == 2 || lp[l + 1] - lp[l] <= fuse_rows); };
+	uint64_t launches = 0, fused = 0;
+	for (uint32_t l = 0; l < s.levels;) {
+		if (thin(l)) {
+			uint32_t e = l + 1;
+			while (e < s.levels && thin(e)) ++e;
+			k_solve_fused<<<dim3(1), dim3(SOLVE_NT), 0, st>>>(a, l, e);
+			SPS_LAUNCH_CHECK();
+			++launches; fused += e - l;
+			l = e;
+			continue;
+		}
+		const uint32_t lo = lp[l], hi = lp[l + 1];
+		const uint64_t total = (uint64_t)(hi - lo) * nrhs;
+		k_solve_serial<<<dim3((unsigned)std::min<uint64_t>(grid_for(total), (uint64_t)c->num_cu * 64)), dim3(256), 0, st>>>(a, lo, hi);
+		SPS_LAUNCH_CHECK();
+		++launches;
+		if (lmax[l] > a.long_min) {
+			if (lanes) k_solve_lanes<<<dim3(hi - lo), dim3(64), 0, st>>>(a, lo);
+			else k_solve_fold<<<dim3(hi - lo), dim3(64), 0, st>>>(a, lo);
+			SPS_LAUNCH_CHECK();
+			++launches;
+		}
+		++l;
+	}
+	if (fused_levels) *fused_levels = fused;
+	return launches;
+}
+
 int solve_tri(spsamd_ctx *c, const spsamd_coo *A, char transpose, int uplo, int diag, const double *B, size_t ldb, double *X,
 	size_t ldx, size_t nrhs, int mem, int duplicate_policy, int zero_nan, spsamd_solve_stats *stats, spsamd_result *res)
 {
@@ -475,49 +521,18 @@ int solve_tri(spsamd_ctx *c, const spsamd_coo *A, char transpose, int uplo, int 
 	}
 	SPS_HIP(hipEventRecord(c->ev[EV_SYMBOLIC], st));
 
-	SolveArgs a;
-	a.t = t; a.rows = s->rows; a.level_ptr = s->level_ptr; a.nrhs = (uint32_t)nrhs;
+	const double *db = B;
+	double *dx = X;
+	uint64_t dldb = ldb, dldx = ldx;
 	if (mem == SPSAMD_MEM_HOST) {                                        // one packed device copy, solved in place
 		double *tx = c->arena.get<double>(N * nrhs);
 		SPS_HIP(hipMemcpy2DAsync(tx, nrhs * sizeof(double), B, ldb * sizeof(double), nrhs * sizeof(double), N, hipMemcpyHostToDevice, st));
-		a.B = tx; a.X = tx; a.ldb = a.ldx = nrhs;
-	} else { a.B = B; a.ldb = ldb; a.X = X; a.ldx = ldx; }
-	const int path = c->tune.solve_path == 1 || c->tune.solve_path == 2 ? c->tune.solve_path : 0;
-	const int rowk = c->tune.solve_row >= 1 && c->tune.solve_row <= 3 ? c->tune.solve_row : 0;
-	// serial rows: up to long_min tuples (0 in a forced wave kernel: only the empty rows are serial)
-	a.long_min = rowk == 1 ? 0xFFFFFFFFu : rowk >= 2 ? 0u : c->tune.spmm_long_min > 0 ? (uint32_t)c->tune.spmm_long_min : 64u;
-	const bool lanes = rowk == 2 || (rowk == 0 && nrhs >= 16);
-	// (a set knob is taken as given; the default also bounds a thin level's work, which grows with nrhs)
-	const uint32_t fuse_rows = c->tune.solve_fuse_rows > 0 ? (uint32_t)c->tune.solve_fuse_rows
-		: (uint32_t)std::min<uint64_t>(SOLVE_FUSE_ROWS, std::max<uint64_t>(SOLVE_FUSE_WORK / nrhs, 1));
-	const uint32_t *lp = s->h_level_ptr.data(), *lmax = s->h_level_max.data();
-	auto thin = [&](uint32_t l) { return path != 1 && lmax[l] <= a.long_min && (path == 2 || lp[l + 1] - lp[l] <= fuse_rows); };
-	uint64_t launches = 0, fused = 0;
-	for (uint32_t l = 0; l < s->levels;) {
-		if (thin(l)) {
-			uint32_t e = l + 1;
-			while (e < s->levels && thin(e)) ++e;
-			k_solve_fused<<<dim3(1), dim3(SOLVE_NT), 0, st>>>(a, l, e);
-			SPS_LAUNCH_CHECK();
-			++launches; fused += e - l;
-			l = e;
-			continue;
-		}
-		const uint32_t lo = lp[l], hi = lp[l + 1];
-		const uint64_t total = (uint64_t)(hi - lo) * nrhs;
-		k_solve_serial<<<dim3((unsigned)std::min<uint64_t>(grid_for(total), (uint64_t)c->num_cu * 64)), dim3(256), 0, st>>>(a, lo, hi);
-		SPS_LAUNCH_CHECK();
-		++launches;
-		if (lmax[l] > a.long_min) {
-			if (lanes) k_solve_lanes<<<dim3(hi - lo), dim3(64), 0, st>>>(a, lo);
-			else k_solve_fold<<<dim3(hi - lo), dim3(64), 0, st>>>(a, lo);
-			SPS_LAUNCH_CHECK();
-			++launches;
-		}
-		++l;
+		db = tx; dx = tx; dldb = dldx = nrhs;
 	}
+	uint64_t fused = 0;
+	const uint64_t launches = solve_levels(c, t, *s, db, dldb, dx, dldx, (uint32_t)nrhs, &fused);
 	if (mem == SPSAMD_MEM_HOST)
-		SPS_HIP(hipMemcpy2DAsync(X, ldx * sizeof(double), a.X, nrhs * sizeof(double), nrhs * sizeof(double), N, hipMemcpyDeviceToHost, st));
+		SPS_HIP(hipMemcpy2DAsync(X, ldx * sizeof(double), dx, nrhs * sizeof(double), nrhs * sizeof(double), N, hipMemcpyDeviceToHost, st));
 	finish_call(c, res);
 	SPS_HIP(hipEventElapsedTime(&res->ms_consolidate, c->ev[EV_BEGIN], c->ev[EV_CONSOLIDATED]));
 	SPS_HIP(hipEventElapsedTime(&res->ms_symbolic, c->ev[EV_CONSOLIDATED], c->ev[EV_SYMBOLIC]));

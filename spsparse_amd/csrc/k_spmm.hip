@@ -191,6 +191,36 @@ __global__ void k_pack_rows(const int32_t *__restrict__ minor, const double *__r
 	out[i] = t;
 }
 
+// (declared in internal.h: spsamd_solve_pcg packs an operand it took itself)
+void pack_tuples(spsamd_ctx *c, const int32_t *minor, const double *val, uint32_t n, BTup *out)
+{
+	if (!n) return;
+	k_pack_rows<<<dim3(grid_for(n)), dim3(256), 0, c->stream>>>(minor, val, n, out);
+	SPS_LAUNCH_CHECK();
+}
+
+// (declared in internal.h) launch_spmm's two halves of the long rows for a caller that applies one operand many times: the
+// list once ...
+uint32_t spmm_long_list(spsamd_ctx *c, const uint32_t *rowptr, uint64_t nrow, uint32_t long_min, uint32_t **list, uint32_t **count)
+{
+	*count = get_zeroed<uint32_t>(c, 1);
+	*list = c->arena.get<uint32_t>(nrow ? nrow : 1);
+	k_spmm_long_rows<<<dim3(grid_for(nrow)), dim3(256), 0, c->stream>>>(rowptr, nrow, long_min, *list, *count);
+	SPS_LAUNCH_CHECK();
+	return read_back(c, *count);
+}
+
+// ... and the wave kernel over it per application (ADD, handle_nan off): one launch, nothing allocated
+void spmm_long_rows(spsamd_ctx *c, const DenseOperand &m, const uint32_t *list, const uint32_t *count, const double *X, uint64_t ldx,
+	double *Y, uint64_t ldy, uint32_t nrhs)
+{
+	const unsigned waves = (unsigned)c->num_cu * 8;
+	const bool lanes = c->tune.spmm_path == 2 || (c->tune.spmm_path == 0 && nrhs >= 16);
+	if (lanes) k_spmm_lanes<SPSAMD_ADD, false><<<dim3(waves), dim3(64), 0, c->stream>>>(m.rowptr, m.tup, list, count, X, ldx, Y, ldy, nrhs);
+	else k_spmm_fold<SPSAMD_ADD, false><<<dim3(waves), dim3(64), 0, c->stream>>>(m.rowptr, m.tup, list, count, X, ldx, Y, ldy, nrhs);
+	SPS_LAUNCH_CHECK();
+}
+
 __global__ void k_row_keys(const int32_t *__restrict__ major, uint32_t n, uint64_t *__restrict__ keys)
 {
 	const uint32_t i = blockIdx.x * blockDim.x + threadIdx.x;
