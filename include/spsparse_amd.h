@@ -773,6 +773,75 @@ int spsamd_color(spsamd_ctx *ctx, const spsamd_coo *A, char transpose, int order
 	size_t *out_ncolors, spsamd_color_stats *stats /* may be NULL */, spsamd_result *result /* may be NULL */);
 
 /*
+ * MIS(2) aggregation of op(A)'s graph: the coarsening step of aggregation multigrid.  A distance-2
+ * maximal independent set is chosen in the order of spsamd_color's key, and an aggregate is grown around every root.
+ *   - Operand.  op(A) is structural, taken exactly as spsamd_color takes it: val is never read and may be NULL, duplicate
+ *     keys count once, explicit zeros count; host, device, a chained SINK_COO result of this context (read in place) and a
+ *     prepared handle are accepted; sort0 only lets the call skip the sort, and a false one is rejected.  op(A) must be
+ *     square (SPSAMD_EDIM); n is its order, K its sorted unique key set.  Strength filtering is not part of this call:
+ *     run spsamd_select or spsamd_emult first and chain the result.
+ *   - Graph.  N(i) = { j != i : (i, j) in K or (j, i) in K }.  Under SPSAMD_AGG_SYMMETRIC the caller states that the pattern
+ *     is symmetric and N(i) is row i alone, without a symmetrisation pass; the promise is checked: asymmetric = the number
+ *     of keys (i, j) of K with i != j and (j, i) not in K, and if it is not 0 the call returns SPSAMD_EINVAL with a message
+ *     and writes no buffer (a distance-2 set on a directed pattern has no definition worth pinning).  deg(i) = |N(i)|,
+ *     N[v] = N(v) + {v}.  u is WITHIN DISTANCE 2 of v when u != v and u is in N[w] for some w in N[v].
+ *   - Order.  key(v) = (order == SPSAMD_AGG_ORDER_DEGREE ? deg(v) : 0) << 32 | h(v), h and the seed mixing exactly
+ *     spsamd_color's.  u precedes v when key(u) > key(v); keys never tie.
+ *   - Every output is defined by this loop:
+ *         root[v] = 0 for all v
+ *         for v in descending key:   root[v] = 1 unless some u within distance 2 of v has root[u] = 1
+ *         id(r) = the number of roots with index < r                 (roots numbered in ascending vertex index)
+ *         ring 0:  a root v:                            agg[v] = id(v)
+ *         ring 1:  a non-root v with a root r in N(v):  agg[v] = id(r)    (r is unique: two roots in N(v) would lie within distance 2)
+ *         ring 2:  every other v:                       agg[v] = agg[w], w the ring-1 vertex of N(v) with the largest key
+ *                                                       (one exists: the set is maximal, so a root lies at distance exactly 2)
+ *     An isolated vertex is a root and an aggregate of its own.  naggregates = the number of roots (0 for n = 0); ring1 and
+ *     ring2 count the vertices of those rings.
+ *   - rounds is defined by the synchronous form the device runs:
+ *         state[v] = UNDECIDED for all v;  t = 0
+ *         while some v is UNDECIDED:
+ *             for every UNDECIDED v, all from the states at the start of the round:
+ *                 if a ROOT lies within distance 2 of v:                         v becomes OUT
+ *                 elif key(v) > key(u) for every UNDECIDED u within distance 2:  v becomes ROOT
+ *             t += 1
+ *         rounds = t
+ *     whose roots are exactly the loop's (DESIGN.md section 24 has the proof).  All of the above are functions of K, order,
+ *     seed and the flag only, never of timing or of a tuning knob.
+ *   - agg (required) gets n aggregate ids.  members (may be NULL) gets the n vertices ascending in (aggregate, ring, index):
+ *     members[agg_ptr[a]] is the root of aggregate a, its ring 1 follows, then its ring 2.  agg_ptr (may be NULL) gets
+ *     naggregates + 1 bounds into members.  The buffers are the caller's; `mem` (SPSAMD_MEM_HOST or SPSAMD_MEM_DEVICE) holds
+ *     for all three.  agg_ptr with ptr_capacity < naggregates + 1: nothing is written, *out_naggregates gets the count and
+ *     the call returns SPSAMD_ECAPACITY; a capacity of n + 1 always suffices.
+ *   - The tentative prolongator P (n x naggregates) is the spsamd_coo { idx0 = 0 .. n - 1, idx1 = agg, val = 1.0, sort0 = 0 }:
+ *     sorted, one tuple per row, to be trusted as it stands; the Galerkin operator is P^T (A P) by two spsamd_multiply calls.
+ * Workspace only, like spsamd_color: neither output set of the context is written, so a chained result stays valid and
+ * can be A.  SPSAMD_EINVAL, with a message and nothing written: A, agg or out_naggregates NULL; an order, flag or mem
+ * outside the above; buffers that overlap each other or A's arrays; a device buffer inside an output set of the context;
+ * an index out of bounds; a false sort0; 2^31 or more tuples; a false promise of symmetry.  n == 0 returns 0 with
+ * *out_naggregates = 0.  stats (may be NULL): see the struct.  result (may be NULL): the fields spsamd_color fills, with
+ * ms_numeric the sweep and the assignment together.  Returns when the buffers are complete.
+ */
+#define SPSAMD_AGG_ORDER_HASH    0   /* visit by hashed index */
+#define SPSAMD_AGG_ORDER_DEGREE  1   /* largest degree first, hash among equal degrees */
+#define SPSAMD_AGG_SYMMETRIC     1   /* agg_flags: the caller states that the pattern is symmetric (checked) */
+
+typedef struct {
+	uint64_t naggregates, rounds;     /* of the aggregation */
+	uint64_t ring1, ring2;            /* vertices adjacent to their root, and at distance 2 of it */
+	uint64_t max_size, min_size;      /* the largest and smallest aggregate (agg_ptr's differences), 0 for n = 0 */
+	uint64_t adjacency, max_degree;   /* the sum and the largest of deg */
+	uint64_t asymmetric;              /* see above; counted under the flag only, else 0 */
+	uint64_t launches;                /* spread and decide launches of the sweep of this call (a fused run is one) */
+	uint64_t fused_rounds;            /* rounds served inside the fused run: the tail of the sweep, one workgroup */
+	uint64_t rows_thread, rows_wave;  /* vertices by the kernel class that walks their row (degree 0: always thread) */
+	float ms_adjacency, ms_sweep, ms_assign;
+} spsamd_aggregate_stats;
+
+int spsamd_aggregate(spsamd_ctx *ctx, const spsamd_coo *A, char transpose, int order, uint32_t seed, int agg_flags,
+	int32_t *agg, int32_t *members, int32_t *agg_ptr, size_t ptr_capacity, int mem,
+	size_t *out_naggregates, spsamd_aggregate_stats *stats /* may be NULL */, spsamd_result *result /* may be NULL */);
+
+/*
  * Solve op(A) x = b by preconditioned conjugate gradients, one right-hand side, the whole loop on the device (DESIGN.md
  * section 23).  It is what the preconditioner stack is for: spsamd_factor_ilu0's result (after spsamd_color + spsamd_extract
  * or not) is M, spsamd_solve_tri's level schedules are built at most once per call, the scalars never visit the host.

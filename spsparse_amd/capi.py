@@ -49,6 +49,10 @@ factor_fuse_rows, factor_serial_work, factor_lds_row, factor_lds_row_max = 256, 
 COLOR_ORDER_HASH, COLOR_ORDER_DEGREE = 0, 1
 COLOR_SYMMETRIC = 1
 color_fuse_rows, color_wave_deg, color_fused_threads = 1024, 16, 1024
+# aggregate: the orders, the flag, and the defaults of the agg_fuse_rows and agg_wave_deg knobs
+AGG_ORDER_HASH, AGG_ORDER_DEGREE = 0, 1
+AGG_SYMMETRIC = 1
+agg_fuse_rows, agg_wave_deg = 1024, 32
 # solve_pcg: the preconditioners, the stop reasons, the default of the pcg_check_every knob and the elements of one chunk of
 # the dot products' fold
 PRECOND_NONE, PRECOND_JACOBI, PRECOND_LU = 0, 1, 2
@@ -119,6 +123,12 @@ class ColorStats(C.Structure):
                 ("rows_thread", C.c_uint64), ("rows_wave", C.c_uint64), ("ms_adjacency", C.c_float), ("ms_color", C.c_float)]
 
 
+class AggregateStats(C.Structure):
+    _fields_ = [(k, C.c_uint64) for k in ("naggregates", "rounds", "ring1", "ring2", "max_size", "min_size", "adjacency", "max_degree",
+                                          "asymmetric", "launches", "fused_rounds", "rows_thread", "rows_wave")] + \
+               [("ms_adjacency", C.c_float), ("ms_sweep", C.c_float), ("ms_assign", C.c_float)]
+
+
 class PcgStats(C.Structure):
     _fields_ = [("iterations", C.c_uint64), ("reason", C.c_int32), ("bb", C.c_double), ("rr0", C.c_double), ("rr", C.c_double),
                 ("launches", C.c_uint64), ("readbacks", C.c_uint64), ("analyses", C.c_uint32),
@@ -145,7 +155,7 @@ SYMBOLS = ["spsamd_ctx_create", "spsamd_ctx_destroy", "spsamd_last_error", "spsa
            "spsamd_operand_prepare", "spsamd_operand_as_coo", "spsamd_operand_bytes", "spsamd_operand_destroy",
            "spsamd_multiply_dense", "spsamd_add", "spsamd_multiply_stream", "spsamd_multiply_masked",
            "spsamd_multiply_sampled", "spsamd_select", "spsamd_extract", "spsamd_reduce", "spsamd_emult", "spsamd_solve_tri",
-           "spsamd_factor_ilu0", "spsamd_color", "spsamd_solve_pcg"]
+           "spsamd_factor_ilu0", "spsamd_color", "spsamd_solve_pcg", "spsamd_aggregate"]
 
 _lib = None
 
@@ -207,6 +217,8 @@ def load():
     L.spsamd_factor_ilu0.argtypes = [C.c_void_p, P(Coo), C.c_char, C.c_int, C.c_int, C.c_int, C.c_int, P(FactorStats), P(Result)]
     L.spsamd_color.argtypes = [C.c_void_p, P(Coo), C.c_char, C.c_int, C.c_uint32, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p,
                                C.c_size_t, C.c_int, P(C.c_size_t), P(ColorStats), P(Result)]
+    L.spsamd_aggregate.argtypes = [C.c_void_p, P(Coo), C.c_char, C.c_int, C.c_uint32, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p,
+                                   C.c_size_t, C.c_int, P(C.c_size_t), P(AggregateStats), P(Result)]
     L.spsamd_solve_pcg.argtypes = [C.c_void_p, P(Coo), C.c_char, C.c_int, P(Coo), C.c_char, C.c_void_p, C.c_void_p, C.c_int,
                                    C.c_double, C.c_uint64, C.c_void_p, C.c_size_t, C.c_int, C.c_int, P(PcgStats), P(Result)]
     L.spsamd_memcpy.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_size_t]
@@ -252,6 +264,20 @@ def result_operand(res):
     """A SINK_COO result as the device operand of the NEXT call on the same context (read in place:
     sorted row-major, each index once -- sort0 = 0, so it is trusted like Consolidate<> does)."""
     return Coo(res.idx0, res.idx1, res.val, int(res.nnz), int(res.shape0), int(res.shape1), 0, MEM_DEVICE)
+
+
+def prolongator(agg, naggregates, device=False):
+    """The tentative prolongator P (n x naggregates) of Context.aggregate's agg: (Coo, keepalive) with idx0 = 0 .. n - 1,
+    idx1 = agg, val = 1.0 and sort0 = 0 -- sorted, one tuple per row, trusted as it stands.  agg: a numpy array, or an
+    int32 torch tensor (kept where it is if on the device).  device: build the arrays with torch on cuda, else numpy."""
+    n = int(agg.shape[0])
+    if device or not isinstance(agg, np.ndarray):
+        import torch
+        a1 = torch.as_tensor(agg, dtype=torch.int32).to("cuda").contiguous()
+        a0 = torch.arange(n, dtype=torch.int32, device=a1.device)
+        av = torch.ones(n, dtype=torch.float64, device=a1.device)
+        return device_coo(a0.data_ptr(), a1.data_ptr(), av.data_ptr(), n, (n, int(naggregates)), 0), (a0, a1, av)
+    return host_coo(np.arange(n, dtype=np.int32), agg, np.ones(n), (n, int(naggregates)), 0)
 
 
 def host_vec(idx, val, shape0, sort0=-1):
@@ -587,6 +613,46 @@ class Context:
         color, perm, ptr = np.empty(max(n, 1), np.int32), np.empty(max(n, 1), np.int32), np.empty(n + 1, np.int32)
         self._check(call(color.ctypes.data, perm.ctypes.data, ptr.ctypes.data, n + 1, MEM_HOST))
         got = (color[:n].copy(), perm[:n].copy(), ptr[:cnt.value + 1].copy())
+        return got + (st,) if stats else got
+
+    def aggregate(self, A, order=AGG_ORDER_HASH, seed=0, flags=0, transpose='.', out=None, stats=False, result=None):
+        """spsamd_aggregate: the MIS(2) aggregates of op(A)'s graph, exactly the serial loop of the header.  A: a Coo struct
+        whose op() is square (only its keys are read).  Without out: returns numpy int32 arrays (agg, members, agg_ptr) --
+        members the vertices ascending in (aggregate, ring, index), agg_ptr the naggregates + 1 bounds of the aggregates in
+        members.  With out: contiguous 1-D int32 torch tensors on this context's device, (agg, members, agg_ptr) with
+        members and agg_ptr possibly None, that receive the result; the aggregate count is returned, and an agg_ptr that
+        is too small raises SpsamdError with code -5.  stats=True appends an AggregateStats to what is returned.  result:
+        a capi.Result to fill (timings).  prolongator(agg, naggregates) makes the tentative prolongator of the result."""
+        n = int(A.shape1 if transpose == 'T' else A.shape0)
+        cnt, st = C.c_size_t(0), AggregateStats()
+        rp = None if result is None else C.byref(result)
+
+        def call(pa, pm, pq, cap, mem):
+            return self.L.spsamd_aggregate(self.h, C.byref(A), transpose.encode(), int(order), int(seed) & 0xFFFFFFFF, int(flags),
+                                           pa, pm, pq, cap, mem, C.byref(cnt), C.byref(st), rp)
+
+        if out is not None:
+            oa, om, oq = out
+            ptrs, sizes = [], []
+            for t, name in ((oa, "out agg"), (om, "out members"), (oq, "out agg_ptr")):
+                if t is None:
+                    if name == "out agg":
+                        raise ValueError("out agg is required")
+                    ptrs.append(None)
+                    sizes.append(0)
+                    continue
+                _p, nt, mt, _k = _index_list(t, name)
+                if mt != MEM_DEVICE and nt:
+                    raise ValueError("%s must be a device tensor" % name)
+                ptrs.append(t.data_ptr())
+                sizes.append(nt)
+            if sizes[0] < n or (om is not None and sizes[1] < n):
+                raise ValueError("out agg and out members need %d entries" % n)
+            self._check(call(ptrs[0], ptrs[1], ptrs[2], sizes[2], MEM_DEVICE))
+            return (int(cnt.value), st) if stats else int(cnt.value)
+        agg, mem, ptr = np.empty(max(n, 1), np.int32), np.empty(max(n, 1), np.int32), np.empty(n + 1, np.int32)
+        self._check(call(agg.ctypes.data, mem.ctypes.data, ptr.ctypes.data, n + 1, MEM_HOST))
+        got = (agg[:n].copy(), mem[:n].copy(), ptr[:cnt.value + 1].copy())
         return got + (st,) if stats else got
 
     def solve_pcg(self, A, b, x=None, precond=PRECOND_NONE, M=None, transpose='.', transpose_M='.', tol=1e-8, max_iter=1000,

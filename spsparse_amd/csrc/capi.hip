@@ -50,8 +50,8 @@ extern "C" int spsamd_ctx_create(spsamd_ctx **out, int device, void *hip_stream)
 	if (hipStreamCreateWithFlags(&c->side2, hipStreamNonBlocking) != hipSuccess) { spsamd_ctx_destroy(c); return SPSAMD_EHIP; }
 	for (auto &e : c->ev_side2) if (hipEventCreateWithFlags(&e, hipEventDisableTiming) != hipSuccess) { spsamd_ctx_destroy(c); return SPSAMD_EHIP; }
 	// developer knobs: the environment is consulted here and nowhere else
-	static const char *const knobs[] = {"window", "cell_cap", "dense_min", "no_tiles", "xcd", "emit_path", "light_path", "no_wmajor", "direct_min", "tiles_v1", "long_cap", "long_dense_min", "index_budget_mb", "trace", "light_two_pass", "spmm_path", "spmm_long_min", "add_path", "masked_path", "sampled_path", "select_path", "extract_path", "reduce_path", "emult_path", "tile_walk", "solve_path", "solve_row", "solve_fuse_rows", "factor_path", "factor_row", "factor_fuse_rows", "factor_serial_work", "factor_lds_row", "color_path", "color_row", "color_fuse_rows", "color_wave_deg", "pcg_check_every", "pcg_fuse"};
-	static const char *const envs[] = {"SPSAMD_W", "SPSAMD_CELL_CAP", "SPSAMD_DENSE_MIN", "SPSAMD_NO_TILES", "SPSAMD_XCD", "SPSAMD_EMIT_PATH", "SPSAMD_LIGHT_PATH", "SPSAMD_NO_WMAJOR", "SPSAMD_DIRECT_MIN", "SPSAMD_TILES_V1", "SPSAMD_LONG_CAP", "SPSAMD_LONG_DENSE_MIN", "SPSAMD_INDEX_BUDGET_MB", "SPSAMD_TRACE", "SPSAMD_LIGHT_TWO_PASS", "SPSAMD_SPMM_PATH", "SPSAMD_SPMM_LONG_MIN", "SPSAMD_ADD_PATH", "SPSAMD_MASKED_PATH", "SPSAMD_SAMPLED_PATH", "SPSAMD_SELECT_PATH", "SPSAMD_EXTRACT_PATH", "SPSAMD_REDUCE_PATH", "SPSAMD_EMULT_PATH", "SPSAMD_TILE_WALK", "SPSAMD_SOLVE_PATH", "SPSAMD_SOLVE_ROW", "SPSAMD_SOLVE_FUSE_ROWS", "SPSAMD_FACTOR_PATH", "SPSAMD_FACTOR_ROW", "SPSAMD_FACTOR_FUSE_ROWS", "SPSAMD_FACTOR_SERIAL_WORK", "SPSAMD_FACTOR_LDS_ROW", "SPSAMD_COLOR_PATH", "SPSAMD_COLOR_ROW", "SPSAMD_COLOR_FUSE_ROWS", "SPSAMD_COLOR_WAVE_DEG", "SPSAMD_PCG_CHECK_EVERY", "SPSAMD_PCG_FUSE"};
+	static const char *const knobs[] = {"window", "cell_cap", "dense_min", "no_tiles", "xcd", "emit_path", "light_path", "no_wmajor", "direct_min", "tiles_v1", "long_cap", "long_dense_min", "index_budget_mb", "trace", "light_two_pass", "spmm_path", "spmm_long_min", "add_path", "masked_path", "sampled_path", "select_path", "extract_path", "reduce_path", "emult_path", "tile_walk", "solve_path", "solve_row", "solve_fuse_rows", "factor_path", "factor_row", "factor_fuse_rows", "factor_serial_work", "factor_lds_row", "color_path", "color_row", "color_fuse_rows", "color_wave_deg", "agg_path", "agg_row", "agg_fuse_rows", "agg_wave_deg", "agg_per_rows", "pcg_check_every", "pcg_fuse"};
+	static const char *const envs[] = {"SPSAMD_W", "SPSAMD_CELL_CAP", "SPSAMD_DENSE_MIN", "SPSAMD_NO_TILES", "SPSAMD_XCD", "SPSAMD_EMIT_PATH", "SPSAMD_LIGHT_PATH", "SPSAMD_NO_WMAJOR", "SPSAMD_DIRECT_MIN", "SPSAMD_TILES_V1", "SPSAMD_LONG_CAP", "SPSAMD_LONG_DENSE_MIN", "SPSAMD_INDEX_BUDGET_MB", "SPSAMD_TRACE", "SPSAMD_LIGHT_TWO_PASS", "SPSAMD_SPMM_PATH", "SPSAMD_SPMM_LONG_MIN", "SPSAMD_ADD_PATH", "SPSAMD_MASKED_PATH", "SPSAMD_SAMPLED_PATH", "SPSAMD_SELECT_PATH", "SPSAMD_EXTRACT_PATH", "SPSAMD_REDUCE_PATH", "SPSAMD_EMULT_PATH", "SPSAMD_TILE_WALK", "SPSAMD_SOLVE_PATH", "SPSAMD_SOLVE_ROW", "SPSAMD_SOLVE_FUSE_ROWS", "SPSAMD_FACTOR_PATH", "SPSAMD_FACTOR_ROW", "SPSAMD_FACTOR_FUSE_ROWS", "SPSAMD_FACTOR_SERIAL_WORK", "SPSAMD_FACTOR_LDS_ROW", "SPSAMD_COLOR_PATH", "SPSAMD_COLOR_ROW", "SPSAMD_COLOR_FUSE_ROWS", "SPSAMD_COLOR_WAVE_DEG", "SPSAMD_AGG_PATH", "SPSAMD_AGG_ROW", "SPSAMD_AGG_FUSE_ROWS", "SPSAMD_AGG_WAVE_DEG", "SPSAMD_AGG_PER_ROWS", "SPSAMD_PCG_CHECK_EVERY", "SPSAMD_PCG_FUSE"};
 	static_assert(sizeof knobs / sizeof knobs[0] == sizeof envs / sizeof envs[0], "one environment variable per knob");
 	for (size_t k = 0; k < sizeof knobs / sizeof knobs[0]; ++k)
 		if (const char *e = getenv(envs[k])) (void)spsamd_ctx_set_tuning(c, knobs[k], atol(e));
@@ -78,6 +78,8 @@ extern "C" int spsamd_ctx_set_tuning(spsamd_ctx *c, const char *name, long value
 		{"factor_fuse_rows", &c->tune.factor_fuse_rows}, {"factor_serial_work", &c->tune.factor_serial_work},
 		{"factor_lds_row", &c->tune.factor_lds_row}, {"color_path", &c->tune.color_path}, {"color_row", &c->tune.color_row},
 		{"color_fuse_rows", &c->tune.color_fuse_rows}, {"color_wave_deg", &c->tune.color_wave_deg},
+		{"agg_path", &c->tune.agg_path}, {"agg_row", &c->tune.agg_row}, {"agg_fuse_rows", &c->tune.agg_fuse_rows},
+		{"agg_wave_deg", &c->tune.agg_wave_deg}, {"agg_per_rows", &c->tune.agg_per_rows},
 		{"pcg_check_every", &c->tune.pcg_check_every}, {"pcg_fuse", &c->tune.pcg_fuse},
 	};
 	for (auto &t : tab) if (!std::strcmp(t.n, name)) { *t.p = (int)value; return SPSAMD_OK; }
@@ -575,6 +577,20 @@ extern "C" int spsamd_color(spsamd_ctx *c, const spsamd_coo *A, char transpose, 
 		if (!A || !color || !out_ncolors) throw Error{SPSAMD_EINVAL, "null operand, color or out_ncolors"};
 		spsamd_result local;
 		return color_graph(c, A, transpose, order, seed, color_flags, color, perm, color_ptr, ptr_capacity, mem, out_ncolors,
+			stats, res ? res : &local);
+	)
+}
+
+// The MIS(2) aggregates of op(A)'s graph (k_aggregate.hip).  Workspace only, like spsamd_color.
+extern "C" int spsamd_aggregate(spsamd_ctx *c, const spsamd_coo *A, char transpose, int order, uint32_t seed, int agg_flags,
+	int32_t *agg, int32_t *members, int32_t *agg_ptr, size_t ptr_capacity, int mem, size_t *out_naggregates,
+	spsamd_aggregate_stats *stats, spsamd_result *res)
+{
+	if (!c) return SPSAMD_EINVAL;
+	API_GUARD(c,
+		if (!A || !agg || !out_naggregates) throw Error{SPSAMD_EINVAL, "null operand, agg or out_naggregates"};
+		spsamd_result local;
+		return aggregate_graph(c, A, transpose, order, seed, agg_flags, agg, members, agg_ptr, ptr_capacity, mem, out_naggregates,
 			stats, res ? res : &local);
 	)
 }

@@ -139,6 +139,33 @@ __device__ __forceinline__ uint32_t wave_claim(uint32_t *counter, bool pred)
 	return at + (uint32_t)__popcll(m & lanemask_lt());
 }
 
+// ---- the graph operations (k_color.hip, k_aggregate.hip) ------------------------------------------------------------
+
+// h(v) of the header: the visiting order of spsamd_color and spsamd_aggregate
+__device__ __forceinline__ uint32_t col_hash(uint32_t v, uint32_t seed)
+{
+	uint32_t h = v + seed * 0x9E3779B9u;
+	h ^= h >> 16; h *= 0x85EBCA6Bu; h ^= h >> 13; h *= 0xC2B2AE35u; h ^= h >> 16;
+	return h;
+}
+
+// first position of [b, e) whose neighbour is >= j
+__device__ __forceinline__ uint32_t col_lower_bound(const int32_t *adj, uint32_t b, uint32_t e, int32_t j)
+{
+	while (b < e) {
+		const uint32_t m = b + ((e - b) >> 1);
+		if (adj[m] < j) b = m + 1; else e = m;
+	}
+	return b;
+}
+
+__device__ __forceinline__ int32_t wave_reduce_max(int32_t v)
+{
+#pragma unroll
+	for (int d = 32; d >= 1; d >>= 1) v = max(v, __shfl_xor(v, d, 64));
+	return v;
+}
+
 // Index hash of the digest sink: one 64-bit multiply and a fold of (i, j).
 // Same arithmetic as orc_mix64 in the test oracle.
 __host__ __device__ __forceinline__ uint64_t mix64(uint32_t i, uint32_t j)

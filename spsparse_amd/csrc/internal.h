@@ -108,6 +108,11 @@ struct Tuning {
 	int color_row = 0;           // color: 0 by degree | 1 thread | 2 wave kernel for every vertex
 	int color_fuse_rows = 0;     // color: the widest worklist that still counts as thin (0: 1024)
 	int color_wave_deg = 0;      // color: the largest degree of a thread-class vertex (0: 16)
+	int agg_path = 0;            // aggregate: 0 the thin tail of the sweep fuses | 1 every round in launches of its own | 2 every round fuses, whatever its width
+	int agg_row = 0;             // aggregate: 0 by degree | 1 thread | 2 wave kernel for every vertex of degree >= 1
+	int agg_fuse_rows = 0;       // aggregate: the longest worklist that still counts as thin (0: 1024)
+	int agg_wave_deg = 0;        // aggregate: the largest degree of a thread-class vertex (0: 32)
+	int agg_per_rows = 0;        // aggregate: the shortest list whose thread kernels take four entries a thread (0: 1024 for every CU)
 	int pcg_check_every = 0;     // solve_pcg: iterations enqueued between two reads of the device state (0: 8)
 	int pcg_fuse = 0;            // solve_pcg: 0 dots fused into the kernels that produce their vectors | 1 every vector operation and every dot a launch of its own
 #ifdef SPSAMD_ABLATIONS
@@ -624,6 +629,32 @@ void factor_ilu0(spsamd_ctx *c, const spsamd_coo *A, char transpose, int duplica
 // or SPSAMD_ECAPACITY with *out_ncolors = the colours and the context's last error set (nothing written).
 int color_graph(spsamd_ctx *c, const spsamd_coo *A, char transpose, int order, uint32_t seed, int color_flags, int32_t *color,
 	int32_t *perm, int32_t *color_ptr, size_t ptr_capacity, int mem, size_t *out_ncolors, spsamd_color_stats *stats,
+	spsamd_result *res);
+
+// The two parts of the colouring that spsamd_aggregate runs too: one copy, in k_color.hip.
+// The graph of the key set K of an n x n operand as rows: K symmetrised, made unique and stripped of its diagonal, or
+// (`symmetric`) K's own rows, which may name the vertex itself.  Workspace memory, or K's and its handle's own arrays.
+struct GraphRows { const uint32_t *ptr; const int32_t *adj; };
+GraphRows graph_adjacency(spsamd_ctx *c, const MaskKeys &K, uint64_t N, bool symmetric);
+// Per vertex its degree (the row without the vertex itself); the worklists of round 0 by class (thread: deg <= wave_deg, or
+// what rowk says), their lengths in ctr[0] and ctr[1]; the totals in acc[GRAPH_*].  A vertex of degree 0 gets color 0 and
+// is on no list, or (`list_isolated`) color -1 and a place on the thread-class list; every other vertex gets color -1.
+enum { GRAPH_ADJ = 0, GRAPH_MAXDEG = 1, GRAPH_ROWS_T = 2, GRAPH_ROWS_W = 3, GRAPH_ACC = 4 };
+void graph_classes(spsamd_ctx *c, const GraphRows &g, uint64_t N, uint32_t *deg, int32_t *color, uint32_t *list_t, uint32_t *list_w,
+	uint32_t *ctr, unsigned long long *acc, uint32_t wave_deg, int rowk, int list_isolated);
+// The output tail: `sort` holds one key of key_bits bits per vertex; a stable sort, so the vertices come out ascending in
+// (key, index), into `list` (may be null; `kind` says where the caller's buffers live); under `bounds` the nbuckets + 1
+// bounds of the buckets key >> shift in that list, every one of which must occur, into workspace memory (returned) and
+// `list_ptr` (may be null).
+uint32_t *order_by_key(spsamd_ctx *c, PairSort &sort, uint64_t N, int key_bits, int shift, uint64_t nbuckets, bool bounds,
+	int32_t *list, int32_t *list_ptr, hipMemcpyKind kind);
+
+// ---------------------------------------------------------------- MIS(2) aggregation (k_aggregate.hip)
+
+// the aggregates of op(A)'s graph into the caller's buffers: spsamd_aggregate after its null checks.  Returns SPSAMD_OK,
+// or SPSAMD_ECAPACITY with *out_naggregates = the aggregates and the context's last error set (nothing written).
+int aggregate_graph(spsamd_ctx *c, const spsamd_coo *A, char transpose, int order, uint32_t seed, int agg_flags, int32_t *agg,
+	int32_t *members, int32_t *agg_ptr, size_t ptr_capacity, int mem, size_t *out_naggregates, spsamd_aggregate_stats *stats,
 	spsamd_result *res);
 
 // ---------------------------------------------------------------- element-wise product and pattern restriction (k_emult.hip)

@@ -36,7 +36,7 @@ constexpr uint32_t COL_WAVE_DEG = 16;                 // default of color_wave_d
 constexpr int COL_NT = SOLVE_NT;                      // threads of k_col_fused's one workgroup
 
 // acc[]: the counters of one call
-enum { COL_ADJ = 0, COL_MAXDEG = 1, COL_ROWS_T = 2, COL_ROWS_W = 3, COL_NCOLORS = 4, COL_CONFLICTS = 5, COL_FUSED = 6, COL_ACC = 8 };
+enum { COL_NCOLORS = GRAPH_ACC, COL_CONFLICTS = 5, COL_FUSED = 6, COL_ACC = 8 };   // (after graph_classes' four)
 
 struct ColArgs {
 	const uint32_t *ptr;                       // row pointer of the adjacency
@@ -51,13 +51,6 @@ struct ColArgs {
 	int directed;                              // the rows are taken on the caller's word (SPSAMD_COLOR_SYMMETRIC): see col_holds
 };
 
-__device__ __forceinline__ uint32_t col_hash(uint32_t v, uint32_t seed)
-{
-	uint32_t h = v + seed * 0x9E3779B9u;
-	h ^= h >> 16; h *= 0x85EBCA6Bu; h ^= h >> 13; h *= 0xC2B2AE35u; h ^= h >> 16;
-	return h;
-}
-
 __device__ __forceinline__ uint64_t col_key(const ColArgs &a, uint32_t v)
 {
 	return (a.by_degree ? (uint64_t)a.deg[v] << 32 : 0ull) | col_hash(v, a.seed);
@@ -71,27 +64,10 @@ __device__ __forceinline__ bool col_holds(const ColArgs &a, uint32_t u, uint64_t
 	return !a.directed || col_key(a, u) > kv;
 }
 
-// first position of [b, e) whose neighbour is >= j
-__device__ __forceinline__ uint32_t col_lower_bound(const int32_t *adj, uint32_t b, uint32_t e, int32_t j)
-{
-	while (b < e) {
-		const uint32_t m = b + ((e - b) >> 1);
-		if (adj[m] < j) b = m + 1; else e = m;
-	}
-	return b;
-}
-
 __device__ __forceinline__ uint64_t wave_reduce_or(uint64_t v)
 {
 #pragma unroll
 	for (int d = 32; d >= 1; d >>= 1) v |= (uint64_t)__shfl_xor((unsigned long long)v, d, 64);
-	return v;
-}
-
-__device__ __forceinline__ int32_t wave_reduce_max(int32_t v)
-{
-#pragma unroll
-	for (int d = 32; d >= 1; d >>= 1) v = max(v, __shfl_xor(v, d, 64));
 	return v;
 }
 
@@ -171,10 +147,10 @@ __global__ void __launch_bounds__(256) k_col_init(const uint32_t *__restrict__ p
 	tot = wave_reduce_sum<unsigned long long>(tot);
 	const int32_t wmd = wave_reduce_max((int32_t)std::min<uint32_t>(md, 0x7FFFFFFFu));
 	if (lane_id() == 0 && tot) {
-		atomicAdd(&acc[COL_ADJ], tot);
-		atomicMax(&acc[COL_MAXDEG], (unsigned long long)wmd);
-		if (n1) atomicAdd(&acc[COL_ROWS_T], (unsigned long long)n1);
-		if (n2) atomicAdd(&acc[COL_ROWS_W], (unsigned long long)n2);
+		atomicAdd(&acc[GRAPH_ADJ], tot);
+		atomicMax(&acc[GRAPH_MAXDEG], (unsigned long long)wmd);
+		if (n1) atomicAdd(&acc[GRAPH_ROWS_T], (unsigned long long)n1);
+		if (n2) atomicAdd(&acc[GRAPH_ROWS_W], (unsigned long long)n2);
 	}
 }
 
@@ -371,17 +347,84 @@ __global__ void __launch_bounds__(256) k_col_keys(const int32_t *__restrict__ co
 	if (v < n) keys[v] = (uint32_t)color[v];
 }
 
-// color_ptr out of the sorted colours: every colour below ncolors occurs (a vertex takes c only past holders of 0 .. c - 1)
-__global__ void __launch_bounds__(256) k_col_bounds(const uint64_t *__restrict__ keys, uint64_t n, uint64_t ncolors, uint32_t *__restrict__ cptr)
+// The bounds of the buckets key >> shift in the sorted keys: every bucket below nbuckets occurs (a vertex takes colour c only
+// past holders of 0 .. c - 1; every aggregate holds its root).
+__global__ void __launch_bounds__(256) k_col_bounds(const uint64_t *__restrict__ keys, uint64_t n, uint64_t nbuckets, int shift, uint32_t *__restrict__ cptr)
 {
 	const uint64_t p = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x;
 	if (p >= n) return;
-	const uint64_t k = keys[p];
-	if (p == 0 || keys[p - 1] != k) cptr[k] = (uint32_t)p;
-	if (p == n - 1) cptr[ncolors] = (uint32_t)n;
+	const uint64_t k = keys[p] >> shift;
+	if (k < nbuckets && (p == 0 || keys[p - 1] >> shift != k)) cptr[k] = (uint32_t)p;
+	if (p == n - 1) cptr[nbuckets] = (uint32_t)n;
 }
 
 // ---------------------------------------------------------------- host
+
+// The parts spsamd_aggregate runs too (k_aggregate.hip; declared in internal.h).
+
+GraphRows graph_adjacency(spsamd_ctx *c, const MaskKeys &K, uint64_t N, bool symmetric)
+{
+	hipStream_t st = c->stream;
+	const uint32_t *ptr;
+	const int32_t *adj;
+	if (symmetric) {
+		if (K.prep) { prepared_row_structure(c, K.prep); ptr = K.prep->rowptr; }
+		else {
+			ConMat m;
+			m.row = const_cast<int32_t *>(K.i); m.nnz = K.n; m.nrow = N;
+			ptr = dense_rowptr(c, m, 0);
+		}
+		adj = K.j;
+	} else {
+		ConMat m;
+		m.nrow = N;
+		if (K.n) {
+			const int bits = bits_of(N);
+			const uint64_t total = 2 * (uint64_t)K.n;                  // (< 2^32: K.n < 2^31)
+			PairSort sort(c, total);
+			k_col_sym_keys<<<dim3(grid_for(K.n)), dim3(256), 0, st>>>(K.i, K.j, K.n, bits, sort.keys);
+			SPS_LAUNCH_CHECK();
+			sort.run(2 * bits);
+			uint8_t *first = c->arena.get<uint8_t>(total);
+			uint32_t *off = c->arena.get<uint32_t>(total + 1);
+			k_col_first<<<dim3(grid_for(total)), dim3(256), 0, st>>>(sort.keys, total, bits, first);
+			SPS_LAUNCH_CHECK();
+			scan_exclusive_u8_u32(c, first, off, total);
+			const uint32_t nu = read_back(c, off + total);
+			if (nu) {
+				m.row = c->arena.get<int32_t>(nu); m.col = c->arena.get<int32_t>(nu); m.nnz = nu;
+				k_col_unique<<<dim3(grid_for(total)), dim3(256), 0, st>>>(sort.keys, first, off, total, bits, m.row, m.col);
+				SPS_LAUNCH_CHECK();
+			}
+		}
+		ptr = dense_rowptr(c, m, 0);
+		adj = m.col;
+	}
+	return GraphRows{ptr, adj};
+}
+
+void graph_classes(spsamd_ctx *c, const GraphRows &g, uint64_t N, uint32_t *deg, int32_t *color, uint32_t *list_t, uint32_t *list_w,
+	uint32_t *ctr, unsigned long long *acc, uint32_t wave_deg, int rowk, int list_isolated)
+{
+	k_col_init<<<dim3(grid_for(N, 256 * COL_INIT_PER)), dim3(256), 0, c->stream>>>(g.ptr, g.adj, N, deg, color, list_t, list_w, ctr, acc, wave_deg, rowk, list_isolated);
+	SPS_LAUNCH_CHECK();
+}
+
+uint32_t *order_by_key(spsamd_ctx *c, PairSort &sort, uint64_t N, int key_bits, int shift, uint64_t nbuckets, bool bounds,
+	int32_t *list, int32_t *list_ptr, hipMemcpyKind kind)
+{
+	hipStream_t st = c->stream;
+	sort.run(key_bits);
+	uint32_t *cptr = nullptr;
+	if (bounds) {
+		cptr = c->arena.get<uint32_t>(nbuckets + 1);
+		k_col_bounds<<<dim3(grid_for(N)), dim3(256), 0, st>>>(sort.keys, N, nbuckets, shift, cptr);
+		SPS_LAUNCH_CHECK();
+		if (list_ptr) SPS_HIP(hipMemcpyAsync(list_ptr, cptr, (nbuckets + 1) * sizeof(uint32_t), kind, st));
+	}
+	if (list) SPS_HIP(hipMemcpyAsync(list, sort.perm, N * sizeof(uint32_t), kind, st));
+	return cptr;
+}
 
 int color_graph(spsamd_ctx *c, const spsamd_coo *A, char transpose, int order, uint32_t seed, int color_flags, int32_t *color,
 	int32_t *perm, int32_t *color_ptr, size_t ptr_capacity, int mem, size_t *out_ncolors, spsamd_color_stats *stats,
@@ -435,41 +478,9 @@ int color_graph(spsamd_ctx *c, const spsamd_coo *A, char transpose, int order, u
 	}
 
 	// ---- adjacency
-	const uint32_t *ptr;
-	const int32_t *adj;
-	if (symmetric) {
-		if (K.prep) { prepared_row_structure(c, K.prep); ptr = K.prep->rowptr; }
-		else {
-			ConMat m;
-			m.row = const_cast<int32_t *>(K.i); m.nnz = K.n; m.nrow = N;
-			ptr = dense_rowptr(c, m, 0);
-		}
-		adj = K.j;
-	} else {
-		ConMat m;
-		m.nrow = N;
-		if (K.n) {
-			const int bits = bits_of(N);
-			const uint64_t total = 2 * (uint64_t)K.n;                  // (< 2^32: K.n < 2^31)
-			PairSort sort(c, total);
-			k_col_sym_keys<<<dim3(grid_for(K.n)), dim3(256), 0, st>>>(K.i, K.j, K.n, bits, sort.keys);
-			SPS_LAUNCH_CHECK();
-			sort.run(2 * bits);
-			uint8_t *first = c->arena.get<uint8_t>(total);
-			uint32_t *off = c->arena.get<uint32_t>(total + 1);
-			k_col_first<<<dim3(grid_for(total)), dim3(256), 0, st>>>(sort.keys, total, bits, first);
-			SPS_LAUNCH_CHECK();
-			scan_exclusive_u8_u32(c, first, off, total);
-			const uint32_t nu = read_back(c, off + total);
-			if (nu) {
-				m.row = c->arena.get<int32_t>(nu); m.col = c->arena.get<int32_t>(nu); m.nnz = nu;
-				k_col_unique<<<dim3(grid_for(total)), dim3(256), 0, st>>>(sort.keys, first, off, total, bits, m.row, m.col);
-				SPS_LAUNCH_CHECK();
-			}
-		}
-		ptr = dense_rowptr(c, m, 0);
-		adj = m.col;
-	}
+	const GraphRows g = graph_adjacency(c, K, N, symmetric);
+	const uint32_t *ptr = g.ptr;
+	const int32_t *adj = g.adj;
 	const int path = c->tune.color_path == 1 || c->tune.color_path == 2 ? c->tune.color_path : 0;
 	const int rowk = c->tune.color_row == 1 || c->tune.color_row == 2 ? c->tune.color_row : 0;
 	const uint32_t fuse_rows = c->tune.color_fuse_rows > 0 ? (uint32_t)c->tune.color_fuse_rows : COL_FUSE_ROWS;
@@ -481,8 +492,7 @@ int color_graph(spsamd_ctx *c, const spsamd_coo *A, char transpose, int order, u
 	uint32_t *wait = get_zeroed<uint32_t>(c, N);
 	uint32_t *list_t[2] = {c->arena.get<uint32_t>(N), c->arena.get<uint32_t>(N)};
 	uint32_t *list_w[2] = {c->arena.get<uint32_t>(N), c->arena.get<uint32_t>(N)};
-	k_col_init<<<dim3(grid_for(N, 256 * COL_INIT_PER)), dim3(256), 0, st>>>(ptr, adj, N, deg, col, list_t[0], list_w[0], ctr, acc, wave_deg, rowk, symmetric);
-	SPS_LAUNCH_CHECK();
+	graph_classes(c, g, N, deg, col, list_t[0], list_w[0], ctr, acc, wave_deg, rowk, symmetric);
 	uint32_t *h = (uint32_t *)c->host_staging(COL_ACC * sizeof(unsigned long long));
 	auto read_counts = [&](int par, uint32_t *cnt_t, uint32_t *cnt_w) {
 		SPS_HIP(hipMemcpyAsync(h, ctr + 2 * par, 2 * sizeof(uint32_t), hipMemcpyDeviceToHost, st));
@@ -534,14 +544,7 @@ int color_graph(spsamd_ctx *c, const spsamd_coo *A, char transpose, int order, u
 		PairSort sort(c, N);
 		k_col_keys<<<dim3(grid_for(N)), dim3(256), 0, st>>>(col, N, sort.keys);
 		SPS_LAUNCH_CHECK();
-		sort.run(bits_of(ncolors));                                    // stable: ascending index inside a colour
-		if (color_ptr) {
-			uint32_t *cptr = c->arena.get<uint32_t>(ncolors + 1);
-			k_col_bounds<<<dim3(grid_for(N)), dim3(256), 0, st>>>(sort.keys, N, ncolors, cptr);
-			SPS_LAUNCH_CHECK();
-			SPS_HIP(hipMemcpyAsync(color_ptr, cptr, (ncolors + 1) * sizeof(uint32_t), kind, st));
-		}
-		if (perm) SPS_HIP(hipMemcpyAsync(perm, sort.perm, N * sizeof(uint32_t), kind, st));
+		order_by_key(c, sort, N, bits_of(ncolors), 0, ncolors, color_ptr != nullptr, perm, color_ptr, kind);   // stable: ascending index inside a colour
 	}
 	SPS_HIP(hipMemcpyAsync(color, col, N * sizeof(int32_t), kind, st));
 	finish_call(c, res);
@@ -550,9 +553,9 @@ int color_graph(spsamd_ctx *c, const spsamd_coo *A, char transpose, int order, u
 	SPS_HIP(hipEventElapsedTime(&res->ms_numeric, c->ev[EV_SYMBOLIC], c->ev[EV_END]));
 	if (stats) {
 		stats->ncolors = ncolors; stats->rounds = rounds;
-		stats->adjacency = hacc[COL_ADJ]; stats->max_degree = hacc[COL_MAXDEG]; stats->conflicts = hacc[COL_CONFLICTS];
+		stats->adjacency = hacc[GRAPH_ADJ]; stats->max_degree = hacc[GRAPH_MAXDEG]; stats->conflicts = hacc[COL_CONFLICTS];
 		stats->launches = launches; stats->fused_rounds = fused_rounds;
-		stats->rows_thread = hacc[COL_ROWS_T]; stats->rows_wave = hacc[COL_ROWS_W];
+		stats->rows_thread = hacc[GRAPH_ROWS_T]; stats->rows_wave = hacc[GRAPH_ROWS_W];
 		stats->ms_adjacency = res->ms_symbolic; stats->ms_color = res->ms_numeric;
 	}
 	return SPSAMD_OK;
