@@ -247,6 +247,10 @@ const char *spsamd_version(void);
  *                                     section 23)
  *   pcg_fuse        1                 solve_pcg: every vector operation and every dot product in a launch of its own
  *                                     (default: a dot's first level rides in the kernel that produces its vector)
+ *   amg_path        1 | 2             amg_apply, solve_pcg_amg: 1 every level of the cycle in launches of its own | 2 the whole
+ *                                     hierarchy in the one launch of the fused tail, whatever its levels' orders (default: the
+ *                                     levels from the first one on from which none has more than amg_fuse_rows rows)
+ *   amg_fuse_rows   > 0               amg_apply, solve_pcg_amg: the largest order of a level of the fused tail (1024)
  * The environment variables of the same purpose (SPSAMD_W ...) are read once, inside spsamd_ctx_create; nothing reads
  * the environment later.  Unknown names: SPSAMD_EINVAL. */
 int spsamd_ctx_set_tuning(spsamd_ctx *ctx, const char *name, long value);
@@ -921,6 +925,86 @@ int spsamd_solve_pcg(spsamd_ctx *ctx, const spsamd_coo *A, char transpose,
 	double *hist_host /* may be NULL */, size_t hist_capacity,
 	int duplicate_policy, int zero_nan,
 	spsamd_pcg_stats *stats /* may be NULL */, spsamd_result *result /* may be NULL */);
+
+/*
+ * One multigrid V-cycle over a hierarchy of the caller's, on the device, and spsamd_solve_pcg's loop with that cycle as its
+ * preconditioner.  The set-up pieces are public calls of their own: spsamd_aggregate and its
+ * tentative prolongator P, the Galerkin operator P^T (A P) by two spsamd_multiply calls; a smoothed P comes from
+ * spsamd_add, spsamd_reduce and spsamd_multiply and goes through here unchanged.
+ *   - Levels.  levels[l], l = 0 .. nlevels - 1 (1 <= nlevels <= 32), holds the level operator op(A_l), n_l x n_l, and below
+ *     the last level the prolongation op(P_l), n_l x n_{l+1}, and the restriction op(R_l), n_{l+1} x n_l; on the last level
+ *     P and R are NULL.  P and R are separate operands: the tentative prolongator is passed twice, as P with '.' and as R
+ *     with 'T'.  The cycle is defined for any operands of these shapes.  A SYMMETRIC preconditioner -- what conjugate
+ *     gradients need -- is the caller's responsibility: R_l = P_l^T and pre == post.
+ *   - Every operand is taken exactly as spsamd_solve_pcg takes A, duplicate_policy and zero_nan included: a raw operand is
+ *     consolidated by op()'s rows, an operand whose sort0 names op()'s row order is trusted, a SINK_COO result of this
+ *     context and a prepared handle of the same transpose are read in place.  Call the sequences S_l, P_l, R_l.  The call
+ *     keeps nothing: prepared handles make the intake free.  Neither output set of the context is written.
+ *   - Every returned bit is defined by this loop.  Products, sums and divisions are each rounded once, with no FMA; a NaN
+ *     result carries the bits x86-64 gives it (the rules of spsamd_solve_pcg above).
+ *       d_l            = the DIAG fold of spsamd_reduce over S_l (+0.0 without a diagonal tuple)
+ *       apply(X, v)_i  = acc after  acc = +0.0;  acc = acc + val * v_j  over row i's tuples (i, j, val) of X in X's order
+ *       smooth0(l, b)  : x_i = omega * (b_i / d_i)
+ *       smooth(l, b, x): q = apply(S_l, x);  x'_i = x_i + omega * ((b_i - q_i) / d_i)    for all i from the old x (Jacobi)
+ *
+ *       cycle(l, b):
+ *           if l == nlevels - 1:
+ *               x = +0.0;  sweep s = 0 .. coarse-1:  x = (s == 0 ? smooth0(l, b) : smooth(l, b, x));  return x
+ *           x = +0.0;      sweep s = 0 .. pre-1:     x = (s == 0 ? smooth0(l, b) : smooth(l, b, x))
+ *           r = (pre == 0 ? b : b - apply(S_l, x))                   (r_i = b_i - q_i)
+ *           e = cycle(l + 1, apply(R_l, r))
+ *           x_i = x_i + apply(P_l, e)_i
+ *           sweep s = 0 .. post-1:  x = smooth(l, b, x)
+ *           return x
+ *     Nothing is checked for a zero or a missing diagonal: the infinities and NaNs go where IEEE sends them (and the loop of
+ *     conjugate gradients then stops with BREAKDOWN).  A level below the first may have order 0: the correction of the level
+ *     above is then a vector of +0.0 (which is still added: a -0.0 becomes +0.0).
+ *   - spsamd_amg_apply:  x = cycle(0, b).  b and x are n_0 doubles in `mem` (SPSAMD_MEM_HOST or SPSAMD_MEM_DEVICE, for both);
+ *     x is written only.
+ *   - spsamd_solve_pcg_amg: the loop of spsamd_solve_pcg's header with A = levels[0].A (and its transpose flag) and
+ *     z = cycle(0, r): the same fold, stop reasons, hist, stats, and the same meaning of pcg_check_every and pcg_fuse.
+ *   - The levels from the first one on from which no level has more than amg_fuse_rows rows (knob, default 1024) are the
+ *     fused tail: one launch of one workgroup walks them down and up.  amg_path = 1 turns the tail off, amg_path = 2 makes
+ *     the whole hierarchy the tail.  Rows above spmm_long_min of a level outside the tail go to the wave kernel of
+ *     spsamd_multiply_dense.  Every row is one serial chain in the operand's order on every path: no knob changes a
+ *     returned bit.  Nothing is allocated inside a cycle; workspace_bytes does not depend on the iteration count.
+ * amg_stats (may be NULL): see the struct.  result (may be NULL): as spsamd_solve_pcg fills it (nnz_a = |S_0|, nnz_b = 0);
+ * for spsamd_amg_apply shape0 = shape1 = n_0, nnz_a = |S_0|, ms_symbolic (the intake and set-up), ms_numeric (the cycle),
+ * ms_total, workspace_bytes.
+ * SPSAMD_EINVAL, with a message and x untouched: levels, params or a level's A NULL; b or x NULL while n_0 > 0; nlevels
+ * outside 1 .. 32; P or R missing below the last level, or present on it; omega not finite; and, applied to every operand,
+ * the overlap, mem, policy, tol and 2^31 rules of spsamd_solve_pcg.  SPSAMD_EDIM: a level operator that is not square, or
+ * P / R shapes that do not chain n_l -> n_{l+1}.  n_0 == 0 returns as spsamd_solve_pcg does.  Returns when x is complete.
+ */
+typedef struct {
+	const spsamd_coo *A; char transpose_A;   /* level operator, op(A_l): n_l x n_l                              */
+	const spsamd_coo *P; char transpose_P;   /* prolongation,  op(P_l): n_l x n_{l+1};  NULL on the last level  */
+	const spsamd_coo *R; char transpose_R;   /* restriction,   op(R_l): n_{l+1} x n_l;  NULL on the last level  */
+} spsamd_amg_level;
+
+typedef struct { uint32_t pre, post, coarse; double omega; } spsamd_amg_params;
+
+typedef struct {
+	uint32_t levels;              /* nlevels */
+	uint32_t fused_levels;        /* levels served inside the fused tail */
+	uint64_t launches_per_cycle;  /* kernel launches (and fills) one cycle enqueues */
+	uint64_t rows[32], nnz[32];   /* n_l and |S_l| */
+	double operator_complexity;   /* sum of |S_l| over |S_0| (0 where S_0 is empty) */
+	uint64_t long_rows;           /* rows sent to the wave kernel, over the operands of all levels outside the tail */
+	float ms_setup, ms_cycle;     /* spsamd_amg_apply only */
+} spsamd_amg_stats;
+
+int spsamd_amg_apply(spsamd_ctx *ctx, const spsamd_amg_level *levels, size_t nlevels, const spsamd_amg_params *params,
+	const double *b, double *x /* out */, int mem, int duplicate_policy, int zero_nan,
+	spsamd_amg_stats *amg_stats /* may be NULL */, spsamd_result *result /* may be NULL */);
+
+int spsamd_solve_pcg_amg(spsamd_ctx *ctx, const spsamd_amg_level *levels, size_t nlevels, const spsamd_amg_params *params,
+	const double *b, double *x /* in: x0, out: the iterate at the stop */, int mem,
+	double tol, uint64_t max_iter,
+	double *hist_host /* may be NULL */, size_t hist_capacity,
+	int duplicate_policy, int zero_nan,
+	spsamd_pcg_stats *stats /* may be NULL */, spsamd_amg_stats *amg_stats /* may be NULL */,
+	spsamd_result *result /* may be NULL */);
 
 /*
  * ret = (C * diag(scalei) * op(A) * diag(scalej) * op(B) * diag(scalek)) restricted to the keys of M  -- a masked product

@@ -58,6 +58,8 @@ agg_fuse_rows, agg_wave_deg = 1024, 32
 PRECOND_NONE, PRECOND_JACOBI, PRECOND_LU = 0, 1, 2
 PCG_CONVERGED, PCG_MAXITER, PCG_BREAKDOWN = 0, 1, 2
 pcg_check_every, pcg_chunk = 8, 1024
+# amg_apply, solve_pcg_amg: the default of the amg_fuse_rows knob and the most levels of a hierarchy
+amg_fuse_rows, amg_max_levels = 1024, 32
 
 ERRORS = {-1: "EDIM", -2: "EINVAL", -3: "EHIP", -4: "ENOMEM", -5: "ECAPACITY", -6: "ENODEVICE", -7: "EPEER"}
 
@@ -135,6 +137,22 @@ class PcgStats(C.Structure):
                 ("ms_setup", C.c_float), ("ms_iterate", C.c_float)]
 
 
+class AmgLevel(C.Structure):
+    """spsamd_amg_level: op(A_l), and below the last level op(P_l) and op(R_l) (pointers to Coo structs the caller keeps alive)."""
+    _fields_ = [("A", C.POINTER(Coo)), ("transpose_A", C.c_char), ("P", C.POINTER(Coo)), ("transpose_P", C.c_char),
+                ("R", C.POINTER(Coo)), ("transpose_R", C.c_char)]
+
+
+class AmgParams(C.Structure):
+    _fields_ = [("pre", C.c_uint32), ("post", C.c_uint32), ("coarse", C.c_uint32), ("omega", C.c_double)]
+
+
+class AmgStats(C.Structure):
+    _fields_ = [("levels", C.c_uint32), ("fused_levels", C.c_uint32), ("launches_per_cycle", C.c_uint64),
+                ("rows", C.c_uint64 * 32), ("nnz", C.c_uint64 * 32), ("operator_complexity", C.c_double),
+                ("long_rows", C.c_uint64), ("ms_setup", C.c_float), ("ms_cycle", C.c_float)]
+
+
 class DistStats(C.Structure):
     _fields_ = [("block_nnz_a", C.c_uint64), ("panel_tuples", C.c_uint64), ("remote_tuples", C.c_uint64),
                 ("sent_tuples", C.c_uint64), ("ms_exchange", C.c_float), ("pad_", C.c_float)]
@@ -155,7 +173,8 @@ SYMBOLS = ["spsamd_ctx_create", "spsamd_ctx_destroy", "spsamd_last_error", "spsa
            "spsamd_operand_prepare", "spsamd_operand_as_coo", "spsamd_operand_bytes", "spsamd_operand_destroy",
            "spsamd_multiply_dense", "spsamd_add", "spsamd_multiply_stream", "spsamd_multiply_masked",
            "spsamd_multiply_sampled", "spsamd_select", "spsamd_extract", "spsamd_reduce", "spsamd_emult", "spsamd_solve_tri",
-           "spsamd_factor_ilu0", "spsamd_color", "spsamd_solve_pcg", "spsamd_aggregate"]
+           "spsamd_factor_ilu0", "spsamd_color", "spsamd_solve_pcg", "spsamd_aggregate",
+           "spsamd_amg_apply", "spsamd_solve_pcg_amg"]
 
 _lib = None
 
@@ -221,6 +240,11 @@ def load():
                                    C.c_size_t, C.c_int, P(C.c_size_t), P(AggregateStats), P(Result)]
     L.spsamd_solve_pcg.argtypes = [C.c_void_p, P(Coo), C.c_char, C.c_int, P(Coo), C.c_char, C.c_void_p, C.c_void_p, C.c_int,
                                    C.c_double, C.c_uint64, C.c_void_p, C.c_size_t, C.c_int, C.c_int, P(PcgStats), P(Result)]
+    L.spsamd_amg_apply.argtypes = [C.c_void_p, P(AmgLevel), C.c_size_t, P(AmgParams), C.c_void_p, C.c_void_p, C.c_int,
+                                   C.c_int, C.c_int, P(AmgStats), P(Result)]
+    L.spsamd_solve_pcg_amg.argtypes = [C.c_void_p, P(AmgLevel), C.c_size_t, P(AmgParams), C.c_void_p, C.c_void_p, C.c_int,
+                                       C.c_double, C.c_uint64, C.c_void_p, C.c_size_t, C.c_int, C.c_int, P(PcgStats),
+                                       P(AmgStats), P(Result)]
     L.spsamd_memcpy.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_size_t]
     L.spsamd_consolidate.argtypes = [C.c_void_p, P(Coo), C.c_int, C.c_int, C.c_int, P(Result)]
     L.spsamd_sorted_permutation.argtypes = [C.c_void_p, P(Coo), C.c_int, C.c_void_p]
@@ -687,6 +711,57 @@ class Context:
                                             int(zero_nan), C.byref(st), None if result is None else C.byref(result)))
         return x, hist[:min(int(st.iterations) + 1, cap)].copy(), st
 
+    def _amg_args(self, levels, params, b, x, zero_x):
+        """The level table, the parameters and the two vectors of amg_apply / solve_pcg_amg as the C ABI takes them."""
+        levels = levels.levels if isinstance(levels, Hierarchy) else list(levels)
+        arr = (AmgLevel * max(len(levels), 1))()
+        for l, lv in enumerate(levels):
+            A, tA, Pm, tP, Rm, tR = amg_level(*lv) if isinstance(lv, (tuple, list)) else lv
+            arr[l] = AmgLevel(C.pointer(A), tA.encode(), None if Pm is None else C.pointer(Pm), tP.encode(),
+                              None if Rm is None else C.pointer(Rm), tR.encode())
+        prm = params if isinstance(params, AmgParams) else AmgParams(*params)
+        pb, _ldb, nb, mb = _dense_arg(b, "b", writable=False)
+        if x is None:
+            if mb == MEM_HOST:
+                x = np.zeros(b.shape, dtype=np.float64) if zero_x else np.empty(b.shape, dtype=np.float64)
+            else:
+                import torch
+                x = torch.zeros(tuple(b.shape), dtype=torch.float64, device=b.device)
+        px, _ldx, nx, mx = _dense_arg(x, "x", writable=True)
+        if mx != mb:
+            raise ValueError("b and x must both be host (numpy) or both device (torch) arrays")
+        if b.ndim != 1 or x.ndim != 1 or nb != 1 or nx != 1 or _rows(b) != _rows(x):
+            raise ValueError("b and x must be 1-D arrays of one length")
+        if _rows(b) > 1 and (_ldb != 1 or _ldx != 1):
+            raise ValueError("b and x must be contiguous")
+        return arr, len(levels), prm, pb, px, mb, x, levels
+
+    def amg_apply(self, levels, params, b, x=None, duplicate_policy=ADD, zero_nan=False, result=None):
+        """spsamd_amg_apply: x = cycle(0, b), one multigrid cycle over `levels`, bit for bit the loop of the header.
+        levels: a Hierarchy, or a list with one entry per level, each (A, P, R) or (A, tA, P, tP, R, tR) of Coo structs and
+        transpose flags (P and R None on the last level; (A, P) passes P again as R with 'T').  params: an AmgParams or
+        (pre, post, coarse, omega).  b, x: 1-D contiguous float64 numpy arrays or device torch tensors of n_0 values (x
+        allocated when None).  Returns (x, AmgStats).  result: a capi.Result to fill (timings)."""
+        arr, nl, prm, pb, px, mem, x, _keep = self._amg_args(levels, params, b, x, False)
+        st = AmgStats()
+        self._check(self.L.spsamd_amg_apply(self.h, arr, nl, C.byref(prm), pb, px, mem, duplicate_policy, int(zero_nan),
+                                            C.byref(st), None if result is None else C.byref(result)))
+        return x, st
+
+    def solve_pcg_amg(self, levels, params, b, x=None, tol=1e-8, max_iter=1000, hist_capacity=None, duplicate_policy=ADD,
+                      zero_nan=False, result=None):
+        """spsamd_solve_pcg_amg: levels[0].A x = b by the loop of solve_pcg with z = cycle(0, r).  levels, params, b, x: as
+        for amg_apply; x holds x0 and receives the iterate at the stop (None: a zero start).  Returns (x, hist, PcgStats,
+        AmgStats) with hist as solve_pcg returns it."""
+        arr, nl, prm, pb, px, mem, x, _keep = self._amg_args(levels, params, b, x, True)
+        cap = int(max_iter) + 1 if hist_capacity is None else int(hist_capacity)
+        hist = np.empty(max(cap, 1), np.float64)
+        st, ast = PcgStats(), AmgStats()
+        self._check(self.L.spsamd_solve_pcg_amg(self.h, arr, nl, C.byref(prm), pb, px, mem, float(tol), int(max_iter),
+                                                hist.ctypes.data if cap else None, cap, duplicate_policy, int(zero_nan),
+                                                C.byref(st), C.byref(ast), None if result is None else C.byref(result)))
+        return x, hist[:min(int(st.iterations) + 1, cap)].copy(), st, ast
+
     def multiply_sampled(self, M, P, Q, out=None, transpose='.', alpha=1.0, beta=0.0):
         """spsamd_multiply_sampled: out[t] = alpha * (P[i] . Q[j]) (+ beta * v) for every tuple t = (i, j, v) of op(M) in
         storage order, the k terms of each summed serially in ascending order, bit for bit.  M: a Coo struct.  P, Q: 2-D
@@ -831,6 +906,85 @@ class Operand:
         if self.h:
             self.ctx.L.spsamd_operand_destroy(self.h)
             self.h = None
+
+
+def amg_level(A, *rest):
+    """One level as (A, tA, P, tP, R, tR) from (A,), (A, P), (A, P, R) or the six values themselves: flags default to '.',
+    and a P without R is passed again as R with 'T' (the tentative prolongator's use)."""
+    if len(rest) == 5:
+        return (A,) + tuple(rest)
+    Pm = rest[0] if len(rest) > 0 else None
+    Rm = rest[1] if len(rest) > 1 else None
+    if Pm is not None and Rm is None:
+        return A, '.', Pm, '.', Pm, 'T'
+    return A, '.', Pm, '.', Rm, '.'
+
+
+class Hierarchy:
+    """An unsmoothed-aggregation hierarchy built from public calls only, as prepared operands: per level
+    Context.aggregate -> prolongator -> the Galerkin operator P^T (A P) by two Context.multiply calls into SINK_COO, each
+    product copied out to device tensors; A and P are prepared with '.', P again with 'T' (the restriction).  It stops at
+    max_levels or at a level of at most min_coarse rows.  `levels` is what Context.amg_apply / solve_pcg_amg take;
+    `seconds` splits the set-up into aggregate, products and prepare (host wall time, each stage synchronised).  A: a Coo
+    struct whose tuples are on the device (a device_coo, or a chained result), square.  close() destroys the handles."""
+
+    def __init__(self, ctx, A, order=AGG_ORDER_HASH, seed=0, flags=0, max_levels=amg_max_levels, min_coarse=64):
+        import time
+        import torch
+        self.ctx, self.levels, self.operands, self.keep = ctx, [], [], []
+        self.seconds = {"aggregate": 0.0, "products": 0.0, "prepare": 0.0}
+        self.rows, self.nnz = [], []
+
+        def timed(key, fn):
+            torch.cuda.synchronize()
+            t0 = time.perf_counter()
+            out = fn()
+            torch.cuda.synchronize()
+            self.seconds[key] += time.perf_counter() - t0
+            return out
+
+        def prepared(X, tr):
+            op = timed("prepare", lambda: Operand(ctx, X, tr, AS_A | AS_B))
+            self.operands.append(op)
+            return op.coo
+
+        def copied(res):
+            i = torch.empty(max(int(res.nnz), 1), dtype=torch.int32, device="cuda")
+            j, v = torch.empty_like(i), torch.empty(max(int(res.nnz), 1), dtype=torch.float64, device="cuda")
+            for dst, src, w in ((i, res.idx0, 4), (j, res.idx1, 4), (v, res.val, 8)):
+                if res.nnz:
+                    ctx.memcpy(dst.data_ptr(), src, int(res.nnz) * w)
+            self.keep.append((i, j, v))
+            return device_coo(i.data_ptr(), j.data_ptr(), v.data_ptr(), int(res.nnz), (int(res.shape0), int(res.shape1)), 0)
+
+        try:
+            cur = A
+            while True:
+                n = int(cur.shape0)
+                Ap = prepared(cur, '.')
+                self.rows.append(n)
+                self.nnz.append(int(cur.nnz))
+                if len(self.levels) + 1 >= max_levels or n <= min_coarse:
+                    self.levels.append((Ap, '.', None, '.', None, '.'))
+                    break
+                agg = torch.empty(max(n, 1), dtype=torch.int32, device="cuda")
+                nagg = timed("aggregate", lambda: ctx.aggregate(cur, order=order, seed=seed, flags=flags, out=(agg, None, None)))
+                if nagg >= n:                                   # no coarsening (no off-diagonal tuple left): this is the last level
+                    self.levels.append((Ap, '.', None, '.', None, '.'))
+                    break
+                Pc, keep = prolongator(agg[:n], nagg, device=True)
+                self.keep.append(keep)
+                AP = copied(timed("products", lambda: ctx.multiply(cur, Pc)))
+                cur = copied(timed("products", lambda: ctx.multiply(Pc, AP, tA='T')))
+                self.levels.append((Ap, '.', prepared(Pc, '.'), '.', prepared(Pc, 'T'), 'T'))
+        except Exception:
+            self.close()
+            raise
+
+    def close(self):
+        for op in self.operands:
+            op.close()
+        self.operands, self.levels, self.keep = [], [], []
 
 
 class Dist:

@@ -115,6 +115,8 @@ struct Tuning {
 	int agg_per_rows = 0;        // aggregate: the shortest list whose thread kernels take four entries a thread (0: 1024 for every CU)
 	int pcg_check_every = 0;     // solve_pcg: iterations enqueued between two reads of the device state (0: 8)
 	int pcg_fuse = 0;            // solve_pcg: 0 dots fused into the kernels that produce their vectors | 1 every vector operation and every dot a launch of its own
+	int amg_path = 0;            // amg cycle: 0 the thin tail of the hierarchy is one launch | 1 every level in launches of its own | 2 the whole hierarchy is the tail, whatever its levels' orders
+	int amg_fuse_rows = 0;       // amg cycle: the largest order of a level that still counts as thin (0: 1024)
 #ifdef SPSAMD_ABLATIONS
 	int dbg = 0;
 #endif
@@ -616,6 +618,49 @@ int solve_pcg(spsamd_ctx *c, const spsamd_coo *A, char transpose, int precond, c
 	const double *b, double *x, int mem, double tol, uint64_t max_iter, double *hist_host, size_t hist_capacity,
 	int duplicate_policy, int zero_nan, spsamd_pcg_stats *stats, spsamd_result *res);
 constexpr int PCG_CHECK_EVERY = 8;             // default of the pcg_check_every knob: the measured sweep is flat from 4 on, and 8 bounds the work after the stop
+
+// An operand taken by consolidate_operand with what its serial chains need: S for the loop's SpMV, and every level operand
+// of the multigrid cycle (k_amg.hip)
+struct RowOperator {
+	const uint32_t *ptr = nullptr;   // dense row pointer, nrow + 1 entries
+	const int32_t *col = nullptr;
+	const double *val = nullptr;
+	uint64_t nrow = 0, ncol = 0;
+	uint32_t nnz = 0;
+	uint32_t long_min = 0xFFFFFFFFu; // rows of more tuples go to the wave kernel of k_spmm.hip
+	uint32_t nlong = 0;              // how many there are; then: their list and its length on the device, the packed tuples in m
+	const uint32_t *list = nullptr, *count = nullptr;
+	DenseOperand m;
+};
+// S's row pointer; under `long_rows` the long rows' list and the packed rows of k_spmm.hip where there is a long row
+void row_operator(spsamd_ctx *c, ConMat &S, Prepared *hp, uint64_t nrow, uint64_t ncol, bool long_rows, RowOperator *out);
+// SPSAMD_EINVAL where X has 2^31 or more tuples or the vector x overlaps one of its arrays
+void check_vector_overlap(spsamd_ctx *c, const spsamd_coo *X, const char *name, const double *x, uint64_t bytes);
+
+// The preconditioner step of the loop as a hook.  setup() runs once, after S is taken and the loop's vectors exist: it
+// takes everything it needs out of the workspace then.  apply() enqueues z = M^-1 r on those two vectors and returns the
+// launches it issued; it allocates nothing, reads no PcgState and writes nothing but its own scratch and z.
+struct PcgPrecond {
+	virtual void setup(spsamd_ctx *c, const RowOperator &S, const double *r, double *z) = 0;
+	virtual uint64_t apply() = 0;
+	virtual ~PcgPrecond() {}
+};
+constexpr int PCG_PRECOND_HOOK = 3;            // pcg_solve's precond under a hook (never a value of the public ABI)
+int pcg_solve(spsamd_ctx *c, const spsamd_coo *A, char transpose, int precond, const spsamd_coo *M, char transpose_M,
+	const double *b, double *x, int mem, double tol, uint64_t max_iter, double *hist_host, size_t hist_capacity,
+	int duplicate_policy, int zero_nan, spsamd_pcg_stats *stats, spsamd_result *res, PcgPrecond *hook);
+
+// ---------------------------------------------------------------- aggregation multigrid cycle (k_amg.hip)
+
+// x = cycle(0, b): spsamd_amg_apply after the context check
+int amg_apply(spsamd_ctx *c, const spsamd_amg_level *levels, size_t nlevels, const spsamd_amg_params *params, const double *b,
+	double *x, int mem, int duplicate_policy, int zero_nan, spsamd_amg_stats *stats, spsamd_result *res);
+// the loop of solve_pcg with z = cycle(0, r): spsamd_solve_pcg_amg after the context check
+int solve_pcg_amg(spsamd_ctx *c, const spsamd_amg_level *levels, size_t nlevels, const spsamd_amg_params *params, const double *b,
+	double *x, int mem, double tol, uint64_t max_iter, double *hist_host, size_t hist_capacity, int duplicate_policy, int zero_nan,
+	spsamd_pcg_stats *stats, spsamd_amg_stats *astats, spsamd_result *res);
+constexpr uint32_t AMG_FUSE_ROWS = 1024;       // default of the amg_fuse_rows knob
+constexpr int AMG_MAX_LEVELS = 32;
 
 // ---------------------------------------------------------------- ILU(0) factorisation (k_factor.hip)
 

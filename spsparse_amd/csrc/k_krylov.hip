@@ -20,6 +20,9 @@
 // state first and does nothing unless it is RUNNING.  q and z are scratch of the loop and may be overwritten after the stop
 // (k_spmm.hip and k_solve.hip know nothing of the state); nothing returned depends on them.  No kernel reads what another
 // workgroup wrote in the same launch: every dependency between workgroups is a kernel boundary.
+//
+// The preconditioner step is also a hook (PcgPrecond, internal.h): spsamd_solve_pcg_amg runs this loop with the multigrid
+// cycle of k_amg.hip as z = M^-1 r, under the rule of the solves -- it writes its own scratch and z, and reads no state.
 #include "internal.h"
 #include "devutil.h"
 #include "x86fp.h"
@@ -276,21 +279,10 @@ struct Pcg {
 	}
 };
 
-// S with what the SpMV needs
-struct PcgOperator {
-	const uint32_t *ptr = nullptr;
-	const int32_t *col = nullptr;
-	const double *val = nullptr;
-	uint32_t long_min = 0xFFFFFFFFu; // rows of more tuples go to the wave kernel of k_spmm.hip
-	uint32_t nlong = 0;              // how many there are; then: their list and its length on the device, S's packed tuples in m
-	const uint32_t *list = nullptr, *count = nullptr;
-	DenseOperand m;
-};
-
 } // namespace
 
 // q = S in (+ the partials of dot(in, q) where `dot`).  Nothing is allocated here: it runs once per iteration.
-static void pcg_spmv(Pcg &k, const PcgOperator &op, const double *in, double *q, bool dot, const PcgState *pred)
+static void pcg_spmv(Pcg &k, const RowOperator &op, const double *in, double *q, bool dot, const PcgState *pred)
 {
 	spsamd_ctx *c = k.c;
 	const bool fused = dot && !k.unfused;
@@ -319,7 +311,28 @@ static const uint32_t *taken_rowptr(spsamd_ctx *c, ConMat &S, Prepared *hp, uint
 	return dense_rowptr(c, S, 0);
 }
 
-static void check_vector_overlap(spsamd_ctx *c, const spsamd_coo *X, const char *name, const double *x, uint64_t bytes)
+// (declared in internal.h) S, taken by consolidate_operand, with what its serial chains need
+void row_operator(spsamd_ctx *c, ConMat &S, Prepared *hp, uint64_t nrow, uint64_t ncol, bool long_rows, RowOperator *out)
+{
+	RowOperator &op = *out;
+	op.nrow = nrow; op.ncol = ncol; op.nnz = S.nnz;
+	op.ptr = taken_rowptr(c, S, hp, nrow);
+	op.col = S.col; op.val = S.val;
+	if (S.nnz && long_rows) {
+		const int path = c->tune.spmm_path;
+		op.long_min = path == 1 ? 0xFFFFFFFFu : path >= 2 ? 0u : c->tune.spmm_long_min > 0 ? (uint32_t)c->tune.spmm_long_min : 64u;
+		uint32_t *list = nullptr, *count = nullptr;
+		if (path != 1) op.nlong = spmm_long_list(c, op.ptr, nrow, op.long_min, &list, &count);
+		if (op.nlong) {
+			op.list = list; op.count = count;
+			op.m.rowptr = op.ptr; op.m.nrow = nrow; op.m.ncol = ncol; op.m.nnz = S.nnz;
+			if (hp) op.m.tup = prepared_btup(c, hp);
+			else { BTup *t = c->arena.get<BTup>(S.nnz); pack_tuples(c, S.col, S.val, S.nnz, t); op.m.tup = t; }
+		}
+	}
+}
+
+void check_vector_overlap(spsamd_ctx *c, const spsamd_coo *X, const char *name, const double *x, uint64_t bytes)
 {
 	const OperandView view = operand_view(c, X);
 	const uint64_t n = view.coo.nnz;
@@ -329,11 +342,12 @@ static void check_vector_overlap(spsamd_ctx *c, const spsamd_coo *X, const char 
 		if (ranges_overlap(x, bytes, arr[k], n * (k == 2 ? 8 : 4))) throw Error{SPSAMD_EINVAL, std::string("x overlaps the arrays of ") + name};
 }
 
-int solve_pcg(spsamd_ctx *c, const spsamd_coo *A, char transpose, int precond, const spsamd_coo *M, char transpose_M,
+// The loop of both entry points.  `hook`: a preconditioner of the caller's own (spsamd_solve_pcg_amg); precond is then
+// PCG_PRECOND_HOOK and M null.
+int pcg_solve(spsamd_ctx *c, const spsamd_coo *A, char transpose, int precond, const spsamd_coo *M, char transpose_M,
 	const double *b, double *x, int mem, double tol, uint64_t max_iter, double *hist_host, size_t hist_capacity,
-	int duplicate_policy, int zero_nan, spsamd_pcg_stats *stats, spsamd_result *res)
+	int duplicate_policy, int zero_nan, spsamd_pcg_stats *stats, spsamd_result *res, PcgPrecond *hook)
 {
-	if (precond < SPSAMD_PRECOND_NONE || precond > SPSAMD_PRECOND_LU) throw Error{SPSAMD_EINVAL, "precond must be SPSAMD_PRECOND_NONE, _JACOBI or _LU"};
 	if (mem != SPSAMD_MEM_HOST && mem != SPSAMD_MEM_DEVICE) throw Error{SPSAMD_EINVAL, "mem of b and x must be SPSAMD_MEM_HOST or SPSAMD_MEM_DEVICE"};
 	if (!(tol >= 0.0) || tol - tol != 0.0) throw Error{SPSAMD_EINVAL, "tol must be finite and not negative"};
 	if ((precond == SPSAMD_PRECOND_LU) != (M != nullptr)) throw Error{SPSAMD_EINVAL, "M goes with SPSAMD_PRECOND_LU, and only with it"};
@@ -378,21 +392,8 @@ int solve_pcg(spsamd_ctx *c, const spsamd_coo *A, char transpose, int precond, c
 	k.hist = hcap ? c->arena.get<double>(hcap) : nullptr;
 
 	// ---- the operator: S's row pointer; the long rows' list and the packed rows of k_spmm.hip only where there is a long row
-	PcgOperator op;
-	op.ptr = taken_rowptr(c, S, hpa, n);
-	op.col = S.col; op.val = S.val;
-	if (S.nnz) {
-		const int path = c->tune.spmm_path;
-		op.long_min = path == 1 ? 0xFFFFFFFFu : path >= 2 ? 0u : c->tune.spmm_long_min > 0 ? (uint32_t)c->tune.spmm_long_min : 64u;
-		uint32_t *list = nullptr, *count = nullptr;
-		if (path != 1) op.nlong = spmm_long_list(c, op.ptr, n, op.long_min, &list, &count);
-		if (op.nlong) {
-			op.list = list; op.count = count;
-			op.m.rowptr = op.ptr; op.m.nrow = op.m.ncol = n; op.m.nnz = S.nnz;
-			if (hpa) op.m.tup = prepared_btup(c, hpa);
-			else { BTup *t = c->arena.get<BTup>(S.nnz); pack_tuples(c, S.col, S.val, S.nnz, t); op.m.tup = t; }
-		}
-	}
+	RowOperator op;
+	row_operator(c, S, hpa, n, n, true, &op);
 
 	// ---- the preconditioner
 	double *diag = nullptr;
@@ -426,6 +427,7 @@ int solve_pcg(spsamd_ctx *c, const spsamd_coo *A, char transpose, int precond, c
 	double *r = c->arena.get<double>(n), *p = c->arena.get<double>(n), *q = c->arena.get<double>(n);
 	double *z = precond == SPSAMD_PRECOND_NONE ? r : c->arena.get<double>(n);
 	const bool vec = (((uintptr_t)z | (uintptr_t)p) & 15u) == 0;
+	if (hook) hook->setup(c, op, r, z);
 
 	// ---- bb, thresh; r = b - A x, rr0, hist[0], the stop tests before the first iteration
 	k_pcg_init<<<dim3(1), dim3(1), 0, st>>>(k.st, max_iter, hcap);
@@ -465,6 +467,9 @@ int solve_pcg(spsamd_ctx *c, const spsamd_coo *A, char transpose, int precond, c
 			} else if (precond == SPSAMD_PRECOND_LU) {
 				k.launches += solve_levels(c, tl, *sched[0], r, 1, z, 1, 1, nullptr);
 				k.launches += solve_levels(c, tu, *sched[1], z, 1, z, 1, 1, nullptr);
+				k.dot(r, z, k.st);
+			} else if (hook) {
+				k.launches += hook->apply();
 				k.dot(r, z, k.st);
 			}
 			k.finish<FIN_RZ>(precond != SPSAMD_PRECOND_NONE);
@@ -507,6 +512,15 @@ int solve_pcg(spsamd_ctx *c, const spsamd_coo *A, char transpose, int precond, c
 		stats->ms_setup = res->ms_consolidate + res->ms_symbolic; stats->ms_iterate = res->ms_numeric;
 	}
 	return SPSAMD_OK;
+}
+
+int solve_pcg(spsamd_ctx *c, const spsamd_coo *A, char transpose, int precond, const spsamd_coo *M, char transpose_M,
+	const double *b, double *x, int mem, double tol, uint64_t max_iter, double *hist_host, size_t hist_capacity,
+	int duplicate_policy, int zero_nan, spsamd_pcg_stats *stats, spsamd_result *res)
+{
+	if (precond < SPSAMD_PRECOND_NONE || precond > SPSAMD_PRECOND_LU) throw Error{SPSAMD_EINVAL, "precond must be SPSAMD_PRECOND_NONE, _JACOBI or _LU"};
+	return pcg_solve(c, A, transpose, precond, M, transpose_M, b, x, mem, tol, max_iter, hist_host, hist_capacity, duplicate_policy,
+		zero_nan, stats, res, nullptr);
 }
 
 } // namespace spsamd
