@@ -332,7 +332,8 @@ extern "C" int spsamd_operand_prepare(spsamd_ctx *c, const spsamd_coo *X, char t
 		}
 		if ((role & SPSAMD_AS_B) && maxlen > 64) {
 			const uint64_t W = m.ncol > (uint64_t(1) << 21) ? 16384 : 8192, nwin = (m.ncol + W - 1) / W, nwp = (nwin + 7) & ~7ull, nrowb = m.nrow + 1;
-			const uint64_t idx = nrowb * (nwin + 1) * 4 + nrowb * nwp * 2 + (nrowb * nwin + 1) * 4 + (n + 8) * 12 + 8192;
+			const uint64_t nbw = (((nwin + 31) >> 5) + 3) & ~3ull;        // (the window-occupancy words, heavy_b_index)
+			const uint64_t idx = nrowb * (nwin + 1) * 4 + nrowb * nwp * 2 + nrowb * nbw * 4 + (nrowb * nwin + 1) * 4 + (n + 8) * 12 + 8192;
 			size_t freeb = 0, totalb = 0;
 			if (idx <= 64 * (uint64_t)n * 16 && hipMemGetInfo(&freeb, &totalb) == hipSuccess && idx + want < freeb / 2) want += idx;
 		}

@@ -443,6 +443,8 @@ struct Prepared {
 	uint64_t nrowb = 0;
 	uint32_t *bwin = nullptr;         // [nrowb][nwin + 1] first tuple of row k with column >= w * W
 	uint16_t *wcnt = nullptr;         // [nrowb][nwp]      tuples of row k in window w
+	uint32_t *bocc = nullptr;         // [nrowb][nbw]      bit w: row k has a tuple in window w (nbw words, a multiple of four)
+	uint32_t nbw = 0;
 	uint32_t *wptr = nullptr;         // [nwin][nrowb] + 1 window-major copy: CSR pointer per window ...
 	BTup *btw = nullptr;              // ... and its tuples
 	// triangular solves

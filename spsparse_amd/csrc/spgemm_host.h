@@ -22,6 +22,8 @@ struct Heavy {
 	uint64_t tuples = 0;             // ... and their A tuples
 	uint32_t *rows = nullptr;
 	uint32_t *bwin = nullptr;
+	uint32_t *bocc = nullptr;        // window-occupancy words of op(B)'s rows (the long rows' hash cells test them before bwin)
+	uint32_t nbw = 0;
 	uint32_t nwin = 0, nwin1 = 0;
 	uint32_t *winprod = nullptr;
 	uint32_t ncell[NCLS] = {};

@@ -58,8 +58,12 @@ __global__ __launch_bounds__(BT_NT) void k_wcnt_count(const int32_t *brow, const
 	}
 }
 
+// It also writes the window-occupancy words: bocc[k * nbw + (w >> 5)] bit (w & 31) is set where row k has a tuple in window
+// w -- one ballot of the lanes' counts per 64 windows, while the counts are in LDS anyway.  nbw = ceil(nwin / 32) rounded up to
+// a multiple of four: a row is 16-byte aligned and up to 128 windows are one 16-byte load (16 MB at scale 20 against bwin's
+// 541 MB).  Every word of a row is written, the padding as zeros.
 __global__ __launch_bounds__(BT_NT) void k_bwin_scan(const uint16_t *wcnt, const uint32_t *bptr, uint64_t nrowb, uint32_t tr, uint32_t nwin, uint32_t nwp,
-	uint32_t *bwin)
+	uint32_t *bwin, uint32_t *bocc, uint32_t nbw)
 {
 	extern __shared__ uint32_t s_dyn[];                              // [tr][nwp / 2] packed pairs of counts, then [tr] row pointers
 	const uint32_t nwin1 = nwin + 1u, lane = lane_id(), wv = wave_id(), nph = nwp >> 1;
@@ -77,9 +81,13 @@ __global__ __launch_bounds__(BT_NT) void k_bwin_scan(const uint16_t *wcnt, const
 		const uint32_t *src = s_dyn + r * nph;
 		uint32_t carry = s_ptr[r];
 		uint32_t *bw = bwin + (k0 + r) * nwin1;
-		for (uint32_t c0 = 0; c0 < nwin1; c0 += 64u) {
+		uint32_t *bo = bocc + (k0 + r) * nbw;
+		const uint32_t cend = max(nwin1, nbw << 5);                 // (nbw is even: the last step ends on the row's last word)
+		for (uint32_t c0 = 0; c0 < cend; c0 += 64u) {
 			const uint32_t w = c0 + lane;
 			const uint32_t v = w < nwin ? (src[w >> 1] >> ((w & 1u) << 4)) & 0xFFFFu : 0u;
+			const unsigned long long nz = __ballot(v != 0u);
+			if (lane < 2u && (c0 >> 5) + lane < nbw) bo[(c0 >> 5) + lane] = (uint32_t)(nz >> (lane << 5));
 			const uint32_t inc = wave_inclusive_scan_u32(v);
 			if (w < nwin1) bw[w] = carry + inc - v;
 			carry += (uint32_t)__builtin_amdgcn_readlane((int)inc, 63);
@@ -499,11 +507,12 @@ int heavy_b_index(spsamd_ctx *c, const ConMat &B, const uint32_t *bptr, uint32_t
 		while (w2 * 2 <= fit - 1) w2 *= 2;
 		throw TooWide{w2 << wshift};
 	}
-	const uint32_t nwin1 = nwin + 1, nwp = (nwin + 7u) & ~7u;
-	pb->reserve(nrowb * nwin1 * 4 + nrowb * nwp * 2 + (nrowb * nwin + 1) * 4 + ((size_t)B.nnz + DENSE_R) * sizeof(BTup) + 4096);   // (a handle: one slab for all four)
+	const uint32_t nwin1 = nwin + 1, nwp = (nwin + 7u) & ~7u, nbw = (((nwin + 31u) >> 5) + 3u) & ~3u;
+	pb->reserve(nrowb * nwin1 * 4 + nrowb * nwp * 2 + nrowb * nbw * 4 + (nrowb * nwin + 1) * 4 + ((size_t)B.nnz + DENSE_R) * sizeof(BTup) + 4096);   // (a handle: one slab for all five)
 	pb->bwin = pb->get<uint32_t>(nrowb * nwin1);
 	pb->wcnt = pb->get<uint16_t>(nrowb * nwp);
-	pb->W = W; pb->nwin = nwin; pb->nwp = nwp; pb->nrowb = nrowb;
+	pb->bocc = pb->get<uint32_t>(nrowb * nbw);
+	pb->W = W; pb->nwin = nwin; pb->nwp = nwp; pb->nbw = nbw; pb->nrowb = nrowb;
 	pb->wptr = nullptr; pb->btw = nullptr;
 	fill_zero(c, pb->wcnt, nrowb * nwp * sizeof(uint16_t));
 	k_wcnt_count<<<dim3((unsigned)c->num_cu * 16u), dim3(BT_NT), 0, st>>>(B.row, B.col, B.nnz, wshift, nwp, reinterpret_cast<uint32_t *>(pb->wcnt));
@@ -513,7 +522,7 @@ int heavy_b_index(spsamd_ctx *c, const ConMat &B, const uint32_t *bptr, uint32_t
 	while (tr > 4 && (size_t)tr * (nwp * 2 + 4) > BT_LDS) tr >>= 1;
 	static bool lds_attr = false;                                   // (more than the default 64 KB of dynamic LDS)
 	if (!lds_attr) { SPS_HIP(hipFuncSetAttribute((const void *)k_bwin_scan, hipFuncAttributeMaxDynamicSharedMemorySize, (int)BT_LDS)); lds_attr = true; }
-	k_bwin_scan<<<dim3((unsigned)((nrowb + tr - 1) / tr)), dim3(BT_NT), (size_t)tr * (nwp * 2 + 4), st>>>(pb->wcnt, bptr, nrowb, tr, nwin, nwp, pb->bwin);
+	k_bwin_scan<<<dim3((unsigned)((nrowb + tr - 1) / tr)), dim3(BT_NT), (size_t)tr * (nwp * 2 + 4), st>>>(pb->wcnt, bptr, nrowb, tr, nwin, nwp, pb->bwin, pb->bocc, nbw);
 	SPS_LAUNCH_CHECK();
 	return W;
 }
@@ -535,6 +544,7 @@ void heavy_prepare(spsamd_ctx *c, Heavy &hv, const Bins &bins, const RowMeta &m,
 	hv.winprod = c->arena.get<uint32_t>((uint64_t)hv.n * hv.nwin);
 	const uint32_t nwp = (hv.nwin + 7u) & ~7u;
 	hv.bwin = pb->bwin;
+	hv.bocc = pb->bocc; hv.nbw = pb->nbw;
 	uint16_t *wcnt = pb->wcnt;
 	// The window-major copy of B needs only the index just built: it goes to the context's side stream now, beside the
 	// histograms, the cell grouping, their host round trips and the numeric kernels that do not read it (a product with heavy
