@@ -145,7 +145,7 @@ __global__ __launch_bounds__(256, 8) void k_light_direct(uint32_t nrow, const ui
 	constexpr int G = 64 / S;
 	constexpr int LOGS = S == 8 ? 3 : (S == 16 ? 4 : (S == 32 ? 5 : 6));
 	typedef typename std::conditional<K64, uint64_t, uint32_t>::type key_t;
-	constexpr key_t NOKEY = (key_t)~(key_t)0;
+	constexpr key_t NOKEY = (key_t)~(key_t)0;                       // no key may equal it: spgemm_all_light keeps (2^26 columns, S = 64) off the narrow variant
 	__shared__ uint32_t s_mark[4][64];
 	__shared__ key_t s_key[4][64];
 	__shared__ key_t s_key2[4][64];

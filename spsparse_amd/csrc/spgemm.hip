@@ -372,8 +372,11 @@ static void spgemm_all_light(spsamd_ctx *c, MultiplyArgs &a, spsamd_result *res,
 	const ConMat &A = a.A, &B = a.B;
 	const uint32_t nrow = (uint32_t)A.nrow;
 	const EmitParams ep = emit_params(c, a, B.ncol, 0, 0);
-	// wide variant: (column << log2 S | A position) does not fit 32 bits, or an operand array reaches 4 GB
-	const bool k64 = ep.ncolbits + 6u > 32u || A.nnz >= (1u << 29) || B.nnz >= (1u << 29) || A.nrow + 2 >= (uint64_t(1) << 30) || B.nrow + 3 >= (uint64_t(1) << 30);
+	// wide variant: (column << log2 S | A position) does not fit 32 bits or its largest value, (ncol - 1, S - 1), is the narrow
+	// NOKEY itself (S = 64 at 2^26 columns: that product was dropped as "no product"), or an operand array reaches 4 GB
+	const uint32_t S = maxp <= 8 ? 8u : (maxp <= 16 ? 16u : (maxp <= 32 ? 32u : 64u)), G = 64u / S;
+	const bool top_is_nokey = S == 64u && B.ncol == (uint64_t(1) << 26);
+	const bool k64 = ep.ncolbits + 6u > 32u || top_is_nokey || A.nnz >= (1u << 29) || B.nnz >= (1u << 29) || A.nrow + 2 >= (uint64_t(1) << 30) || B.nrow + 3 >= (uint64_t(1) << 30);
 	SinkParams sk{};
 	sk.err = get_zeroed<uint32_t>(c, 1);
 	unsigned long long *pc = get_zeroed<unsigned long long>(c, 1);
@@ -385,7 +388,6 @@ static void spgemm_all_light(spsamd_ctx *c, MultiplyArgs &a, spsamd_result *res,
 		check_kernel_error(digest_end(c, slots, sk.err, res, c->ev[EV_N1]));
 	} else {
 		// COO: one segment per row of op(A) (empty rows included) -- or, in one pass, per wave round of the kernel
-		const uint32_t S = maxp <= 8 ? 8u : (maxp <= 16 ? 16u : (maxp <= 32 ? 32u : 64u)), G = 64u / S;
 		const size_t nround = ((size_t)nrow + 4u * G - 1u) / (4u * G) * 4u;      // wave rounds: G rows each, four waves per workgroup round
 		const size_t nsegs = std::max<size_t>(nrow, nround);
 		sk.segcount = c->arena.get<uint32_t>(nsegs + 1);
