@@ -182,6 +182,9 @@ const char *spsamd_version(void);
  *   dense_min       64..4096          a window above this many products is a dense cell (3072 with bitmap tiles, else 2048)
  *   long_dense_min  > 0               the same for rows of more than 256 A tuples (1024 at 8192-column windows)
  *   long_cap        > 0               grouping target of those rows' hash cells (cell_cap)
+ *   few_max         1..16 | -1        mid rows (65 .. 4096 products) of at most this many A tuples run in k_few, which holds a
+ *                                     row's B segments in registers and requests the next row's B tuples a row ahead (8);
+ *                                     -1: none, every mid row in k_hash.  ORDERED and EXACT_PATTERN calls: always none
  *   direct_min      > 0               a window of a tile row above this is a direct cell (off: >= dense_min)
  *   tiles_v1        1 | 2 | 3         hash tiles r01 | hash tiles v2 | bitmap-rank tiles (default: chosen per call)
  *   no_tiles, no_wmajor               1: no tiles | no window-major copy of B

@@ -50,8 +50,8 @@ extern "C" int spsamd_ctx_create(spsamd_ctx **out, int device, void *hip_stream)
 	if (hipStreamCreateWithFlags(&c->side2, hipStreamNonBlocking) != hipSuccess) { spsamd_ctx_destroy(c); return SPSAMD_EHIP; }
 	for (auto &e : c->ev_side2) if (hipEventCreateWithFlags(&e, hipEventDisableTiming) != hipSuccess) { spsamd_ctx_destroy(c); return SPSAMD_EHIP; }
 	// developer knobs: the environment is consulted here and nowhere else
-	static const char *const knobs[] = {"window", "cell_cap", "dense_min", "no_tiles", "xcd", "emit_path", "light_path", "no_wmajor", "direct_min", "tiles_v1", "long_cap", "long_dense_min", "index_budget_mb", "trace", "light_two_pass", "spmm_path", "spmm_long_min", "add_path", "masked_path", "sampled_path", "select_path", "extract_path", "reduce_path", "emult_path", "tile_walk", "solve_path", "solve_row", "solve_fuse_rows", "factor_path", "factor_row", "factor_fuse_rows", "factor_serial_work", "factor_lds_row", "color_path", "color_row", "color_fuse_rows", "color_wave_deg", "agg_path", "agg_row", "agg_fuse_rows", "agg_wave_deg", "agg_per_rows", "pcg_check_every", "pcg_fuse", "amg_path", "amg_fuse_rows"};
-	static const char *const envs[] = {"SPSAMD_W", "SPSAMD_CELL_CAP", "SPSAMD_DENSE_MIN", "SPSAMD_NO_TILES", "SPSAMD_XCD", "SPSAMD_EMIT_PATH", "SPSAMD_LIGHT_PATH", "SPSAMD_NO_WMAJOR", "SPSAMD_DIRECT_MIN", "SPSAMD_TILES_V1", "SPSAMD_LONG_CAP", "SPSAMD_LONG_DENSE_MIN", "SPSAMD_INDEX_BUDGET_MB", "SPSAMD_TRACE", "SPSAMD_LIGHT_TWO_PASS", "SPSAMD_SPMM_PATH", "SPSAMD_SPMM_LONG_MIN", "SPSAMD_ADD_PATH", "SPSAMD_MASKED_PATH", "SPSAMD_SAMPLED_PATH", "SPSAMD_SELECT_PATH", "SPSAMD_EXTRACT_PATH", "SPSAMD_REDUCE_PATH", "SPSAMD_EMULT_PATH", "SPSAMD_TILE_WALK", "SPSAMD_SOLVE_PATH", "SPSAMD_SOLVE_ROW", "SPSAMD_SOLVE_FUSE_ROWS", "SPSAMD_FACTOR_PATH", "SPSAMD_FACTOR_ROW", "SPSAMD_FACTOR_FUSE_ROWS", "SPSAMD_FACTOR_SERIAL_WORK", "SPSAMD_FACTOR_LDS_ROW", "SPSAMD_COLOR_PATH", "SPSAMD_COLOR_ROW", "SPSAMD_COLOR_FUSE_ROWS", "SPSAMD_COLOR_WAVE_DEG", "SPSAMD_AGG_PATH", "SPSAMD_AGG_ROW", "SPSAMD_AGG_FUSE_ROWS", "SPSAMD_AGG_WAVE_DEG", "SPSAMD_AGG_PER_ROWS", "SPSAMD_PCG_CHECK_EVERY", "SPSAMD_PCG_FUSE", "SPSAMD_AMG_PATH", "SPSAMD_AMG_FUSE_ROWS"};
+	static const char *const knobs[] = {"window", "cell_cap", "dense_min", "no_tiles", "xcd", "emit_path", "light_path", "no_wmajor", "direct_min", "tiles_v1", "long_cap", "long_dense_min", "few_max", "index_budget_mb", "trace", "light_two_pass", "spmm_path", "spmm_long_min", "add_path", "masked_path", "sampled_path", "select_path", "extract_path", "reduce_path", "emult_path", "tile_walk", "solve_path", "solve_row", "solve_fuse_rows", "factor_path", "factor_row", "factor_fuse_rows", "factor_serial_work", "factor_lds_row", "color_path", "color_row", "color_fuse_rows", "color_wave_deg", "agg_path", "agg_row", "agg_fuse_rows", "agg_wave_deg", "agg_per_rows", "pcg_check_every", "pcg_fuse", "amg_path", "amg_fuse_rows"};
+	static const char *const envs[] = {"SPSAMD_W", "SPSAMD_CELL_CAP", "SPSAMD_DENSE_MIN", "SPSAMD_NO_TILES", "SPSAMD_XCD", "SPSAMD_EMIT_PATH", "SPSAMD_LIGHT_PATH", "SPSAMD_NO_WMAJOR", "SPSAMD_DIRECT_MIN", "SPSAMD_TILES_V1", "SPSAMD_LONG_CAP", "SPSAMD_LONG_DENSE_MIN", "SPSAMD_FEW_MAX", "SPSAMD_INDEX_BUDGET_MB", "SPSAMD_TRACE", "SPSAMD_LIGHT_TWO_PASS", "SPSAMD_SPMM_PATH", "SPSAMD_SPMM_LONG_MIN", "SPSAMD_ADD_PATH", "SPSAMD_MASKED_PATH", "SPSAMD_SAMPLED_PATH", "SPSAMD_SELECT_PATH", "SPSAMD_EXTRACT_PATH", "SPSAMD_REDUCE_PATH", "SPSAMD_EMULT_PATH", "SPSAMD_TILE_WALK", "SPSAMD_SOLVE_PATH", "SPSAMD_SOLVE_ROW", "SPSAMD_SOLVE_FUSE_ROWS", "SPSAMD_FACTOR_PATH", "SPSAMD_FACTOR_ROW", "SPSAMD_FACTOR_FUSE_ROWS", "SPSAMD_FACTOR_SERIAL_WORK", "SPSAMD_FACTOR_LDS_ROW", "SPSAMD_COLOR_PATH", "SPSAMD_COLOR_ROW", "SPSAMD_COLOR_FUSE_ROWS", "SPSAMD_COLOR_WAVE_DEG", "SPSAMD_AGG_PATH", "SPSAMD_AGG_ROW", "SPSAMD_AGG_FUSE_ROWS", "SPSAMD_AGG_WAVE_DEG", "SPSAMD_AGG_PER_ROWS", "SPSAMD_PCG_CHECK_EVERY", "SPSAMD_PCG_FUSE", "SPSAMD_AMG_PATH", "SPSAMD_AMG_FUSE_ROWS"};
 	static_assert(sizeof knobs / sizeof knobs[0] == sizeof envs / sizeof envs[0], "one environment variable per knob");
 	for (size_t k = 0; k < sizeof knobs / sizeof knobs[0]; ++k)
 		if (const char *e = getenv(envs[k])) (void)spsamd_ctx_set_tuning(c, knobs[k], atol(e));
@@ -69,7 +69,7 @@ extern "C" int spsamd_ctx_set_tuning(spsamd_ctx *c, const char *name, long value
 	struct { const char *n; int *p; } tab[] = {
 		{"window", &c->tune.window}, {"cell_cap", &c->tune.cell_cap}, {"dense_min", &c->tune.dense_min},
 		{"no_tiles", &c->tune.no_tiles}, {"xcd", &c->tune.xcd}, {"emit_path", &c->tune.emit_path},
-		{"light_path", &c->tune.light_path}, {"no_wmajor", &c->tune.no_wmajor}, {"direct_min", &c->tune.direct_min}, {"tiles_v1", &c->tune.tiles_v1}, {"long_cap", &c->tune.long_cap}, {"long_dense_min", &c->tune.long_dense_min}, {"index_budget_mb", &c->tune.index_budget_mb}, {"trace", &c->tune.trace}, {"light_two_pass", &c->tune.light_two_pass},
+		{"light_path", &c->tune.light_path}, {"no_wmajor", &c->tune.no_wmajor}, {"direct_min", &c->tune.direct_min}, {"tiles_v1", &c->tune.tiles_v1}, {"long_cap", &c->tune.long_cap}, {"long_dense_min", &c->tune.long_dense_min}, {"few_max", &c->tune.few_max}, {"index_budget_mb", &c->tune.index_budget_mb}, {"trace", &c->tune.trace}, {"light_two_pass", &c->tune.light_two_pass},
 		{"spmm_path", &c->tune.spmm_path}, {"spmm_long_min", &c->tune.spmm_long_min}, {"add_path", &c->tune.add_path},
 		{"masked_path", &c->tune.masked_path}, {"sampled_path", &c->tune.sampled_path}, {"select_path", &c->tune.select_path},
 		{"extract_path", &c->tune.extract_path}, {"reduce_path", &c->tune.reduce_path}, {"emult_path", &c->tune.emult_path},

@@ -1,5 +1,5 @@
 // spgemm.hip -- the hot path: C = c * Di * op(A) * Dj * op(B) * Dk on gfx950.  This file is the DRIVER and the small symbolic
-// kernels; the numeric kernels live in k_light.hip, k_hash.hip, k_dense.hip and k_tiles.hip, the heavy rows' symbolic phase
+// kernels; the numeric kernels live in k_light.hip, k_hash.hip, k_few.hip, k_dense.hip and k_tiles.hip, the heavy rows' symbolic phase
 // in symbolic_heavy.hip (source map: DESIGN.md section 4).  One multiply is spgemm_once, a sequence of phases: spgemm_all_light,
 // or classify_rows, build_segments, then numeric_digest / numeric_coo (every pass over the numeric kernels: launch_pass).  The
 // two sinks are digest_begin / digest_end and sink_output; spgemm_column_blocks is the fallback for an op(B) too wide.
@@ -88,7 +88,7 @@ constexpr int CLS_ITEMS = 4;                    // rows per thread: fewer workgr
                                                 // are a chain of dependent loads (16: 78 us for the 68 K rows of a 1/8 block of cfg2 -- 17 workgroups)
 
 __global__ __launch_bounds__(256) void k_classify(const uint32_t *beg, const int32_t *id, uint32_t nrows, const int64_t *pref, const uint32_t *elen,
-	const int32_t *si_pos, const double *si_val, uint32_t *rprod, uint8_t *rbin, BinCounters *bc)
+	const int32_t *si_pos, const double *si_val, int few_max, uint32_t *rprod, uint8_t *rbin, BinCounters *bc)
 {
 	// bin statistics: wave-aggregated (ballot per bin present in the wave), then LDS, then one
 	// global atomic per (workgroup, bin).  Same-address global atomics serialise (~5 ns each), so
@@ -117,6 +117,7 @@ __global__ __launch_bounds__(256) void k_classify(const uint32_t *beg, const int
 				if (q < 0 || si_val[q] == 0) P = 0;
 			}
 			b = bin_of(P);
+			if (b >= 5 && b <= 7 && (int)La <= few_max) b += BIN_FEW - 5;       // a mid row of few A tuples: k_few (few_max < 1: none)
 			rprod[r] = P;
 			rbin[r] = (uint8_t)b;
 		}
@@ -527,8 +528,11 @@ static RowClasses classify_rows(spsamd_ctx *c, const MultiplyArgs &a, const RowL
 	rc.rprod = c->arena.get<uint32_t>(rl.nrows);
 	uint8_t *rbin = c->arena.get<uint8_t>(rl.nrows);
 	BinCounters *bc = get_zeroed<BinCounters>(c, 1);
+	// k_few has neither the ordered insertion nor the EXACT_PATTERN bookkeeping: those calls keep every mid row on k_hash
+	const bool arrival = !(a.sink_flags & (SPSAMD_SINK_ORDERED | SPSAMD_SINK_EXACT_PATTERN));
+	const int few_max = !arrival || c->tune.few_max < 0 ? -1 : (c->tune.few_max == 0 ? FEW_MAX_DEFAULT : std::min(c->tune.few_max, (int)FEW_LMAX));
 	k_classify<<<dim3(grid_for(rl.nrows, 256 * CLS_ITEMS)), dim3(256), 0, st>>>(rl.beg, rl.id, rl.nrows, pref, rc.elen,
-		a.si.present ? a.si.pos : nullptr, a.si.val, rc.rprod, rbin, bc);
+		a.si.present ? a.si.pos : nullptr, a.si.val, few_max, rc.rprod, rbin, bc);
 	SPS_LAUNCH_CHECK();
 	rc.hbc = read_back(c, bc);
 	if (rc.hbc.too_big) throw Error{SPSAMD_EINVAL, "an output row with more than 2^32-1 scalar products is not supported"};
@@ -552,17 +556,17 @@ static RowClasses classify_rows(spsamd_ctx *c, const MultiplyArgs &a, const RowL
 	return rc;
 }
 
-// rows, products and A tuples of the light (bins 1-4), mid (5-7) and heavy (8) rows
+// rows, products and A tuples of the light (bins 1-4), mid (5-7 and k_few's, BIN_FEW ..) and heavy (8) rows
 static void fill_class_counters(spsamd_result *res, const BinCounters &h)
 {
-	const struct { int first, last; uint64_t *rows, *prods, *tuples; } cls[3] = {{1, 4, &res->rows_light, &res->products_light, &res->tuples_light},
-		{5, 7, &res->rows_mid, &res->products_mid, &res->tuples_mid}, {8, 8, &res->rows_heavy, &res->products_heavy, &res->tuples_heavy}};
+	const struct { int first, last; uint64_t *rows, *prods, *tuples; } cls[4] = {{1, 4, &res->rows_light, &res->products_light, &res->tuples_light},
+		{5, 7, &res->rows_mid, &res->products_mid, &res->tuples_mid}, {8, 8, &res->rows_heavy, &res->products_heavy, &res->tuples_heavy},
+		{BIN_FEW, BIN_FEW + 2, &res->rows_mid, &res->products_mid, &res->tuples_mid}};
 	res->products = 0;
-	for (auto &k : cls) {
-		*k.rows = *k.prods = *k.tuples = 0;
-		for (int b = k.first; b <= k.last; ++b) { *k.rows += h.rows[b]; *k.prods += h.prods[b]; *k.tuples += h.tuples[b]; }
-		res->products += *k.prods;
-	}
+	res->rows_light = res->products_light = res->tuples_light = res->rows_mid = res->products_mid = res->tuples_mid = 0;
+	res->rows_heavy = res->products_heavy = res->tuples_heavy = 0;
+	for (auto &k : cls)
+		for (int b = k.first; b <= k.last; ++b) { *k.rows += h.rows[b]; *k.prods += h.prods[b]; *k.tuples += h.tuples[b]; res->products += h.prods[b]; }
 }
 
 // Segments (the COO sink's: one per light / mid row, one per cell of a heavy row; sk.segbase, their number returned) and the heavy and mid rows' cells
@@ -585,13 +589,16 @@ static int64_t build_segments(spsamd_ctx *c, const MultiplyArgs &a, const RowLis
 		scan_exclusive_u32_u32(c, nseg, segbase, rl.nrows);
 	}
 	if (hv.n) heavy_cells(c, hv, m, segbase);
-	for (int k = 0; k < 3; ++k) {
-		uint32_t nb = bins.count[5 + k];
+	for (int k = 0; k < 6; ++k) {                                   // the mid bins, then k_few's
+		const int bin = k < 3 ? 5 + k : BIN_FEW + k - 3;
+		uint32_t nb = bins.count[bin];
 		if (!nb) continue;
-		mc.cells[k] = c->arena.get<Cell>(nb);
-		k_row_cells<<<dim3(grid_for(nb)), dim3(256), 0, c->stream>>>(bins.rows + bins.off[5 + k], nb, rl.beg, rl.id, rc.rprod, segbase, mc.cells[k]);
+		Cell *&list = k < 3 ? mc.cells[k] : mc.few[k - 3];
+		list = c->arena.get<Cell>(nb);
+		k_row_cells<<<dim3(grid_for(nb)), dim3(256), 0, c->stream>>>(bins.rows + bins.off[bin], nb, rl.beg, rl.id, rc.rprod, segbase, list);
 		SPS_LAUNCH_CHECK();
 	}
+	if (c->tune.trace) fprintf(stderr, "few cells: mid %u\n", bins.count[BIN_FEW] + bins.count[BIN_FEW + 1] + bins.count[BIN_FEW + 2]);
 	res->cells_hash = (uint64_t)hv.ncell[0] + hv.ncell[1] + hv.ncell[2] + hv.ncell[3] + hv.ntcell + hv.ntcell2;
 	res->cells_dense = hv.ncell[CLS_DENSE]; res->window = hv.n ? (uint32_t)hv.W : 0u;
 	res->products_dense = hv.clsprod[CLS_DENSE]; res->products_tiles = hv.clsprod[NCLS]; res->products_direct = hv.clsprod[NCLS + 1];
@@ -611,6 +618,7 @@ static void launch_pass(spsamd_ctx *c, const Work &w, const SinkParams &sk, cons
 	launch_light<MODE>(c, w.bins, w.m, w.ep, sk);
 	record(mark[1]);
 	launch_mid<MODE>(c, w.bins, w.mc, w.m, w.ep, sk);
+	launch_mid_few<MODE>(c, w.bins, w.mc, w.m, w.ep, sk);
 	record(mark[2]);
 	if (MODE != MODE_STORE && w.hv.n) heavy_sort_lists(c, w.hv);
 	launch_heavy_hash<MODE>(c, w.hv, w.m, w.ep, sk);

@@ -15,7 +15,10 @@ namespace spsamd {
 
 enum { MODE_COUNT = 0, MODE_STORE = 1, MODE_DIGEST = 2 };
 
-constexpr int NBIN = 9;          // 0 none | 1..4 light (S = 8,16,32,64) | 5..7 mid (T = 1024,4096,8192) | 8 heavy
+constexpr int NBIN = 12;         // 0 none | 1..4 light (S = 8,16,32,64) | 5..7 mid (T = 1024,4096,8192) | 8 heavy | 9..11 mid rows of few A tuples (k_few; same T)
+constexpr int BIN_FEW = 9;       // first of the few-tuple mid bins: bin b of 5..7 with at most few_max A tuples is bin b + BIN_FEW - 5
+constexpr uint32_t FEW_LMAX = 16;        // most A tuples of a k_few cell: a wave holds a cell's segments in its first 16 lanes
+constexpr int FEW_MAX_DEFAULT = 8;       // the few_max knob's default (profiles/few/README.md)
 #ifndef MID_MAX_V
 #define MID_MAX_V 4096
 #endif

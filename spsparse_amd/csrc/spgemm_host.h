@@ -10,7 +10,7 @@ struct Bins {
 	uint32_t *rows;
 };
 
-struct MidCells { Cell *cells[3] = {nullptr, nullptr, nullptr}; };
+struct MidCells { Cell *cells[3] = {nullptr, nullptr, nullptr}; Cell *few[3] = {nullptr, nullptr, nullptr}; };   // by table class: k_hash's rows, k_few's (bins BIN_FEW ..)
 
 // Thrown by heavy_prepare: op(B) has more column windows than the heavy-row path indexes, or its window indices would not
 // fit the device -- spgemm() then multiplies by column blocks of `width` columns (spgemm_column_blocks).
@@ -124,6 +124,7 @@ template <int MODE> void launch_light_direct_s(spsamd_ctx *c, uint32_t maxp, uin
 void launch_light_gather(spsamd_ctx *c, uint32_t nrow, uint32_t S, const uint32_t *cnt, const int64_t *off,
 	const int32_t *si, const int32_t *sj, const double *sv, int32_t *oi, int32_t *oj, double *ov);                                                    // k_light.hip
 template <int MODE> void launch_mid(spsamd_ctx *c, const Bins &b, const MidCells &mc, const RowMeta &m, const EmitParams &ep, const SinkParams &sk);  // k_hash.hip
+template <int MODE> void launch_mid_few(spsamd_ctx *c, const Bins &b, const MidCells &mc, const RowMeta &m, const EmitParams &ep, const SinkParams &sk);  // k_few.hip
 template <int MODE> void launch_hash_windowed(spsamd_ctx *c, const Heavy &hv, const RowMeta &m, const EmitParams &ep, const SinkParams &sk);  // k_hash.hip
 template <int MODE> void launch_tiles_v1(spsamd_ctx *c, const Heavy &hv, const RowMeta &m, const EmitParams &ep, const SinkParams &sk);       // k_hash.hip
 template <int MODE> void launch_tiles_bm(spsamd_ctx *c, const Heavy &hv, const RowMeta &m, const EmitParams &ep, const SinkParams &sk);       // k_tiles.hip
