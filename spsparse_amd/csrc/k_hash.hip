@@ -43,7 +43,7 @@ __global__ __launch_bounds__(NT) void k_hash(const Cell *cells, uint32_t ncell, 
 	__shared__ int32_t h_key[T];
 	__shared__ double h_val[MODE == MODE_COUNT ? 1 : T];
 	__shared__ uint16_t occ[T / 2];
-	__shared__ uint64_t s_sort[MODE == MODE_STORE ? T / 2 : 1];
+	__shared__ uint64_t s_sort[MODE == MODE_STORE ? sort_slots(T) : 1];
 	__shared__ uint16_t s_cnt[MODE == MODE_STORE ? 16 * ((T / 2 + NT - 1) / NT) * (NT / 64) : 1];
 	__shared__ Expand<NT, T / 2> X;
 	__shared__ uint32_t scr32[NT / 64 + 1];

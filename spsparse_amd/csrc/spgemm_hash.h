@@ -180,6 +180,10 @@ __device__ __forceinline__ uint32_t *lds_radix_sort(uint32_t *a, uint32_t *b, ui
 
 struct DigestAcc { unsigned long long cnt, hash; double sum; };
 
+// 64-bit entries of s_sort for a table of T slots.  The bitonic network of hash_emit pads a cell's keys (at most T / 2) to a
+// power of two: the table that is none, 3072, sorts up to 2048 entries for a cell of more than 1024 outputs.
+constexpr int sort_slots(int T) { int n = 1; while (n < T / 2) n <<= 1; return n; }
+
 // Emit the occupied slots of the finished cell into the sink and clean them.
 template <int T, int NT, int MODE, bool PAT>
 __device__ __forceinline__ void hash_emit(uint32_t nocc, int32_t rowid, uint32_t seg, const EmitParams &ep, const SinkParams &sk,

@@ -607,9 +607,11 @@ def emit_args(A, B, emit):
     C_ = 2.0 if emit in ("C", "all") else 1.0
     rows = np.arange(A.shape[0])
     scalei = orc.Vec(rows, 3.0 + rows % 3, A.shape[0]) if emit in ("scalei", "all") else None
-    j = np.arange(B.shape[1])
-    j = j[j % DROP != 0]
-    scalek = orc.Vec(j, np.where(j % 2 == 0, 1.0, 2.0), B.shape[1]) if emit in ("scalek", "all") else None
+    scalek = None
+    if emit in ("scalek", "all"):                                   # (an entry per column: not for the plans of 2^25 columns)
+        j = np.arange(B.shape[1])
+        j = j[j % DROP != 0]
+        scalek = orc.Vec(j, np.where(j % 2 == 0, 1.0, 2.0), B.shape[1])
     return C_, scalei, scalek
 
 
