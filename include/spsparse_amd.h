@@ -246,9 +246,9 @@ const char *spsamd_version(void);
  *   factor_fuse_rows > 0              factor_ilu0: the widest level that still counts as thin (256 rows)
  *   factor_serial_work > 0            factor_ilu0: rows of at most this many lookups are serial-class (64)
  *   factor_lds_row  1..4096           factor_ilu0: the longest row (tuples) of the wave kernel's LDS copy (256)
- *   pcg_check_every > 0               solve_pcg: iterations enqueued between two reads of the device state (8, DESIGN.md
+ *   pcg_check_every > 0               solve_pcg, solve_bicgstab: iterations enqueued between two reads of the device state (8, DESIGN.md
  *                                     section 23)
- *   pcg_fuse        1                 solve_pcg: every vector operation and every dot product in a launch of its own
+ *   pcg_fuse        1                 solve_pcg, solve_bicgstab: every vector operation and every dot product in a launch of its own
  *                                     (default: a dot's first level rides in the kernel that produces its vector)
  *   amg_path        1 | 2             amg_apply, solve_pcg_amg: 1 every level of the cycle in launches of its own | 2 the whole
  *                                     hierarchy in the one launch of the fused tail, whatever its levels' orders (default: the
@@ -922,6 +922,50 @@ typedef struct {
 } spsamd_pcg_stats;
 
 int spsamd_solve_pcg(spsamd_ctx *ctx, const spsamd_coo *A, char transpose,
+	int precond, const spsamd_coo *M /* PRECOND_LU only, else NULL */, char transpose_M,
+	const double *b, double *x /* in: x0, out: the iterate at the stop */, int mem,
+	double tol, uint64_t max_iter,
+	double *hist_host /* may be NULL */, size_t hist_capacity,
+	int duplicate_policy, int zero_nan,
+	spsamd_pcg_stats *stats /* may be NULL */, spsamd_result *result /* may be NULL */);
+
+/*
+ * Solve op(A) x = b for an unsymmetric op(A) by right-preconditioned BiCGStab with rhat = r0, one right-hand side, the whole
+ * loop on the device.  Everything around the loop is spsamd_solve_pcg's and is not restated: the
+ * operands and their intake (S of A, F of M), b, x and mem, the overlap rules, the three preconditioners, dot, fold,
+ * q = A p, M^-1, usable, the NaN and rounding rules, hist_host, stats (the same struct and SPSAMD_PCG_* reasons), result,
+ * the SPSAMD_EINVAL / SPSAMD_EDIM cases with x untouched, n == 0, and the meaning of the knobs pcg_check_every and pcg_fuse.
+ * Every value returned -- x, hist, iterations, reason, bb, rr0, rr -- is defined by this loop, bit for bit:
+ *
+ *       bb = dot(b, b);  thresh = (tol * tol) * bb
+ *       q = A x;  r_i = b_i - q_i;  rhat = r;  rr = dot(r, r);  rho' = rr;  k = 0;  hist[0] = rr;  rr0 = rr
+ *       loop:
+ *           if rr <= thresh:                  stop CONVERGED          (a NaN compares false)
+ *           if k == max_iter:                 stop MAXITER
+ *           if not usable(rho'):              stop BREAKDOWN
+ *           if k == 0:  p = r
+ *           else:       if not usable(omega): stop BREAKDOWN
+ *                       beta = (rho' / rho) * (alpha / omega);   p_i = r_i + beta * (p_i - omega * v_i)
+ *           rho = rho'
+ *           y = M^-1 p;  v = A y;  rv = dot(rhat, v)
+ *           if not usable(rv):                stop BREAKDOWN
+ *           alpha = rho / rv
+ *           s_i = r_i - alpha * v_i;  ss = dot(s, s)
+ *           if ss <= thresh:                  x_i = x_i + alpha * y_i;  rr = ss;  k = k + 1;  hist[k] = rr;  stop CONVERGED
+ *           z = M^-1 s;  t = A z;  ts = dot(t, s);  tt = dot(t, t)
+ *           if not usable(tt):                stop BREAKDOWN
+ *           omega = ts / tt
+ *           x_i = (x_i + alpha * y_i) + omega * z_i;   r_i = s_i - omega * t_i
+ *           rr = dot(r, r);  rho' = dot(rhat, r);  k = k + 1;  hist[k] = rr
+ *
+ *   - At k = 0 dot(rhat, r) is dot(r, r) term for term: rho' has the bits of rr0 and is not computed.
+ *   - At a BREAKDOWN inside an iteration x, rr and k are those after k whole iterations.
+ *   - The half-step exit is part of the definition: a system solved exactly at the half step (a diagonal A under Jacobi, at
+ *     k = 1) would otherwise end in 0 / 0.  An iteration that ends there counts as one, and applies M^-1 and A once.
+ *   - Under SPSAMD_PRECOND_NONE y is p and z is s.
+ * Returns when x is complete.
+ */
+int spsamd_solve_bicgstab(spsamd_ctx *ctx, const spsamd_coo *A, char transpose,
 	int precond, const spsamd_coo *M /* PRECOND_LU only, else NULL */, char transpose_M,
 	const double *b, double *x /* in: x0, out: the iterate at the stop */, int mem,
 	double tol, uint64_t max_iter,

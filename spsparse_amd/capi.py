@@ -174,7 +174,7 @@ SYMBOLS = ["spsamd_ctx_create", "spsamd_ctx_destroy", "spsamd_last_error", "spsa
            "spsamd_multiply_dense", "spsamd_add", "spsamd_multiply_stream", "spsamd_multiply_masked",
            "spsamd_multiply_sampled", "spsamd_select", "spsamd_extract", "spsamd_reduce", "spsamd_emult", "spsamd_solve_tri",
            "spsamd_factor_ilu0", "spsamd_color", "spsamd_solve_pcg", "spsamd_aggregate",
-           "spsamd_amg_apply", "spsamd_solve_pcg_amg"]
+           "spsamd_amg_apply", "spsamd_solve_pcg_amg", "spsamd_solve_bicgstab"]
 
 _lib = None
 
@@ -240,6 +240,7 @@ def load():
                                    C.c_size_t, C.c_int, P(C.c_size_t), P(AggregateStats), P(Result)]
     L.spsamd_solve_pcg.argtypes = [C.c_void_p, P(Coo), C.c_char, C.c_int, P(Coo), C.c_char, C.c_void_p, C.c_void_p, C.c_int,
                                    C.c_double, C.c_uint64, C.c_void_p, C.c_size_t, C.c_int, C.c_int, P(PcgStats), P(Result)]
+    L.spsamd_solve_bicgstab.argtypes = L.spsamd_solve_pcg.argtypes
     L.spsamd_amg_apply.argtypes = [C.c_void_p, P(AmgLevel), C.c_size_t, P(AmgParams), C.c_void_p, C.c_void_p, C.c_int,
                                    C.c_int, C.c_int, P(AmgStats), P(Result)]
     L.spsamd_solve_pcg_amg.argtypes = [C.c_void_p, P(AmgLevel), C.c_size_t, P(AmgParams), C.c_void_p, C.c_void_p, C.c_int,
@@ -687,6 +688,19 @@ class Context:
         x0 and receives the iterate at the stop (x=None: a zero start, allocated here).  hist_capacity: the entries of the
         history to bring back (None: max_iter + 1; 0: none).  Returns (x, hist, PcgStats): hist a float64 numpy array of
         min(iterations + 1, hist_capacity) values of dot(r, r).  result: a capi.Result to fill (timings)."""
+        return self._krylov(self.L.spsamd_solve_pcg, A, b, x, precond, M, transpose, transpose_M, tol, max_iter, hist_capacity,
+                            duplicate_policy, zero_nan, result)
+
+    def solve_bicgstab(self, A, b, x=None, precond=PRECOND_NONE, M=None, transpose='.', transpose_M='.', tol=1e-8,
+                       max_iter=1000, hist_capacity=None, duplicate_policy=ADD, zero_nan=False, result=None):
+        """spsamd_solve_bicgstab: op(A) x = b for an unsymmetric op(A) by right-preconditioned BiCGStab, bit for bit the loop
+        of the header.  The arguments and the returned (x, hist, PcgStats) are solve_pcg's."""
+        return self._krylov(self.L.spsamd_solve_bicgstab, A, b, x, precond, M, transpose, transpose_M, tol, max_iter,
+                            hist_capacity, duplicate_policy, zero_nan, result)
+
+    def _krylov(self, call, A, b, x, precond, M, transpose, transpose_M, tol, max_iter, hist_capacity, duplicate_policy,
+                zero_nan, result):
+        """The arguments of solve_pcg / solve_bicgstab as the C ABI takes them, the call, and what both return."""
         pb, _ldb, nb, mb = _dense_arg(b, "b", writable=False)
         if x is None:
             if mb == MEM_HOST:
@@ -705,10 +719,9 @@ class Context:
         cap = int(max_iter) + 1 if hist_capacity is None else int(hist_capacity)
         hist = np.empty(max(cap, 1), np.float64)
         st = PcgStats()
-        self._check(self.L.spsamd_solve_pcg(self.h, C.byref(A), transpose.encode(), int(precond),
-                                            None if M is None else C.byref(M), transpose_M.encode(), pb, px, mb, float(tol),
-                                            int(max_iter), hist.ctypes.data if cap else None, cap, duplicate_policy,
-                                            int(zero_nan), C.byref(st), None if result is None else C.byref(result)))
+        self._check(call(self.h, C.byref(A), transpose.encode(), int(precond), None if M is None else C.byref(M),
+                         transpose_M.encode(), pb, px, mb, float(tol), int(max_iter), hist.ctypes.data if cap else None, cap,
+                         duplicate_policy, int(zero_nan), C.byref(st), None if result is None else C.byref(result)))
         return x, hist[:min(int(st.iterations) + 1, cap)].copy(), st
 
     def _amg_args(self, levels, params, b, x, zero_x):

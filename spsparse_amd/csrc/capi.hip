@@ -612,6 +612,21 @@ extern "C" int spsamd_solve_pcg(spsamd_ctx *c, const spsamd_coo *A, char transpo
 	)
 }
 
+// op(A) x = b by right-preconditioned BiCGStab, the loop on the device (k_bicgstab.hip).  Workspace only, like
+// spsamd_solve_pcg.
+extern "C" int spsamd_solve_bicgstab(spsamd_ctx *c, const spsamd_coo *A, char transpose, int precond, const spsamd_coo *M, char transpose_M,
+	const double *b, double *x, int mem, double tol, uint64_t max_iter, double *hist_host, size_t hist_capacity,
+	int duplicate_policy, int zero_nan, spsamd_pcg_stats *stats, spsamd_result *res)
+{
+	if (!c) return SPSAMD_EINVAL;
+	API_GUARD(c,
+		if (!A) throw Error{SPSAMD_EINVAL, "null operand"};
+		spsamd_result local;
+		return solve_bicgstab(c, A, transpose, precond, M, transpose_M, b, x, mem, tol, max_iter, hist_host, hist_capacity,
+			duplicate_policy, zero_nan, stats, res ? res : &local);
+	)
+}
+
 // x = cycle(0, b): one multigrid cycle over the caller's levels (k_amg.hip).  Workspace only.
 extern "C" int spsamd_amg_apply(spsamd_ctx *c, const spsamd_amg_level *levels, size_t nlevels, const spsamd_amg_params *params,
 	const double *b, double *x, int mem, int duplicate_policy, int zero_nan, spsamd_amg_stats *stats, spsamd_result *res)

@@ -653,6 +653,13 @@ int pcg_solve(spsamd_ctx *c, const spsamd_coo *A, char transpose, int precond, c
 	const double *b, double *x, int mem, double tol, uint64_t max_iter, double *hist_host, size_t hist_capacity,
 	int duplicate_policy, int zero_nan, spsamd_pcg_stats *stats, spsamd_result *res, PcgPrecond *hook);
 
+// ---------------------------------------------------------------- BiCGStab (k_bicgstab.hip)
+
+// A x = b for an unsymmetric A by the loop of the header: spsamd_solve_bicgstab after the context check
+int solve_bicgstab(spsamd_ctx *c, const spsamd_coo *A, char transpose, int precond, const spsamd_coo *M, char transpose_M,
+	const double *b, double *x, int mem, double tol, uint64_t max_iter, double *hist_host, size_t hist_capacity,
+	int duplicate_policy, int zero_nan, spsamd_pcg_stats *stats, spsamd_result *res);
+
 // ---------------------------------------------------------------- aggregation multigrid cycle (k_amg.hip)
 
 // x = cycle(0, b): spsamd_amg_apply after the context check

@@ -23,60 +23,12 @@
 //
 // The preconditioner step is also a hook (PcgPrecond, internal.h): spsamd_solve_pcg_amg runs this loop with the multigrid
 // cycle of k_amg.hip as z = M^-1 r, under the rule of the solves -- it writes its own scratch and z, and reads no state.
-#include "internal.h"
-#include "devutil.h"
-#include "x86fp.h"
+#include "krylov_dev.h"                        // PcgState, the fold's chunk_partial and block_fold: shared with k_bicgstab.hip
 
 #include <algorithm>
 #include <cstring>
 
 namespace spsamd {
-
-constexpr int PCG_CHUNK = 1024;                // elements of a level-0 chunk: 16 per lane of one wave
-constexpr int PCG_NT = 256;                    // four waves, a chunk each
-constexpr int PCG_FINISH_NT = 1024;            // the one workgroup of k_pcg_finish
-constexpr int32_t PCG_RUNNING = -1;            // PcgState::state; from 0 on: SPSAMD_PCG_*
-
-struct PcgState {
-	double bb, thresh, rr0, rr, rz, pq, alpha, beta;
-	unsigned long long k, max_iter, hist_cap;
-	int32_t state, pad;
-};
-
-__device__ __forceinline__ bool pcg_usable(double v) { return v == v && mag_of(v) != 0x7FF0000000000000ull && v != 0.0; }
-
-// The partial of chunk g of t[0 .. n), t[e] = term(e) (called once per element of the chunk, by the lane that owns it):
-// valid in lane 0.  Every lane of the wave calls it.
-template <class Term>
-__device__ __forceinline__ double chunk_partial(uint64_t g, uint64_t n, Term term)
-{
-	const uint64_t base = g * PCG_CHUNK + lane_id();
-	double t[PCG_CHUNK / 64];
-#pragma unroll
-	for (int k = 0; k < PCG_CHUNK / 64; ++k) {
-		const uint64_t e = base + (uint64_t)k * 64;
-		t[k] = e < n ? term(e) : 0.0;
-	}
-	double a = 0.0;
-#pragma unroll
-	for (int k = 0; k < PCG_CHUNK / 64; ++k)
-		if (base + (uint64_t)k * 64 < n) a = ref_add(a, t[k]);
-#pragma unroll
-	for (int s = 32; s >= 1; s >>= 1) {
-		const double o = __shfl_down(a, s, 64);
-		if (lane_id() < (unsigned)s) a = ref_add(a, o);              // a_l is the left operand
-	}
-	return a;
-}
-
-// the chunk of this wave, or false past the last one
-__device__ __forceinline__ bool my_chunk(uint64_t n, uint64_t *g)
-{
-	*g = (uint64_t)blockIdx.x * (PCG_NT / 64) + wave_id();
-	return *g * PCG_CHUNK < n;
-}
-
-__device__ __forceinline__ bool stopped(const PcgState *st) { return st && st->state != PCG_RUNNING; }
 
 // ---------------------------------------------------------------- level 0: the vector kernels
 
@@ -196,25 +148,6 @@ __global__ void k_pcg_init(PcgState *st, unsigned long long max_iter, unsigned l
 // ---------------------------------------------------------------- levels 1 and up, the scalars, the stop tests
 
 enum { FIN_BB = 0, FIN_RR0 = 1, FIN_RZ = 2, FIN_PQ = 3, FIN_RR = 4 };
-
-// fold(part, c0) for c0 >= 2 by the whole workgroup: a wave per chunk, a barrier between two levels; b0 / b1 take the
-// levels' partials in turn (ceil(c0 / 1024) entries each).  The value comes back in every thread.
-__device__ double block_fold(const double *part, uint64_t m, double *b0, double *b1, double *s_out)
-{
-	const double *src = part;
-	double *dst = b0;
-	for (;;) {                                                       // uniform
-		const uint64_t c = (m + PCG_CHUNK - 1) / PCG_CHUNK;
-		for (uint64_t g = wave_id(); g < c; g += PCG_FINISH_NT / 64) {
-			const double a = chunk_partial(g, m, [&](uint64_t e) { return src[e]; });
-			if (lane_id() == 0) { if (c == 1) *s_out = a; else dst[g] = a; }
-		}
-		__syncthreads();                                             // this level's partials are complete, and visible to the workgroup
-		if (c == 1) break;
-		src = dst; dst = dst == b0 ? b1 : b0; m = c;
-	}
-	return *s_out;
-}
 
 // part == nullptr (FIN_RZ under PRECOND_NONE): z is r, and dot(r, z) has the bits of rr
 template <int KIND>
