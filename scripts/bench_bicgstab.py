@@ -34,22 +34,22 @@ REASONS = {0: "converged", 1: "maxiter", 2: "breakdown"}
 
 
 def PASSES(precond, unfused):
-    """[(kernel, vector passes)] of one iteration after the first: what each vector kernel of k_bicgstab.hip reads and
-    writes, a vector read twice by one kernel counted once.  Without a preconditioner y is p and z is s.  The SpMVs' own
-    traffic (S, the gathers, the product) is not in the model: a fused dot costs the SpMV one more vector where its partner
-    is not the SpMV's input."""
+    """[(kernel, vector passes)] of one iteration after the first: what each vector kernel of the loop reads and writes
+    (k_bicgstab.hip; the k_pcg_ ones are the shared kernels of k_krylov.hip), a vector read twice by one kernel counted
+    once.  Without a preconditioner y is p and z is s.  The SpMVs' own traffic (S, the gathers, the product) is not in
+    the model: a fused dot costs the SpMV one more vector where its partner is not the SpMV's input."""
     none = precond == capi.PRECOND_NONE
     k = [("k_bicg_direction (r, p, v in; p out)", 4)]
     if precond == capi.PRECOND_JACOBI:
-        k += [("k_bicg_jacobi y (p, d in; y out)", 3), ("k_bicg_jacobi z (s, d in; z out)", 3)]
+        k += [("k_pcg_jacobi<plain> y (p, d in; y out)", 3), ("k_pcg_jacobi<plain> z (s, d in; z out)", 3)]
     if unfused:
-        k += [("k_bicg_dot (rhat, v)", 2), ("k_bicg_half<plain> (r, v in; s out)", 3), ("k_bicg_dot (s, s)", 1),
-              ("k_bicg_dot (t, s)", 2), ("k_bicg_dot (t, t)", 1),
+        k += [("k_pcg_dot (rhat, v)", 2), ("k_bicg_half<plain> (r, v in; s out)", 3), ("k_pcg_dot (s, s)", 1),
+              ("k_pcg_dot (t, s)", 2), ("k_pcg_dot (t, t)", 1),
               ("k_bicg_update<1> (x, y, z in; x out)", 4), ("k_bicg_update<2> (s, t in; r out)", 3),
-              ("k_bicg_dot (r, r)", 1), ("k_bicg_dot (rhat, r)", 2)]
+              ("k_pcg_dot (r, r)", 1), ("k_pcg_dot (rhat, r)", 2)]
     else:
-        k += [("k_bicg_spmv<1>: rhat beside v = A y", 1), ("k_bicg_half<dot> (r, v in; s out)", 3),
-              ("k_bicg_spmv<2>: s beside t = A z", 0 if none else 1),
+        k += [("k_pcg_spmv<1>: rhat beside v = A y", 1), ("k_bicg_half<dot> (r, v in; s out)", 3),
+              ("k_pcg_spmv<2>: s beside t = A z", 0 if none else 1),
               ("k_bicg_update<0> (x, y, z, s, t, rhat in; x, r out)", 7 if none else 8)]
     return k
 

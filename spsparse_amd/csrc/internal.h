@@ -614,9 +614,13 @@ uint64_t solve_levels(spsamd_ctx *c, const TriView &t, const SolveSchedule &s, c
 constexpr int SOLVE_NT = 1024;                 // threads of the one workgroup of a fused run (k_solve_fused, k_fac_fused) and of k_peel_thin
 constexpr uint32_t SOLVE_FUSE_ROWS = 256;      // default of the solve_fuse_rows knob: the flat end of the measured sweep
 
-// ---------------------------------------------------------------- preconditioned conjugate gradients (k_krylov.hip)
+// ---------------------------------------------------------------- Krylov loops (k_krylov.hip, k_bicgstab.hip)
+// Both loops, and solve_pcg_amg through pcg_solve, run inside one frame, KrylovCall (krylov_dev.h, HIP only): it owns the
+// argument checks and their order, the operands, the workspace order, the preconditioner's data with the schedule rollback,
+// the vector kernels, the read-back loop, what counts as a launch, and the tail.  A loop supplies its state struct, its own
+// vectors, its direction / update / finish kernels and the body of an iteration.
 
-// A x = b by the loop of the header: spsamd_solve_pcg after the context check
+// A x = b by preconditioned conjugate gradients, the loop of the header: spsamd_solve_pcg after the context check
 int solve_pcg(spsamd_ctx *c, const spsamd_coo *A, char transpose, int precond, const spsamd_coo *M, char transpose_M,
 	const double *b, double *x, int mem, double tol, uint64_t max_iter, double *hist_host, size_t hist_capacity,
 	int duplicate_policy, int zero_nan, spsamd_pcg_stats *stats, spsamd_result *res);
@@ -640,7 +644,7 @@ void row_operator(spsamd_ctx *c, ConMat &S, Prepared *hp, uint64_t nrow, uint64_
 // SPSAMD_EINVAL where X has 2^31 or more tuples or the vector x overlaps one of its arrays
 void check_vector_overlap(spsamd_ctx *c, const spsamd_coo *X, const char *name, const double *x, uint64_t bytes);
 
-// The preconditioner step of the loop as a hook.  setup() runs once, after S is taken and the loop's vectors exist: it
+// The preconditioner step of the frame as a hook.  setup() runs once, after S is taken and the loop's vectors exist: it
 // takes everything it needs out of the workspace then.  apply() enqueues z = M^-1 r on those two vectors and returns the
 // launches it issued; it allocates nothing, reads no PcgState and writes nothing but its own scratch and z.
 struct PcgPrecond {
@@ -649,13 +653,12 @@ struct PcgPrecond {
 	virtual ~PcgPrecond() {}
 };
 constexpr int PCG_PRECOND_HOOK = 3;            // pcg_solve's precond under a hook (never a value of the public ABI)
+// solve_pcg's loop with z = M^-1 r left to `hook` (precond PCG_PRECOND_HOOK, M null), or solve_pcg itself (hook null)
 int pcg_solve(spsamd_ctx *c, const spsamd_coo *A, char transpose, int precond, const spsamd_coo *M, char transpose_M,
 	const double *b, double *x, int mem, double tol, uint64_t max_iter, double *hist_host, size_t hist_capacity,
 	int duplicate_policy, int zero_nan, spsamd_pcg_stats *stats, spsamd_result *res, PcgPrecond *hook);
 
-// ---------------------------------------------------------------- BiCGStab (k_bicgstab.hip)
-
-// A x = b for an unsymmetric A by the loop of the header: spsamd_solve_bicgstab after the context check
+// A x = b for an unsymmetric A by BiCGStab, the loop of the header: spsamd_solve_bicgstab after the context check
 int solve_bicgstab(spsamd_ctx *c, const spsamd_coo *A, char transpose, int precond, const spsamd_coo *M, char transpose_M,
 	const double *b, double *x, int mem, double tol, uint64_t max_iter, double *hist_host, size_t hist_capacity,
 	int duplicate_policy, int zero_nan, spsamd_pcg_stats *stats, spsamd_result *res);

@@ -23,14 +23,18 @@
 //
 // The preconditioner step is also a hook (PcgPrecond, internal.h): spsamd_solve_pcg_amg runs this loop with the multigrid
 // cycle of k_amg.hip as z = M^-1 r, under the rule of the solves -- it writes its own scratch and z, and reads no state.
-#include "krylov_dev.h"                        // PcgState, the fold's chunk_partial and block_fold: shared with k_bicgstab.hip
+//
+// This file also holds what every Krylov loop of the library shares (k_bicgstab.hip is the other one): the vector kernels
+// k_pcg_dot, _residual, _jacobi, _spmv, _dot_rows and _init, and the members of the frame that alone launches them
+// (KrylovCall, krylov_dev.h) -- the argument checks, the operands, the workspace, the preconditioner's data, the read-back
+// loop and the tail of a call.  A loop keeps its direction, update and finish kernels, its state struct and its body.
+#include "krylov_dev.h"
 
-#include <algorithm>
 #include <cstring>
 
 namespace spsamd {
 
-// ---------------------------------------------------------------- level 0: the vector kernels
+// ---------------------------------------------------------------- level 0: the vector kernels of every loop
 
 __global__ void __launch_bounds__(PCG_NT) k_pcg_dot(const double *u, const double *w, uint64_t n, double *__restrict__ part, const PcgState *st)
 {
@@ -40,7 +44,7 @@ __global__ void __launch_bounds__(PCG_NT) k_pcg_dot(const double *u, const doubl
 	if (lane_id() == 0) part[g] = a;
 }
 
-// r = b - q (the set-up's residual)
+// r = b - q (the set-up's residual), and the partials of dot(r, r)
 template <bool DOT>
 __global__ void __launch_bounds__(PCG_NT) k_pcg_residual(const double *__restrict__ b, const double *__restrict__ q, double *__restrict__ r,
 	uint64_t n, double *__restrict__ part)
@@ -51,50 +55,71 @@ __global__ void __launch_bounds__(PCG_NT) k_pcg_residual(const double *__restric
 	if (DOT && lane_id() == 0) part[g] = a;
 }
 
-// z = r / d, and the partials of dot(r, z)
+// out = in / d, and the partials of dot(in, out)
 template <bool DOT>
-__global__ void __launch_bounds__(PCG_NT) k_pcg_jacobi(const double *__restrict__ r, const double *__restrict__ d, double *__restrict__ z,
+__global__ void __launch_bounds__(PCG_NT) k_pcg_jacobi(const double *__restrict__ in, const double *__restrict__ d, double *__restrict__ out,
 	uint64_t n, double *__restrict__ part, const PcgState *st)
 {
 	uint64_t g;
 	if (stopped(st) || !my_chunk(n, &g)) return;
-	const double a = chunk_partial(g, n, [&](uint64_t e) { const double re = r[e], v = ref_div(re, d[e]); z[e] = v; return DOT ? ref_mul(re, v) : 0.0; });
+	const double a = chunk_partial(g, n, [&](uint64_t e) { const double re = in[e], v = ref_div(re, d[e]); out[e] = v; return DOT ? ref_mul(re, v) : 0.0; });
 	if (DOT && lane_id() == 0) part[g] = a;
 }
 
-// q_i = the serial chain of row i over S, and the partials of dot(in, q).  A row of more than long_min tuples gets +0.0: the
-// wave kernel of k_spmm.hip adds its chain in the next launch, and the partial of its chunk is redone after that
-// (k_pcg_dot_rows).  A lane walks the 16 rows 64 apart that the fold gives it.
-template <bool DOT>
+// out = S in by row_chain.  NDOT 1: and the partials of dot(u, out) | 2: of dot(out, u) and dot(out, out).  The partial of a
+// chunk that holds a long row is redone once the wave kernel has added that row's chain (k_pcg_dot_rows).  A lane walks the
+// 16 rows 64 apart that the fold gives it.  u may be `in`.
+template <int NDOT>
 __global__ void __launch_bounds__(PCG_NT) k_pcg_spmv(const uint32_t *__restrict__ ptr, const int32_t *__restrict__ col, const double *__restrict__ val,
-	const double *__restrict__ in, double *__restrict__ q, uint64_t n, uint32_t long_min, double *__restrict__ part, const PcgState *st)
+	const double *in, double *__restrict__ out, uint64_t n, uint32_t long_min, const double *u, double *__restrict__ part0,
+	double *__restrict__ part1, const PcgState *st)
 {
 	uint64_t g;
 	if (stopped(st) || !my_chunk(n, &g)) return;
-	const double a = chunk_partial(g, n, [&](uint64_t i) {
-		double acc = 0.0;
-		const uint32_t b = ptr[i], e = ptr[i + 1];
-		if (e - b <= long_min)
-			for (uint32_t k = b; k < e; ++k) acc = ref_add(acc, ref_mul(val[k], in[(uint32_t)col[k]]));
-		q[i] = acc;
-		return DOT ? ref_mul(in[i], acc) : 0.0;
-	});
-	if (DOT && lane_id() == 0) part[g] = a;
+	if (NDOT == 2) {
+		double a0, a1;
+		chunk_partial2(g, n, [&](uint64_t i, double *t0, double *t1) {
+			const double acc = row_chain(ptr, col, val, in, i, long_min);
+			out[i] = acc;
+			*t0 = ref_mul(acc, u[i]); *t1 = ref_mul(acc, acc);
+		}, &a0, &a1);
+		if (lane_id() == 0) { part0[g] = a0; part1[g] = a1; }
+	} else {
+		const double a = chunk_partial(g, n, [&](uint64_t i) {
+			const double acc = row_chain(ptr, col, val, in, i, long_min);
+			out[i] = acc;
+			return NDOT ? ref_mul(u[i], acc) : 0.0;
+		});
+		if (NDOT && lane_id() == 0) part0[g] = a;
+	}
 }
 
-// The partials of dot(u, w) for the chunks that hold a listed row, a wave per listed row (two rows of one chunk store the
-// same value twice)
-__global__ void __launch_bounds__(64) k_pcg_dot_rows(const double *u, const double *w, uint64_t n, const uint32_t *__restrict__ list,
-	const uint32_t *__restrict__ count, double *part, const PcgState *st)
+// The partials of dot(u0, w0) -- and of dot(u1, w1) where u1 is given -- for the chunks that hold a listed row, a wave per
+// listed row (two rows of one chunk store the same value twice)
+__global__ void __launch_bounds__(64) k_pcg_dot_rows(const double *u0, const double *w0, double *part0, const double *u1, const double *w1,
+	double *part1, uint64_t n, const uint32_t *__restrict__ list, const uint32_t *__restrict__ count, const PcgState *st)
 {
 	if (stopped(st)) return;
 	const uint32_t m = *count;
 	for (uint32_t r = blockIdx.x; r < m; r += gridDim.x) {               // uniform
 		const uint64_t g = list[r] / PCG_CHUNK;
-		const double a = chunk_partial(g, n, [&](uint64_t e) { return ref_mul(u[e], w[e]); });
-		if (lane_id() == 0) part[g] = a;
+		const double a = chunk_partial(g, n, [&](uint64_t e) { return ref_mul(u0[e], w0[e]); });
+		if (lane_id() == 0) part0[g] = a;
+		if (u1) {
+			const double b = chunk_partial(g, n, [&](uint64_t e) { return ref_mul(u1[e], w1[e]); });
+			if (lane_id() == 0) part1[g] = b;
+		}
 	}
 }
+
+// A loop's state struct of `words` 8-byte words, a PcgState first: all +0.0 / 0 but these three
+__global__ void k_pcg_init(PcgState *st, uint32_t words, unsigned long long max_iter, unsigned long long hist_cap)
+{
+	for (uint32_t w = 0; w < words; ++w) reinterpret_cast<unsigned long long *>(st)[w] = 0;
+	st->max_iter = max_iter; st->hist_cap = hist_cap; st->state = PCG_RUNNING;
+}
+
+// ---------------------------------------------------------------- the loop's own vector kernels
 
 // p = z (k == 0), else p = z + beta p.  No fold here, so nothing fixes which lane owns which element: VEC takes two
 // neighbouring elements per thread in 16-byte loads and stores (z and p 16-byte aligned), the odd last element alone.
@@ -138,13 +163,6 @@ __global__ void __launch_bounds__(PCG_NT) k_pcg_update(double *__restrict__ x, c
 	if (WHAT == 0 && lane_id() == 0) part[g] = a;
 }
 
-__global__ void k_pcg_init(PcgState *st, unsigned long long max_iter, unsigned long long hist_cap)
-{
-	PcgState s = {};
-	s.max_iter = max_iter; s.hist_cap = hist_cap; s.state = PCG_RUNNING;
-	*st = s;
-}
-
 // ---------------------------------------------------------------- levels 1 and up, the scalars, the stop tests
 
 enum { FIN_BB = 0, FIN_RR0 = 1, FIN_RZ = 2, FIN_PQ = 3, FIN_RR = 4 };
@@ -184,72 +202,16 @@ __global__ void __launch_bounds__(PCG_FINISH_NT) k_pcg_finish(const double *part
 	else if (k == st->max_iter) st->state = SPSAMD_PCG_MAXITER;
 }
 
-// ---------------------------------------------------------------- host
-
-namespace {
-
-struct Pcg {
-	spsamd_ctx *c;
-	uint64_t n, c0;
-	bool unfused;
-	double *part, *b0, *b1, *hist;
-	PcgState *st;
-	uint64_t launches = 0;
-	unsigned chunk_grid() const { return (unsigned)((c0 + PCG_NT / 64 - 1) / (PCG_NT / 64)); }
-
-	void dot(const double *u, const double *w, const PcgState *pred)
-	{
-		if (!c0) return;
-		k_pcg_dot<<<dim3(chunk_grid()), dim3(PCG_NT), 0, c->stream>>>(u, w, n, part, pred);
-		SPS_LAUNCH_CHECK();
-		++launches;
-	}
-	template <int KIND> void finish(bool have_part, double tol2 = 0.0)
-	{
-		k_pcg_finish<KIND><<<dim3(1), dim3(PCG_FINISH_NT), 0, c->stream>>>(have_part ? part : nullptr, c0, b0, b1, st, hist, tol2);
-		SPS_LAUNCH_CHECK();
-		++launches;
-	}
-};
-
-} // namespace
-
-// q = S in (+ the partials of dot(in, q) where `dot`).  Nothing is allocated here: it runs once per iteration.
-static void pcg_spmv(Pcg &k, const RowOperator &op, const double *in, double *q, bool dot, const PcgState *pred)
-{
-	spsamd_ctx *c = k.c;
-	const bool fused = dot && !k.unfused;
-	if (fused) k_pcg_spmv<true><<<dim3(k.chunk_grid()), dim3(PCG_NT), 0, c->stream>>>(op.ptr, op.col, op.val, in, q, k.n, op.long_min, k.part, pred);
-	else k_pcg_spmv<false><<<dim3(k.chunk_grid()), dim3(PCG_NT), 0, c->stream>>>(op.ptr, op.col, op.val, in, q, k.n, op.long_min, k.part, pred);
-	SPS_LAUNCH_CHECK();
-	++k.launches;
-	if (op.nlong) {
-		spmm_long_rows(c, op.m, op.list, op.count, in, 1, q, 1, 1);
-		++k.launches;
-	}
-	if (!dot) return;
-	if (!fused || op.nlong > k.c0) k.dot(in, q, pred);                  // (more long rows than chunks: every chunk once instead)
-	else if (op.nlong) {
-		k_pcg_dot_rows<<<dim3(std::min<unsigned>(op.nlong, (unsigned)c->num_cu * 8)), dim3(64), 0, c->stream>>>(in, q, k.n, op.list, op.count, k.part, pred);
-		SPS_LAUNCH_CHECK();
-		++k.launches;
-	}
-}
-
-static const uint32_t *taken_rowptr(spsamd_ctx *c, ConMat &S, Prepared *hp, uint64_t n)
-{
-	if (hp) { prepared_row_structure(c, hp); return hp->rowptr; }
-	if (!S.nnz) return get_zeroed<uint32_t>(c, n + 1);
-	S.nrow = n;
-	return dense_rowptr(c, S, 0);
-}
+// ---------------------------------------------------------------- host: the frame
 
 // (declared in internal.h) S, taken by consolidate_operand, with what its serial chains need
 void row_operator(spsamd_ctx *c, ConMat &S, Prepared *hp, uint64_t nrow, uint64_t ncol, bool long_rows, RowOperator *out)
 {
 	RowOperator &op = *out;
 	op.nrow = nrow; op.ncol = ncol; op.nnz = S.nnz;
-	op.ptr = taken_rowptr(c, S, hp, nrow);
+	if (hp) { prepared_row_structure(c, hp); op.ptr = hp->rowptr; }
+	else if (!S.nnz) op.ptr = get_zeroed<uint32_t>(c, nrow + 1);
+	else { S.nrow = nrow; op.ptr = dense_rowptr(c, S, 0); }
 	op.col = S.col; op.val = S.val;
 	if (S.nnz && long_rows) {
 		const int path = c->tune.spmm_path;
@@ -275,18 +237,17 @@ void check_vector_overlap(spsamd_ctx *c, const spsamd_coo *X, const char *name, 
 		if (ranges_overlap(x, bytes, arr[k], n * (k == 2 ? 8 : 4))) throw Error{SPSAMD_EINVAL, std::string("x overlaps the arrays of ") + name};
 }
 
-// The loop of both entry points.  `hook`: a preconditioner of the caller's own (spsamd_solve_pcg_amg); precond is then
-// PCG_PRECOND_HOOK and M null.
-int pcg_solve(spsamd_ctx *c, const spsamd_coo *A, char transpose, int precond, const spsamd_coo *M, char transpose_M,
-	const double *b, double *x, int mem, double tol, uint64_t max_iter, double *hist_host, size_t hist_capacity,
-	int duplicate_policy, int zero_nan, spsamd_pcg_stats *stats, spsamd_result *res, PcgPrecond *hook)
+bool KrylovCall::open(spsamd_ctx *ctx, const spsamd_coo *A, char transpose, int pre, const spsamd_coo *M, char transpose_M, const double *b,
+	double *xx, int mm, double tol, uint64_t maxit, double *hh, size_t hist_capacity, int duplicate_policy, int zero_nan,
+	spsamd_pcg_stats *ss, spsamd_result *rr, int nparts, size_t state_bytes, PcgPrecond *hk)
 {
+	c = ctx; precond = pre; x = xx; mem = mm; max_iter = maxit; hist_host = hh; stats = ss; res = rr; hook = hk;
 	if (mem != SPSAMD_MEM_HOST && mem != SPSAMD_MEM_DEVICE) throw Error{SPSAMD_EINVAL, "mem of b and x must be SPSAMD_MEM_HOST or SPSAMD_MEM_DEVICE"};
 	if (!(tol >= 0.0) || tol - tol != 0.0) throw Error{SPSAMD_EINVAL, "tol must be finite and not negative"};
 	if ((precond == SPSAMD_PRECOND_LU) != (M != nullptr)) throw Error{SPSAMD_EINVAL, "M goes with SPSAMD_PRECOND_LU, and only with it"};
 	if (duplicate_policy < 0 || duplicate_policy > 2) throw Error{SPSAMD_EINVAL, "bad duplicate_policy"};
 	const int lead = transpose == 'T' ? 1 : 0, lead_m = transpose_M == 'T' ? 1 : 0;
-	const uint64_t n = A->shape0;
+	n = A->shape0;
 	if (A->shape0 != A->shape1) throw Error{SPSAMD_EDIM, "op(A) must be square"};
 	if (M && (M->shape0 != M->shape1 || M->shape0 != n)) throw Error{SPSAMD_EDIM, "op(M) must be square and of op(A)'s order"};
 	if (n && (!b || !x)) throw Error{SPSAMD_EINVAL, "null b or x"};
@@ -301,44 +262,42 @@ int pcg_solve(spsamd_ctx *c, const spsamd_coo *A, char transpose, int precond, c
 	res->shape0 = res->shape1 = n;
 	if (!n) {                                                        // every dot is the fold of nothing: rr = +0.0 <= thresh
 		if (hist_host && hist_capacity) hist_host[0] = 0.0;
-		return SPSAMD_OK;
+		return false;
 	}
 
 	SPS_HIP(hipSetDevice(c->device));
 	c->arena.reset();
-	hipStream_t st = c->stream;
-	SPS_HIP(hipEventRecord(c->ev[EV_BEGIN], st));
+	SPS_HIP(hipEventRecord(c->ev[EV_BEGIN], c->stream));
 	ConMat S, F;
 	Prepared *hpa = nullptr, *hpm = nullptr;
 	consolidate_operand(c, A, lead, lead, duplicate_policy, zero_nan, &S, &hpa);
 	if (M) consolidate_operand(c, M, lead_m, lead_m, duplicate_policy, zero_nan, &F, &hpm);
-	SPS_HIP(hipEventRecord(c->ev[EV_CONSOLIDATED], st));
+	SPS_HIP(hipEventRecord(c->ev[EV_CONSOLIDATED], c->stream));
 	res->nnz_a = S.nnz;
 	res->nnz_b = M ? F.nnz : 0;
 
-	Pcg k;
-	k.c = c; k.n = n; k.c0 = (n + PCG_CHUNK - 1) / PCG_CHUNK; k.unfused = c->tune.pcg_fuse == 1;
-	const uint64_t c1 = (k.c0 + PCG_CHUNK - 1) / PCG_CHUNK;
-	k.part = c->arena.get<double>(k.c0); k.b0 = c->arena.get<double>(c1); k.b1 = c->arena.get<double>(c1);
-	k.st = c->arena.get<PcgState>(1);
-	const uint64_t hcap = !hist_host ? 0 : std::min<uint64_t>(hist_capacity, max_iter == ~0ull ? max_iter : max_iter + 1);
-	k.hist = hcap ? c->arena.get<double>(hcap) : nullptr;
+	// ---- the workspace of the frame (this order fixes workspace_bytes)
+	c0 = (n + PCG_CHUNK - 1) / PCG_CHUNK; unfused = c->tune.pcg_fuse == 1;
+	const uint64_t c1 = (c0 + PCG_CHUNK - 1) / PCG_CHUNK;
+	part0 = c->arena.get<double>(c0);
+	if (nparts == 2) part1 = c->arena.get<double>(c0);
+	b0 = c->arena.get<double>(c1); b1 = c->arena.get<double>(c1);
+	st = (PcgState *)c->arena.alloc(state_bytes);
+	hcap = !hist_host ? 0 : std::min<uint64_t>(hist_capacity, max_iter == ~0ull ? max_iter : max_iter + 1);
+	hist = hcap ? c->arena.get<double>(hcap) : nullptr;
 
 	// ---- the operator: S's row pointer; the long rows' list and the packed rows of k_spmm.hip only where there is a long row
-	RowOperator op;
 	row_operator(c, S, hpa, n, n, true, &op);
 
 	// ---- the preconditioner
-	double *diag = nullptr;
-	TriView tl = {}, tu = {};
-	SolveSchedule local[2], *sched[2] = {nullptr, nullptr};
-	uint32_t analyses = 0;
 	if (precond == SPSAMD_PRECOND_JACOBI) {
 		diag = c->arena.get<double>(n);
 		if (S.nnz) reduce_diag_dense(c, op.ptr, S.col, S.val, n, diag);
 		else fill_zero(c, diag, vbytes);
 	} else if (precond == SPSAMD_PRECOND_LU) {
-		tl.ptr = taken_rowptr(c, F, hpm, n);
+		RowOperator fop;
+		row_operator(c, F, hpm, n, n, false, &fop);                      // (F's row pointer; the solves walk its rows themselves)
+		tl.ptr = fop.ptr;
 		tl.col = F.col; tl.val = F.val; tl.n = n; tl.upper = 0; tl.unit = 1;
 		tu = tl; tu.upper = 1; tu.unit = 0;
 		const TriView *tv[2] = {&tl, &tu};
@@ -353,87 +312,79 @@ int pcg_solve(spsamd_ctx *c, const spsamd_coo *A, char transpose, int precond, c
 		}
 	}
 
-	// ---- the vectors
-	const double *db = to_device(c, b, n, mem);
-	double *dx = x;
-	if (mem == SPSAMD_MEM_HOST) { dx = c->arena.get<double>(n); SPS_HIP(hipMemcpyAsync(dx, x, vbytes, hipMemcpyHostToDevice, st)); }
-	double *r = c->arena.get<double>(n), *p = c->arena.get<double>(n), *q = c->arena.get<double>(n);
-	double *z = precond == SPSAMD_PRECOND_NONE ? r : c->arena.get<double>(n);
-	const bool vec = (((uintptr_t)z | (uintptr_t)p) & 15u) == 0;
-	if (hook) hook->setup(c, op, r, z);
-
-	// ---- bb, thresh; r = b - A x, rr0, hist[0], the stop tests before the first iteration
-	k_pcg_init<<<dim3(1), dim3(1), 0, st>>>(k.st, max_iter, hcap);
+	// ---- b and x; the state
+	db = to_device(c, b, n, mem);
+	dx = x;
+	if (mem == SPSAMD_MEM_HOST) { dx = c->arena.get<double>(n); SPS_HIP(hipMemcpyAsync(dx, x, vbytes, hipMemcpyHostToDevice, c->stream)); }
+	k_pcg_init<<<dim3(1), dim3(1), 0, c->stream>>>(st, (uint32_t)(state_bytes / 8), max_iter, hcap);
 	SPS_LAUNCH_CHECK();
-	k.dot(db, db, nullptr);
-	k.finish<FIN_BB>(true, tol * tol);
-	pcg_spmv(k, op, dx, q, false, nullptr);
-	if (k.unfused) {
-		k_pcg_residual<false><<<dim3(k.chunk_grid()), dim3(PCG_NT), 0, st>>>(db, q, r, n, k.part);
-		SPS_LAUNCH_CHECK();
-		k.dot(r, r, nullptr);
-	} else {
-		k_pcg_residual<true><<<dim3(k.chunk_grid()), dim3(PCG_NT), 0, st>>>(db, q, r, n, k.part);
-		SPS_LAUNCH_CHECK();
-	}
-	k.finish<FIN_RR0>(true);
-	SPS_HIP(hipEventRecord(c->ev[EV_SYMBOLIC], st));
+	return true;
+}
 
-	// ---- the iterations, pcg_check_every of them between two reads of the state
-	const uint64_t every = c->tune.pcg_check_every > 0 ? (uint64_t)c->tune.pcg_check_every : (uint64_t)PCG_CHECK_EVERY;
-	k.launches = 0;
-	uint64_t readbacks = 0, enqueued = 0;
-	PcgState hs;
-	for (;;) {
-		hs = read_back(c, k.st);
-		++readbacks;
-		if (hs.state != PCG_RUNNING) break;
-		const uint64_t batch = std::min<uint64_t>(every, max_iter - enqueued);   // (RUNNING: k < max_iter, and k <= enqueued)
-		for (uint64_t it = 0; it < batch; ++it) {
-			// z = M^-1 r, rz' = dot(r, z), beta, rz
-			if (precond == SPSAMD_PRECOND_JACOBI) {
-				if (k.unfused) k_pcg_jacobi<false><<<dim3(k.chunk_grid()), dim3(PCG_NT), 0, st>>>(r, diag, z, n, k.part, k.st);
-				else k_pcg_jacobi<true><<<dim3(k.chunk_grid()), dim3(PCG_NT), 0, st>>>(r, diag, z, n, k.part, k.st);
-				SPS_LAUNCH_CHECK();
-				++k.launches;
-				if (k.unfused) k.dot(r, z, k.st);
-			} else if (precond == SPSAMD_PRECOND_LU) {
-				k.launches += solve_levels(c, tl, *sched[0], r, 1, z, 1, 1, nullptr);
-				k.launches += solve_levels(c, tu, *sched[1], z, 1, z, 1, 1, nullptr);
-				k.dot(r, z, k.st);
-			} else if (hook) {
-				k.launches += hook->apply();
-				k.dot(r, z, k.st);
-			}
-			k.finish<FIN_RZ>(precond != SPSAMD_PRECOND_NONE);
-			if (vec) k_pcg_direction<true><<<dim3(grid_for((n + 1) / 2)), dim3(256), 0, st>>>(z, p, n, k.st);
-			else k_pcg_direction<false><<<dim3(grid_for(n)), dim3(256), 0, st>>>(z, p, n, k.st);
-			SPS_LAUNCH_CHECK();
-			++k.launches;
-			// q = A p, pq = dot(p, q), alpha
-			pcg_spmv(k, op, p, q, true, k.st);
-			k.finish<FIN_PQ>(true);
-			// x += alpha p, r -= alpha q, rr = dot(r, r), k, hist, the stop tests
-			if (k.unfused) {
-				k_pcg_update<1><<<dim3(k.chunk_grid()), dim3(PCG_NT), 0, st>>>(dx, p, r, q, n, k.part, k.st);
-				SPS_LAUNCH_CHECK();
-				k_pcg_update<2><<<dim3(k.chunk_grid()), dim3(PCG_NT), 0, st>>>(dx, p, r, q, n, k.part, k.st);
-				SPS_LAUNCH_CHECK();
-				k.launches += 2;
-				k.dot(r, r, k.st);
-			} else {
-				k_pcg_update<0><<<dim3(k.chunk_grid()), dim3(PCG_NT), 0, st>>>(dx, p, r, q, n, k.part, k.st);
-				SPS_LAUNCH_CHECK();
-				++k.launches;
-			}
-			k.finish<FIN_RR>(true);
-		}
-		enqueued += batch;
-	}
+void KrylovCall::dot(const double *u, const double *w, double *part, const PcgState *pred)
+{
+	k_pcg_dot<<<dim3(chunk_grid()), dim3(PCG_NT), 0, c->stream>>>(u, w, n, part, pred);
+	SPS_LAUNCH_CHECK();
+	++launches;
+}
 
-	if (mem == SPSAMD_MEM_HOST) SPS_HIP(hipMemcpyAsync(x, dx, vbytes, hipMemcpyDeviceToHost, st));
+// Nothing is allocated here: it runs in every iteration.
+void KrylovCall::spmv(const double *in, double *out, int ndot, const double *u, const PcgState *pred)
+{
+	const int fused = unfused ? 0 : ndot;
+	const dim3 grid(chunk_grid()), nt(PCG_NT);
+	if (fused == 2) k_pcg_spmv<2><<<grid, nt, 0, c->stream>>>(op.ptr, op.col, op.val, in, out, n, op.long_min, u, part0, part1, pred);
+	else if (fused == 1) k_pcg_spmv<1><<<grid, nt, 0, c->stream>>>(op.ptr, op.col, op.val, in, out, n, op.long_min, u, part0, part1, pred);
+	else k_pcg_spmv<0><<<grid, nt, 0, c->stream>>>(op.ptr, op.col, op.val, in, out, n, op.long_min, u, part0, part1, pred);
+	SPS_LAUNCH_CHECK();
+	++launches;
+	if (op.nlong) {
+		spmm_long_rows(c, op.m, op.list, op.count, in, 1, out, 1, 1);
+		++launches;
+	}
+	if (!ndot) return;
+	const double *u0 = ndot == 1 ? u : out, *w0 = ndot == 1 ? out : u;
+	if (!fused || op.nlong > c0) {                                       // (more long rows than chunks: every chunk once instead)
+		dot(u0, w0, part0, pred);
+		if (ndot == 2) dot(out, out, part1, pred);
+	} else if (op.nlong) {
+		k_pcg_dot_rows<<<dim3(std::min<unsigned>(op.nlong, (unsigned)c->num_cu * 8)), dim3(64), 0, c->stream>>>(u0, w0, part0,
+			ndot == 2 ? out : nullptr, out, part1, n, op.list, op.count, pred);
+		SPS_LAUNCH_CHECK();
+		++launches;
+	}
+}
+
+void KrylovCall::residual(const double *b, const double *q, double *r)
+{
+	if (unfused) k_pcg_residual<false><<<dim3(chunk_grid()), dim3(PCG_NT), 0, c->stream>>>(b, q, r, n, part0);
+	else k_pcg_residual<true><<<dim3(chunk_grid()), dim3(PCG_NT), 0, c->stream>>>(b, q, r, n, part0);
+	SPS_LAUNCH_CHECK();
+	if (unfused) dot(r, r, part0, nullptr);
+}
+
+void KrylovCall::precondition(const double *in, double *out, double *part)
+{
+	if (precond == SPSAMD_PRECOND_JACOBI) {
+		const bool fused = part && !unfused;                             // the dot rides in the division
+		if (fused) k_pcg_jacobi<true><<<dim3(chunk_grid()), dim3(PCG_NT), 0, c->stream>>>(in, diag, out, n, part, st);
+		else k_pcg_jacobi<false><<<dim3(chunk_grid()), dim3(PCG_NT), 0, c->stream>>>(in, diag, out, n, part, st);
+		SPS_LAUNCH_CHECK();
+		++launches;
+		if (fused) return;
+	} else if (precond == SPSAMD_PRECOND_LU) {
+		launches += solve_levels(c, tl, *sched[0], in, 1, out, 1, 1, nullptr);
+		launches += solve_levels(c, tu, *sched[1], out, 1, out, 1, 1, nullptr);
+	} else if (hook) launches += hook->apply();
+	else return;
+	if (part) dot(in, out, part, st);
+}
+
+int KrylovCall::close(const PcgState &hs)
+{
+	if (mem == SPSAMD_MEM_HOST) SPS_HIP(hipMemcpyAsync(x, dx, n * sizeof(double), hipMemcpyDeviceToHost, c->stream));
 	const uint64_t nh = std::min<uint64_t>(hs.k + 1, hcap);
-	if (nh) SPS_HIP(hipMemcpyAsync(hist_host, k.hist, nh * sizeof(double), hipMemcpyDeviceToHost, st));
+	if (nh) SPS_HIP(hipMemcpyAsync(hist_host, hist, nh * sizeof(double), hipMemcpyDeviceToHost, c->stream));
 	finish_call(c, res);
 	SPS_HIP(hipEventElapsedTime(&res->ms_consolidate, c->ev[EV_BEGIN], c->ev[EV_CONSOLIDATED]));
 	SPS_HIP(hipEventElapsedTime(&res->ms_symbolic, c->ev[EV_CONSOLIDATED], c->ev[EV_SYMBOLIC]));
@@ -441,10 +392,72 @@ int pcg_solve(spsamd_ctx *c, const spsamd_coo *A, char transpose, int precond, c
 	if (stats) {
 		stats->iterations = hs.k; stats->reason = hs.state;
 		stats->bb = hs.bb; stats->rr0 = hs.rr0; stats->rr = hs.rr;
-		stats->launches = k.launches; stats->readbacks = readbacks; stats->analyses = analyses;
+		stats->launches = launches; stats->readbacks = readbacks; stats->analyses = analyses;
 		stats->ms_setup = res->ms_consolidate + res->ms_symbolic; stats->ms_iterate = res->ms_numeric;
 	}
 	return SPSAMD_OK;
+}
+
+// ---------------------------------------------------------------- host: conjugate gradients
+
+template <int KIND> static void pcg_finish(KrylovCall &k, bool have_part, double tol2 = 0.0)
+{
+	k_pcg_finish<KIND><<<dim3(1), dim3(PCG_FINISH_NT), 0, k.c->stream>>>(have_part ? k.part0 : nullptr, k.c0, k.b0, k.b1, k.st, k.hist, tol2);
+	SPS_LAUNCH_CHECK();
+	++k.launches;
+}
+
+// The loop of both entry points.  `hook`: a preconditioner of the caller's own (spsamd_solve_pcg_amg); precond is then
+// PCG_PRECOND_HOOK and M null.
+int pcg_solve(spsamd_ctx *c, const spsamd_coo *A, char transpose, int precond, const spsamd_coo *M, char transpose_M,
+	const double *b, double *x, int mem, double tol, uint64_t max_iter, double *hist_host, size_t hist_capacity,
+	int duplicate_policy, int zero_nan, spsamd_pcg_stats *stats, spsamd_result *res, PcgPrecond *hook)
+{
+	KrylovCall k;
+	if (!k.open(c, A, transpose, precond, M, transpose_M, b, x, mem, tol, max_iter, hist_host, hist_capacity, duplicate_policy, zero_nan,
+			stats, res, 1, sizeof(PcgState), hook)) return SPSAMD_OK;
+	const uint64_t n = k.n;
+	hipStream_t st = c->stream;
+	double *r = c->arena.get<double>(n), *p = c->arena.get<double>(n), *q = c->arena.get<double>(n);
+	double *z = precond == SPSAMD_PRECOND_NONE ? r : c->arena.get<double>(n);
+	const bool vec = (((uintptr_t)z | (uintptr_t)p) & 15u) == 0;
+	const dim3 grid(k.chunk_grid()), nt(PCG_NT);
+	if (hook) hook->setup(c, k.op, r, z);
+
+	// ---- bb, thresh; r = b - A x, rr0, hist[0], the stop tests before the first iteration
+	k.dot(k.db, k.db, k.part0, nullptr);
+	pcg_finish<FIN_BB>(k, true, tol * tol);
+	k.spmv(k.dx, q, 0, nullptr, nullptr);
+	k.residual(k.db, q, r);
+	pcg_finish<FIN_RR0>(k, true);
+
+	const PcgState hs = k.iterate([&] {
+		// z = M^-1 r, rz' = dot(r, z), beta, rz
+		k.precondition(r, z, k.part0);
+		pcg_finish<FIN_RZ>(k, precond != SPSAMD_PRECOND_NONE);
+		if (vec) k_pcg_direction<true><<<dim3(grid_for((n + 1) / 2)), dim3(256), 0, st>>>(z, p, n, k.st);
+		else k_pcg_direction<false><<<dim3(grid_for(n)), dim3(256), 0, st>>>(z, p, n, k.st);
+		SPS_LAUNCH_CHECK();
+		++k.launches;
+		// q = A p, pq = dot(p, q), alpha
+		k.spmv(p, q, 1, p, k.st);
+		pcg_finish<FIN_PQ>(k, true);
+		// x += alpha p, r -= alpha q, rr = dot(r, r), k, hist, the stop tests
+		if (k.unfused) {
+			k_pcg_update<1><<<grid, nt, 0, st>>>(k.dx, p, r, q, n, k.part0, k.st);
+			SPS_LAUNCH_CHECK();
+			k_pcg_update<2><<<grid, nt, 0, st>>>(k.dx, p, r, q, n, k.part0, k.st);
+			SPS_LAUNCH_CHECK();
+			k.launches += 2;
+			k.dot(r, r, k.part0, k.st);
+		} else {
+			k_pcg_update<0><<<grid, nt, 0, st>>>(k.dx, p, r, q, n, k.part0, k.st);
+			SPS_LAUNCH_CHECK();
+			++k.launches;
+		}
+		pcg_finish<FIN_RR>(k, true);
+	});
+	return k.close(hs);
 }
 
 int solve_pcg(spsamd_ctx *c, const spsamd_coo *A, char transpose, int precond, const spsamd_coo *M, char transpose_M,

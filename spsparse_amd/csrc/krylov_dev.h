@@ -1,11 +1,14 @@
 // krylov_dev.h -- what the device loops of k_krylov.hip (conjugate gradients) and k_bicgstab.hip (BiCGStab) share: the state
-// word and the scalars of a loop in device memory, and the one reduction shape of every dot product (the fold of
-// include/spsparse_amd.h).  Device code only; included after devutil.h and x86fp.h.
+// word and the scalars of a loop in device memory, the one reduction shape of every dot product (the fold of
+// include/spsparse_amd.h), a row's serial chain, and the frame of a call (KrylovCall; its members
+// and the vector kernels they launch are k_krylov.hip's).  HIP only.
 #pragma once
 
 #include "internal.h"
 #include "devutil.h"
 #include "x86fp.h"
+
+#include <algorithm>
 
 namespace spsamd {
 
@@ -46,6 +49,42 @@ __device__ __forceinline__ double chunk_partial(uint64_t g, uint64_t n, Term ter
 	return a;
 }
 
+// chunk_partial for two folds of one pass: term(e, &t0, &t1) gives element e's term of each
+template <class Term>
+__device__ __forceinline__ void chunk_partial2(uint64_t g, uint64_t n, Term term, double *a0, double *a1)
+{
+	const uint64_t base = g * PCG_CHUNK + lane_id();
+	double t0[PCG_CHUNK / 64], t1[PCG_CHUNK / 64];
+#pragma unroll
+	for (int k = 0; k < PCG_CHUNK / 64; ++k) {
+		const uint64_t e = base + (uint64_t)k * 64;
+		t0[k] = t1[k] = 0.0;
+		if (e < n) term(e, &t0[k], &t1[k]);
+	}
+	double a = 0.0, b = 0.0;
+#pragma unroll
+	for (int k = 0; k < PCG_CHUNK / 64; ++k)
+		if (base + (uint64_t)k * 64 < n) { a = ref_add(a, t0[k]); b = ref_add(b, t1[k]); }
+#pragma unroll
+	for (int s = 32; s >= 1; s >>= 1) {
+		const double oa = __shfl_down(a, s, 64), ob = __shfl_down(b, s, 64);
+		if (lane_id() < (unsigned)s) { a = ref_add(a, oa); b = ref_add(b, ob); }
+	}
+	*a0 = a; *a1 = b;
+}
+
+// row i's serial chain over S; +0.0 for a row of more than long_min tuples (k_spmm.hip's wave kernel adds its chain in the
+// next launch)
+__device__ __forceinline__ double row_chain(const uint32_t *__restrict__ ptr, const int32_t *__restrict__ col, const double *__restrict__ val,
+	const double *__restrict__ in, uint64_t i, uint32_t long_min)
+{
+	double acc = 0.0;
+	const uint32_t b = ptr[i], e = ptr[i + 1];
+	if (e - b <= long_min)
+		for (uint32_t k = b; k < e; ++k) acc = ref_add(acc, ref_mul(val[k], in[(uint32_t)col[k]]));
+	return acc;
+}
+
 // the chunk of this wave, or false past the last one
 __device__ __forceinline__ bool my_chunk(uint64_t n, uint64_t *g)
 {
@@ -73,5 +112,72 @@ __device__ inline double block_fold(const double *part, uint64_t m, double *b0, 
 	}
 	return *s_out;
 }
+
+// ---------------------------------------------------------------- the frame of a call (members: k_krylov.hip)
+
+// What solve_pcg, solve_pcg_amg and solve_bicgstab do alike around their iteration bodies.  A loop open()s the call, takes
+// its own vectors (then hook->setup), enqueues its set-up with dot / spmv / residual and its own finish kernels, hands its
+// iteration body to iterate() and close()s.  Every launch of an iteration goes through a member or bumps `launches`.
+struct KrylovCall {
+	spsamd_ctx *c = nullptr;
+	uint64_t n = 0, c0 = 0;                    // the order; the level-0 chunks of a vector
+	bool unfused = false;                      // pcg_fuse 1: every vector operation and every dot a launch of its own
+	int precond = 0;
+	double *part0 = nullptr, *part1 = nullptr; // level-0 partials (part1 under nparts 2)
+	double *b0 = nullptr, *b1 = nullptr;       // block_fold's levels
+	double *hist = nullptr;
+	PcgState *st = nullptr;                    // the loop's state struct: a PcgState, or one derived from it
+	RowOperator op;                            // S
+	const double *db = nullptr;                // b and x on the device
+	double *dx = nullptr;
+	uint64_t launches = 0;
+
+	// The checks (but the range of precond), the zeroing of res / stats, both operands, the workspace of the frame, S's
+	// row_operator, the preconditioner's data, b and x on the device, the state's init.  False: n == 0, the call is over.
+	bool open(spsamd_ctx *c, const spsamd_coo *A, char transpose, int precond, const spsamd_coo *M, char transpose_M, const double *b,
+		double *x, int mem, double tol, uint64_t max_iter, double *hist_host, size_t hist_capacity, int duplicate_policy, int zero_nan,
+		spsamd_pcg_stats *stats, spsamd_result *res, int nparts, size_t state_bytes, PcgPrecond *hook);
+	// the partials of dot(u, w)
+	void dot(const double *u, const double *w, double *part, const PcgState *pred);
+	// out = S in.  ndot 1: + the partials of dot(u, out) in part0 | 2: of dot(out, u) in part0 and dot(out, out) in part1
+	void spmv(const double *in, double *out, int ndot, const double *u, const PcgState *pred);
+	// r = b - q, and the partials of dot(r, r) in part0 (the set-up: no state is read)
+	void residual(const double *b, const double *q, double *r);
+	// out = M^-1 in (the hook: on the pair of its setup), and where `part` is given the partials of dot(in, out).
+	// Nothing is launched without a preconditioner.
+	void precondition(const double *in, double *out, double *part);
+	// the three event times and stats, x and the history back with the caller
+	int close(const PcgState &hs);
+
+	unsigned chunk_grid() const { return (unsigned)((c0 + PCG_NT / 64 - 1) / (PCG_NT / 64)); }
+
+	// The end of the set-up; then `one()` enqueues an iteration, pcg_check_every of them between two reads of the state
+	template <class Body> PcgState iterate(Body one)
+	{
+		SPS_HIP(hipEventRecord(c->ev[EV_SYMBOLIC], c->stream));
+		const uint64_t every = c->tune.pcg_check_every > 0 ? (uint64_t)c->tune.pcg_check_every : (uint64_t)PCG_CHECK_EVERY;
+		launches = 0;
+		for (uint64_t enqueued = 0;;) {
+			const PcgState hs = read_back(c, st);
+			++readbacks;
+			if (hs.state != PCG_RUNNING) return hs;
+			const uint64_t batch = std::min<uint64_t>(every, max_iter - enqueued);   // (RUNNING: k < max_iter, and k <= enqueued)
+			for (uint64_t it = 0; it < batch; ++it) one();
+			enqueued += batch;
+		}
+	}
+
+	// ---- what only the members use
+	double *diag = nullptr;                    // Jacobi
+	TriView tl = {}, tu = {};                  // LU: F's triangles and their schedules
+	SolveSchedule local[2], *sched[2] = {nullptr, nullptr};
+	PcgPrecond *hook = nullptr;
+	uint64_t max_iter = 0, hcap = 0, readbacks = 0;
+	uint32_t analyses = 0;
+	int mem = 0;
+	double *x = nullptr, *hist_host = nullptr; // the caller's
+	spsamd_pcg_stats *stats = nullptr;
+	spsamd_result *res = nullptr;
+};
 
 } // namespace spsamd

@@ -152,11 +152,15 @@ def test_the_reference_solves_poisson(precond):
 
 
 def test_no_krylov_kernel_uses_scratch():
-    """Every kernel of k_krylov.hip in the built library: no scratch, no spill (resource figures only, no GPU)."""
+    """Every kernel of k_krylov.hip in the built library -- the loop's own and the vector kernels every Krylov loop launches
+    through the frame, k_pcg_spmv in its three forms: no scratch, no spill (resource figures only, no GPU)."""
     from scripts import kernel_resources
     from spsparse_amd import build
-    found = {name: f for name, f in kernel_resources.library_kernels(build.build()).items() if "k_pcg_" in name}
-    want = ("dot", "residual", "jacobi", "spmv", "direction", "update", "dot_rows", "init", "finish")
+    every = kernel_resources.library_kernels(build.build())
+    found = {name: f for name, f in every.items() if "k_pcg_" in name}
+    want = ("dot", "residual", "jacobi", "spmvILi0", "spmvILi1", "spmvILi2", "direction", "update", "dot_rows", "init", "finish")
     assert all(any("k_pcg_" + k in name for name in found) for k in want), sorted(found)
+    twins = [name for name in every for k in ("dot", "residual", "jacobi", "spmv", "init") if "k_bicg_" + k in name]
+    assert not twins, twins                                                # the shared kernels exist once
     for name, f in found.items():
         assert f["scratch"] == 0 and f["vgpr_spill"] == 0, (name, f)
