@@ -250,6 +250,8 @@ const char *spsamd_version(void);
  *                                     section 23)
  *   pcg_fuse        1                 solve_pcg, solve_bicgstab: every vector operation and every dot product in a launch of its own
  *                                     (default: a dot's first level rides in the kernel that produces its vector)
+ *   gmres_path      1                 solve_gmres: every dot product through the frame's dot kernel with a fold of its own, and every
+ *                                     w = w - coef * v a launch of its own (default: the block kernels)
  *   amg_path        1 | 2             amg_apply, solve_pcg_amg: 1 every level of the cycle in launches of its own | 2 the whole
  *                                     hierarchy in the one launch of the fused tail, whatever its levels' orders (default: the
  *                                     levels from the first one on from which none has more than amg_fuse_rows rows)
@@ -969,6 +971,73 @@ int spsamd_solve_bicgstab(spsamd_ctx *ctx, const spsamd_coo *A, char transpose,
 	int precond, const spsamd_coo *M /* PRECOND_LU only, else NULL */, char transpose_M,
 	const double *b, double *x /* in: x0, out: the iterate at the stop */, int mem,
 	double tol, uint64_t max_iter,
+	double *hist_host /* may be NULL */, size_t hist_capacity,
+	int duplicate_policy, int zero_nan,
+	spsamd_pcg_stats *stats /* may be NULL */, spsamd_result *result /* may be NULL */);
+
+/*
+ * Solve op(A) x = b for an unsymmetric op(A) by right-preconditioned restarted GMRES(m), m = restart, one right-hand side,
+ * the whole loop on the device.  Everything around the loop is spsamd_solve_pcg's and is not restated:
+ * the operands and their intake (S of A, F of M), b, x and mem, the overlap rules, the three preconditioners, dot, fold,
+ * q = A p, M^-1, usable, the NaN and rounding rules (no FMA, true divisions), hist_host, stats (the same struct and
+ * SPSAMD_PCG_* reasons), result, the SPSAMD_EINVAL / SPSAMD_EDIM cases with x untouched, and n == 0.  One more
+ * SPSAMD_EINVAL: restart == 0 or restart > SPSAMD_GMRES_MAX_RESTART.  stats->iterations counts Arnoldi steps, and
+ * stats->readbacks - 1 is the number of cycles.  Square roots are correctly rounded IEEE square roots with spsamd_reduce's
+ * rules for a NaN, a negative operand and -0.0.  The Arnoldi step is classical Gram-Schmidt done twice, the Hessenberg
+ * matrix is kept triangular by Givens rotations.  Every value returned -- x, hist, iterations, reason, bb, rr0, rr -- is
+ * defined by this loop, bit for bit; every product, sum and difference is rounded on its own:
+ *
+ *       bb = dot(b, b);  thresh = (tol * tol) * bb
+ *       q = A x;  r_e = b_e - q_e;  rr = dot(r, r);  k = 0;  hist[0] = rr;  rr0 = rr
+ *       cycle:
+ *           if rr <= thresh:        stop CONVERGED        (a NaN compares false)
+ *           if k == max_iter:       stop MAXITER
+ *           if not usable(rr):      stop BREAKDOWN
+ *           beta = sqrt(rr);  v_0 = r / beta (element by element);  g_0 = beta;  j = 0;  broken = false
+ *           step:
+ *               z = M^-1 v_j;  w = A z
+ *               for i = 0..j:  h_i = dot(v_i, w)                      (all on the same w: classical Gram-Schmidt)
+ *               for i = 0..j ascending:  w_e = w_e - h_i * v_i[e]
+ *               for i = 0..j:  d_i = dot(v_i, w)                      (the second pass)
+ *               for i = 0..j ascending:  w_e = w_e - d_i * v_i[e];   h_i = h_i + d_i
+ *               ww = dot(w, w);  hn = sqrt(ww)
+ *               for i = 0..j-1:  t = c_i*h_i + s_i*h_{i+1};  h_{i+1} = c_i*h_{i+1} - s_i*h_i;  h_i = t
+ *               den = sqrt(h_j*h_j + hn*hn)
+ *               if not usable(den):  broken = true;  goto end     (the step is discarded: k and j stay)
+ *               c_j = h_j / den;  s_j = hn / den;  R[i][j] = h_i for i < j;  R[j][j] = den
+ *               g_{j+1} = -(s_j * g_j);  g_j = c_j * g_j
+ *               k = k + 1;  j = j + 1;  est = g_j * g_j;  hist[k] = est
+ *               if est <= thresh or j == m or k == max_iter or not usable(ww):
+ *                   if ww is NaN or Inf:  broken = true
+ *                   goto end
+ *               v_j = w / hn (element by element);  goto step
+ *           end:
+ *               if j > 0:
+ *                   for i = j-1 .. 0:  a = g_i;  for l = i+1 .. j-1 ascending:  a = a - R[i][l]*y_l;   y_i = a / R[i][i]
+ *                   u_e = +0.0;  for i = 0..j-1 ascending:  u_e = u_e + y_i * v_i[e]
+ *                   z = M^-1 u;  x_e = x_e + z_e
+ *                   q = A x;  r_e = b_e - q_e;  rr = dot(r, r);  hist[k] = rr       (the true value replaces the estimate)
+ *               if broken:  stop BREAKDOWN
+ *               goto cycle
+ *
+ *   - CONVERGED is only ever decided on dot(b - A x, b - A x) of the returned x.
+ *   - hist[k] inside a cycle is the Givens estimate of the squared residual norm; at a cycle's last step it is the true value.
+ *   - Stagnation (a cycle that does not lower rr) ends in MAXITER.
+ *   - Under SPSAMD_PRECOND_NONE z is its input, with no copy.
+ *   - An exactly solved system (ww == 0) ends its cycle through est == 0 <= thresh.
+ *   - The negation of g_{j+1} flips the sign bit, of a NaN too.
+ *   - Between two reads of the device state the host enqueues one whole cycle: min(m, max_iter - k) steps and one cycle
+ *     end.  Step kernels after an in-cycle end are idle, the cycle-end kernels run once.  The knobs pcg_check_every and
+ *     pcg_fuse are not read by this call; gmres_path changes launches, never a returned bit.
+ *   - The workspace holds the m basis vectors v_0 .. v_{m-1} and up to three more vectors of n doubles beside the frame's;
+ *     SPSAMD_ENOMEM where that does not fit.  Nothing is allocated inside the loop.
+ * Returns when x is complete.
+ */
+#define SPSAMD_GMRES_MAX_RESTART 256
+int spsamd_solve_gmres(spsamd_ctx *ctx, const spsamd_coo *A, char transpose,
+	int precond, const spsamd_coo *M /* PRECOND_LU only, else NULL */, char transpose_M,
+	const double *b, double *x /* in: x0, out: the iterate at the stop */, int mem,
+	double tol, uint64_t max_iter, uint32_t restart,
 	double *hist_host /* may be NULL */, size_t hist_capacity,
 	int duplicate_policy, int zero_nan,
 	spsamd_pcg_stats *stats /* may be NULL */, spsamd_result *result /* may be NULL */);

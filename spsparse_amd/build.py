@@ -17,7 +17,7 @@ CSRC = os.path.join(HERE, "csrc")
 VARIANT = os.environ.get("SPSAMD_VARIANT", "")
 LIBDIR = os.path.join(HERE, "lib", VARIANT) if VARIANT else os.path.join(HERE, "lib")
 LIB = os.path.join(LIBDIR, "libspsparse_amd.so")
-SOURCES = ["prims.hip", "operand.hip", "sink.hip", "consolidate.hip", "spgemm.hip", "symbolic_heavy.hip", "k_light.hip", "k_hash.hip", "k_few.hip", "k_dense.hip", "k_tiles.hip", "k_spmm.hip", "k_add.hip", "k_stream.hip", "k_masked.hip", "k_sampled.hip", "k_select.hip", "k_extract.hip", "k_reduce.hip", "k_emult.hip", "k_solve.hip", "k_factor.hip", "k_color.hip", "k_aggregate.hip", "k_krylov.hip", "k_bicgstab.hip", "k_amg.hip",
+SOURCES = ["prims.hip", "operand.hip", "sink.hip", "consolidate.hip", "spgemm.hip", "symbolic_heavy.hip", "k_light.hip", "k_hash.hip", "k_few.hip", "k_dense.hip", "k_tiles.hip", "k_spmm.hip", "k_add.hip", "k_stream.hip", "k_masked.hip", "k_sampled.hip", "k_select.hip", "k_extract.hip", "k_reduce.hip", "k_emult.hip", "k_solve.hip", "k_factor.hip", "k_color.hip", "k_aggregate.hip", "k_krylov.hip", "k_bicgstab.hip", "k_gmres.hip", "k_amg.hip",
            "workload.hip", "capi.hip", "dist.hip"]
 HEADERS = ["internal.h", "devutil.h", "bank_layout.h", "spgemm_dev.h", "spgemm_host.h", "spgemm_hash.h", "workload_common.h", "x86fp.h", "krylov_dev.h", os.path.join("..", "..", "include", "spsparse_amd.h")]
 # -ffp-contract=off: products and sums are rounded separately like the

@@ -58,6 +58,8 @@ agg_fuse_rows, agg_wave_deg = 1024, 32
 PRECOND_NONE, PRECOND_JACOBI, PRECOND_LU = 0, 1, 2
 PCG_CONVERGED, PCG_MAXITER, PCG_BREAKDOWN = 0, 1, 2
 pcg_check_every, pcg_chunk = 8, 1024
+# solve_gmres: the largest restart length
+GMRES_MAX_RESTART = 256
 # amg_apply, solve_pcg_amg: the default of the amg_fuse_rows knob and the most levels of a hierarchy
 amg_fuse_rows, amg_max_levels = 1024, 32
 
@@ -174,7 +176,7 @@ SYMBOLS = ["spsamd_ctx_create", "spsamd_ctx_destroy", "spsamd_last_error", "spsa
            "spsamd_multiply_dense", "spsamd_add", "spsamd_multiply_stream", "spsamd_multiply_masked",
            "spsamd_multiply_sampled", "spsamd_select", "spsamd_extract", "spsamd_reduce", "spsamd_emult", "spsamd_solve_tri",
            "spsamd_factor_ilu0", "spsamd_color", "spsamd_solve_pcg", "spsamd_aggregate",
-           "spsamd_amg_apply", "spsamd_solve_pcg_amg", "spsamd_solve_bicgstab"]
+           "spsamd_amg_apply", "spsamd_solve_pcg_amg", "spsamd_solve_bicgstab", "spsamd_solve_gmres"]
 
 _lib = None
 
@@ -241,6 +243,7 @@ def load():
     L.spsamd_solve_pcg.argtypes = [C.c_void_p, P(Coo), C.c_char, C.c_int, P(Coo), C.c_char, C.c_void_p, C.c_void_p, C.c_int,
                                    C.c_double, C.c_uint64, C.c_void_p, C.c_size_t, C.c_int, C.c_int, P(PcgStats), P(Result)]
     L.spsamd_solve_bicgstab.argtypes = L.spsamd_solve_pcg.argtypes
+    L.spsamd_solve_gmres.argtypes = L.spsamd_solve_pcg.argtypes[:11] + [C.c_uint32] + L.spsamd_solve_pcg.argtypes[11:]
     L.spsamd_amg_apply.argtypes = [C.c_void_p, P(AmgLevel), C.c_size_t, P(AmgParams), C.c_void_p, C.c_void_p, C.c_int,
                                    C.c_int, C.c_int, P(AmgStats), P(Result)]
     L.spsamd_solve_pcg_amg.argtypes = [C.c_void_p, P(AmgLevel), C.c_size_t, P(AmgParams), C.c_void_p, C.c_void_p, C.c_int,
@@ -698,9 +701,19 @@ class Context:
         return self._krylov(self.L.spsamd_solve_bicgstab, A, b, x, precond, M, transpose, transpose_M, tol, max_iter,
                             hist_capacity, duplicate_policy, zero_nan, result)
 
+    def solve_gmres(self, A, b, x=None, precond=PRECOND_NONE, M=None, transpose='.', transpose_M='.', tol=1e-8,
+                    max_iter=1000, restart=30, hist_capacity=None, duplicate_policy=ADD, zero_nan=False, result=None):
+        """spsamd_solve_gmres: op(A) x = b for an unsymmetric op(A) by right-preconditioned restarted GMRES(restart), bit
+        for bit the loop of the header; CONVERGED is decided on the recomputed b - A x alone.  The other arguments and the
+        returned (x, hist, PcgStats) are solve_pcg's: iterations counts Arnoldi steps, readbacks - 1 the cycles, and inside
+        a cycle hist holds the estimate of dot(r, r), at a cycle's last step the true value."""
+        return self._krylov(self.L.spsamd_solve_gmres, A, b, x, precond, M, transpose, transpose_M, tol, max_iter,
+                            hist_capacity, duplicate_policy, zero_nan, result, (int(restart),))
+
     def _krylov(self, call, A, b, x, precond, M, transpose, transpose_M, tol, max_iter, hist_capacity, duplicate_policy,
-                zero_nan, result):
-        """The arguments of solve_pcg / solve_bicgstab as the C ABI takes them, the call, and what both return."""
+                zero_nan, result, loop_args=()):
+        """The arguments of solve_pcg / solve_bicgstab / solve_gmres as the C ABI takes them (loop_args: those a loop adds
+        behind max_iter), the call, and what all return."""
         pb, _ldb, nb, mb = _dense_arg(b, "b", writable=False)
         if x is None:
             if mb == MEM_HOST:
@@ -720,8 +733,8 @@ class Context:
         hist = np.empty(max(cap, 1), np.float64)
         st = PcgStats()
         self._check(call(self.h, C.byref(A), transpose.encode(), int(precond), None if M is None else C.byref(M),
-                         transpose_M.encode(), pb, px, mb, float(tol), int(max_iter), hist.ctypes.data if cap else None, cap,
-                         duplicate_policy, int(zero_nan), C.byref(st), None if result is None else C.byref(result)))
+                         transpose_M.encode(), pb, px, mb, float(tol), int(max_iter), *loop_args, hist.ctypes.data if cap else None,
+                         cap, duplicate_policy, int(zero_nan), C.byref(st), None if result is None else C.byref(result)))
         return x, hist[:min(int(st.iterations) + 1, cap)].copy(), st
 
     def _amg_args(self, levels, params, b, x, zero_x):

@@ -50,8 +50,8 @@ extern "C" int spsamd_ctx_create(spsamd_ctx **out, int device, void *hip_stream)
 	if (hipStreamCreateWithFlags(&c->side2, hipStreamNonBlocking) != hipSuccess) { spsamd_ctx_destroy(c); return SPSAMD_EHIP; }
 	for (auto &e : c->ev_side2) if (hipEventCreateWithFlags(&e, hipEventDisableTiming) != hipSuccess) { spsamd_ctx_destroy(c); return SPSAMD_EHIP; }
 	// developer knobs: the environment is consulted here and nowhere else
-	static const char *const knobs[] = {"window", "cell_cap", "dense_min", "no_tiles", "xcd", "emit_path", "light_path", "no_wmajor", "direct_min", "tiles_v1", "long_cap", "long_dense_min", "few_max", "index_budget_mb", "trace", "light_two_pass", "spmm_path", "spmm_long_min", "add_path", "masked_path", "sampled_path", "select_path", "extract_path", "reduce_path", "emult_path", "tile_walk", "solve_path", "solve_row", "solve_fuse_rows", "factor_path", "factor_row", "factor_fuse_rows", "factor_serial_work", "factor_lds_row", "color_path", "color_row", "color_fuse_rows", "color_wave_deg", "agg_path", "agg_row", "agg_fuse_rows", "agg_wave_deg", "agg_per_rows", "pcg_check_every", "pcg_fuse", "amg_path", "amg_fuse_rows"};
-	static const char *const envs[] = {"SPSAMD_W", "SPSAMD_CELL_CAP", "SPSAMD_DENSE_MIN", "SPSAMD_NO_TILES", "SPSAMD_XCD", "SPSAMD_EMIT_PATH", "SPSAMD_LIGHT_PATH", "SPSAMD_NO_WMAJOR", "SPSAMD_DIRECT_MIN", "SPSAMD_TILES_V1", "SPSAMD_LONG_CAP", "SPSAMD_LONG_DENSE_MIN", "SPSAMD_FEW_MAX", "SPSAMD_INDEX_BUDGET_MB", "SPSAMD_TRACE", "SPSAMD_LIGHT_TWO_PASS", "SPSAMD_SPMM_PATH", "SPSAMD_SPMM_LONG_MIN", "SPSAMD_ADD_PATH", "SPSAMD_MASKED_PATH", "SPSAMD_SAMPLED_PATH", "SPSAMD_SELECT_PATH", "SPSAMD_EXTRACT_PATH", "SPSAMD_REDUCE_PATH", "SPSAMD_EMULT_PATH", "SPSAMD_TILE_WALK", "SPSAMD_SOLVE_PATH", "SPSAMD_SOLVE_ROW", "SPSAMD_SOLVE_FUSE_ROWS", "SPSAMD_FACTOR_PATH", "SPSAMD_FACTOR_ROW", "SPSAMD_FACTOR_FUSE_ROWS", "SPSAMD_FACTOR_SERIAL_WORK", "SPSAMD_FACTOR_LDS_ROW", "SPSAMD_COLOR_PATH", "SPSAMD_COLOR_ROW", "SPSAMD_COLOR_FUSE_ROWS", "SPSAMD_COLOR_WAVE_DEG", "SPSAMD_AGG_PATH", "SPSAMD_AGG_ROW", "SPSAMD_AGG_FUSE_ROWS", "SPSAMD_AGG_WAVE_DEG", "SPSAMD_AGG_PER_ROWS", "SPSAMD_PCG_CHECK_EVERY", "SPSAMD_PCG_FUSE", "SPSAMD_AMG_PATH", "SPSAMD_AMG_FUSE_ROWS"};
+	static const char *const knobs[] = {"window", "cell_cap", "dense_min", "no_tiles", "xcd", "emit_path", "light_path", "no_wmajor", "direct_min", "tiles_v1", "long_cap", "long_dense_min", "few_max", "index_budget_mb", "trace", "light_two_pass", "spmm_path", "spmm_long_min", "add_path", "masked_path", "sampled_path", "select_path", "extract_path", "reduce_path", "emult_path", "tile_walk", "solve_path", "solve_row", "solve_fuse_rows", "factor_path", "factor_row", "factor_fuse_rows", "factor_serial_work", "factor_lds_row", "color_path", "color_row", "color_fuse_rows", "color_wave_deg", "agg_path", "agg_row", "agg_fuse_rows", "agg_wave_deg", "agg_per_rows", "pcg_check_every", "pcg_fuse", "amg_path", "amg_fuse_rows", "gmres_path"};
+	static const char *const envs[] = {"SPSAMD_W", "SPSAMD_CELL_CAP", "SPSAMD_DENSE_MIN", "SPSAMD_NO_TILES", "SPSAMD_XCD", "SPSAMD_EMIT_PATH", "SPSAMD_LIGHT_PATH", "SPSAMD_NO_WMAJOR", "SPSAMD_DIRECT_MIN", "SPSAMD_TILES_V1", "SPSAMD_LONG_CAP", "SPSAMD_LONG_DENSE_MIN", "SPSAMD_FEW_MAX", "SPSAMD_INDEX_BUDGET_MB", "SPSAMD_TRACE", "SPSAMD_LIGHT_TWO_PASS", "SPSAMD_SPMM_PATH", "SPSAMD_SPMM_LONG_MIN", "SPSAMD_ADD_PATH", "SPSAMD_MASKED_PATH", "SPSAMD_SAMPLED_PATH", "SPSAMD_SELECT_PATH", "SPSAMD_EXTRACT_PATH", "SPSAMD_REDUCE_PATH", "SPSAMD_EMULT_PATH", "SPSAMD_TILE_WALK", "SPSAMD_SOLVE_PATH", "SPSAMD_SOLVE_ROW", "SPSAMD_SOLVE_FUSE_ROWS", "SPSAMD_FACTOR_PATH", "SPSAMD_FACTOR_ROW", "SPSAMD_FACTOR_FUSE_ROWS", "SPSAMD_FACTOR_SERIAL_WORK", "SPSAMD_FACTOR_LDS_ROW", "SPSAMD_COLOR_PATH", "SPSAMD_COLOR_ROW", "SPSAMD_COLOR_FUSE_ROWS", "SPSAMD_COLOR_WAVE_DEG", "SPSAMD_AGG_PATH", "SPSAMD_AGG_ROW", "SPSAMD_AGG_FUSE_ROWS", "SPSAMD_AGG_WAVE_DEG", "SPSAMD_AGG_PER_ROWS", "SPSAMD_PCG_CHECK_EVERY", "SPSAMD_PCG_FUSE", "SPSAMD_AMG_PATH", "SPSAMD_AMG_FUSE_ROWS", "SPSAMD_GMRES_PATH"};
 	static_assert(sizeof knobs / sizeof knobs[0] == sizeof envs / sizeof envs[0], "one environment variable per knob");
 	for (size_t k = 0; k < sizeof knobs / sizeof knobs[0]; ++k)
 		if (const char *e = getenv(envs[k])) (void)spsamd_ctx_set_tuning(c, knobs[k], atol(e));
@@ -81,7 +81,7 @@ extern "C" int spsamd_ctx_set_tuning(spsamd_ctx *c, const char *name, long value
 		{"agg_path", &c->tune.agg_path}, {"agg_row", &c->tune.agg_row}, {"agg_fuse_rows", &c->tune.agg_fuse_rows},
 		{"agg_wave_deg", &c->tune.agg_wave_deg}, {"agg_per_rows", &c->tune.agg_per_rows},
 		{"pcg_check_every", &c->tune.pcg_check_every}, {"pcg_fuse", &c->tune.pcg_fuse},
-		{"amg_path", &c->tune.amg_path}, {"amg_fuse_rows", &c->tune.amg_fuse_rows},
+		{"gmres_path", &c->tune.gmres_path}, {"amg_path", &c->tune.amg_path}, {"amg_fuse_rows", &c->tune.amg_fuse_rows},
 	};
 	for (auto &t : tab) if (!std::strcmp(t.n, name)) { *t.p = (int)value; return SPSAMD_OK; }
 	c->last_error = std::string("unknown tuning knob: ") + name;
@@ -623,6 +623,21 @@ extern "C" int spsamd_solve_bicgstab(spsamd_ctx *c, const spsamd_coo *A, char tr
 		if (!A) throw Error{SPSAMD_EINVAL, "null operand"};
 		spsamd_result local;
 		return solve_bicgstab(c, A, transpose, precond, M, transpose_M, b, x, mem, tol, max_iter, hist_host, hist_capacity,
+			duplicate_policy, zero_nan, stats, res ? res : &local);
+	)
+}
+
+// op(A) x = b by right-preconditioned restarted GMRES(restart), the loop on the device (k_gmres.hip).  Workspace only, like
+// spsamd_solve_pcg.
+extern "C" int spsamd_solve_gmres(spsamd_ctx *c, const spsamd_coo *A, char transpose, int precond, const spsamd_coo *M, char transpose_M,
+	const double *b, double *x, int mem, double tol, uint64_t max_iter, uint32_t restart, double *hist_host, size_t hist_capacity,
+	int duplicate_policy, int zero_nan, spsamd_pcg_stats *stats, spsamd_result *res)
+{
+	if (!c) return SPSAMD_EINVAL;
+	API_GUARD(c,
+		if (!A) throw Error{SPSAMD_EINVAL, "null operand"};
+		spsamd_result local;
+		return solve_gmres(c, A, transpose, precond, M, transpose_M, b, x, mem, tol, max_iter, restart, hist_host, hist_capacity,
 			duplicate_policy, zero_nan, stats, res ? res : &local);
 	)
 }

@@ -116,6 +116,7 @@ struct Tuning {
 	int agg_per_rows = 0;        // aggregate: the shortest list whose thread kernels take four entries a thread (0: 1024 for every CU)
 	int pcg_check_every = 0;     // solve_pcg: iterations enqueued between two reads of the device state (0: 8)
 	int pcg_fuse = 0;            // solve_pcg: 0 dots fused into the kernels that produce their vectors | 1 every vector operation and every dot a launch of its own
+	int gmres_path = 0;          // solve_gmres: 0 the block kernels of k_gmres.hip | 1 every dot through the frame's dot and every w -= coef v a launch of its own
 	int amg_path = 0;            // amg cycle: 0 the thin tail of the hierarchy is one launch | 1 every level in launches of its own | 2 the whole hierarchy is the tail, whatever its levels' orders
 	int amg_fuse_rows = 0;       // amg cycle: the largest order of a level that still counts as thin (0: 1024)
 #ifdef SPSAMD_ABLATIONS
@@ -614,8 +615,8 @@ uint64_t solve_levels(spsamd_ctx *c, const TriView &t, const SolveSchedule &s, c
 constexpr int SOLVE_NT = 1024;                 // threads of the one workgroup of a fused run (k_solve_fused, k_fac_fused) and of k_peel_thin
 constexpr uint32_t SOLVE_FUSE_ROWS = 256;      // default of the solve_fuse_rows knob: the flat end of the measured sweep
 
-// ---------------------------------------------------------------- Krylov loops (k_krylov.hip, k_bicgstab.hip)
-// Both loops, and solve_pcg_amg through pcg_solve, run inside one frame, KrylovCall (krylov_dev.h, HIP only): it owns the
+// ---------------------------------------------------------------- Krylov loops (k_krylov.hip, k_bicgstab.hip, k_gmres.hip)
+// All three loops, and solve_pcg_amg through pcg_solve, run inside one frame, KrylovCall (krylov_dev.h, HIP only): it owns the
 // argument checks and their order, the operands, the workspace order, the preconditioner's data with the schedule rollback,
 // the vector kernels, the read-back loop, what counts as a launch, and the tail.  A loop supplies its state struct, its own
 // vectors, its direction / update / finish kernels and the body of an iteration.
@@ -661,6 +662,11 @@ int pcg_solve(spsamd_ctx *c, const spsamd_coo *A, char transpose, int precond, c
 // A x = b for an unsymmetric A by BiCGStab, the loop of the header: spsamd_solve_bicgstab after the context check
 int solve_bicgstab(spsamd_ctx *c, const spsamd_coo *A, char transpose, int precond, const spsamd_coo *M, char transpose_M,
 	const double *b, double *x, int mem, double tol, uint64_t max_iter, double *hist_host, size_t hist_capacity,
+	int duplicate_policy, int zero_nan, spsamd_pcg_stats *stats, spsamd_result *res);
+
+// A x = b for an unsymmetric A by restarted GMRES(m), the loop of the header: spsamd_solve_gmres after the context check
+int solve_gmres(spsamd_ctx *c, const spsamd_coo *A, char transpose, int precond, const spsamd_coo *M, char transpose_M,
+	const double *b, double *x, int mem, double tol, uint64_t max_iter, uint32_t restart, double *hist_host, size_t hist_capacity,
 	int duplicate_policy, int zero_nan, spsamd_pcg_stats *stats, spsamd_result *res);
 
 // ---------------------------------------------------------------- aggregation multigrid cycle (k_amg.hip)

@@ -68,12 +68,7 @@ __device__ __forceinline__ double red_step(double acc, double v, bool on_diag, b
 }
 
 __device__ __forceinline__ double red_recip(double r) { return r != r ? quiet(r) : __ddiv_rn(1.0, r); }
-__device__ __forceinline__ double red_sqrt(double r)
-{
-	if (r != r) return quiet(r);
-	if (r < 0.0) return __longlong_as_double((long long)X86_DEFAULT_NAN);
-	return __dsqrt_rn(r);
-}
+__device__ __forceinline__ double red_sqrt(double r) { return ref_sqrt(r); }
 __device__ __forceinline__ double red_post(double r, int post)
 {
 	if (post == SPSAMD_POST_RECIP) return red_recip(r);

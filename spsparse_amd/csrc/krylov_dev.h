@@ -1,4 +1,5 @@
-// krylov_dev.h -- what the device loops of k_krylov.hip (conjugate gradients) and k_bicgstab.hip (BiCGStab) share: the state
+// krylov_dev.h -- what the device loops of k_krylov.hip (conjugate gradients), k_bicgstab.hip (BiCGStab) and k_gmres.hip
+// (restarted GMRES) share: the state
 // word and the scalars of a loop in device memory, the one reduction shape of every dot product (the fold of
 // include/spsparse_amd.h), a row's serial chain, and the frame of a call (KrylovCall; its members
 // and the vector kernels they launch are k_krylov.hip's).  HIP only.
@@ -25,6 +26,23 @@ struct PcgState {
 
 __device__ __forceinline__ bool pcg_usable(double v) { return v == v && mag_of(v) != 0x7FF0000000000000ull && v != 0.0; }
 
+// The partial of chunk g of t[0 .. n) from the 16 terms a lane holds in registers (t[k]: element 1024 g + 64 k + lane; those
+// at or past n are not read): valid in lane 0.  Every lane of the wave calls it.
+__device__ __forceinline__ double chunk_partial_regs(uint64_t g, uint64_t n, const double (&t)[PCG_CHUNK / 64])
+{
+	const uint64_t base = g * PCG_CHUNK + lane_id();
+	double a = 0.0;
+#pragma unroll
+	for (int k = 0; k < PCG_CHUNK / 64; ++k)
+		if (base + (uint64_t)k * 64 < n) a = ref_add(a, t[k]);
+#pragma unroll
+	for (int s = 32; s >= 1; s >>= 1) {
+		const double o = __shfl_down(a, s, 64);
+		if (lane_id() < (unsigned)s) a = ref_add(a, o);              // a_l is the left operand
+	}
+	return a;
+}
+
 // The partial of chunk g of t[0 .. n), t[e] = term(e) (called once per element of the chunk, by the lane that owns it):
 // valid in lane 0.  Every lane of the wave calls it.
 template <class Term>
@@ -37,16 +55,7 @@ __device__ __forceinline__ double chunk_partial(uint64_t g, uint64_t n, Term ter
 		const uint64_t e = base + (uint64_t)k * 64;
 		t[k] = e < n ? term(e) : 0.0;
 	}
-	double a = 0.0;
-#pragma unroll
-	for (int k = 0; k < PCG_CHUNK / 64; ++k)
-		if (base + (uint64_t)k * 64 < n) a = ref_add(a, t[k]);
-#pragma unroll
-	for (int s = 32; s >= 1; s >>= 1) {
-		const double o = __shfl_down(a, s, 64);
-		if (lane_id() < (unsigned)s) a = ref_add(a, o);              // a_l is the left operand
-	}
-	return a;
+	return chunk_partial_regs(g, n, t);
 }
 
 // chunk_partial for two folds of one pass: term(e, &t0, &t1) gives element e's term of each
@@ -115,7 +124,7 @@ __device__ inline double block_fold(const double *part, uint64_t m, double *b0, 
 
 // ---------------------------------------------------------------- the frame of a call (members: k_krylov.hip)
 
-// What solve_pcg, solve_pcg_amg and solve_bicgstab do alike around their iteration bodies.  A loop open()s the call, takes
+// What solve_pcg, solve_pcg_amg, solve_bicgstab and solve_gmres do alike around their iteration bodies.  A loop open()s the call, takes
 // its own vectors (then hook->setup), enqueues its set-up with dot / spmv / residual and its own finish kernels, hands its
 // iteration body to iterate() and close()s.  Every launch of an iteration goes through a member or bumps `launches`.
 struct KrylovCall {
@@ -154,16 +163,26 @@ struct KrylovCall {
 	// The end of the set-up; then `one()` enqueues an iteration, pcg_check_every of them between two reads of the state
 	template <class Body> PcgState iterate(Body one)
 	{
-		SPS_HIP(hipEventRecord(c->ev[EV_SYMBOLIC], c->stream));
 		const uint64_t every = c->tune.pcg_check_every > 0 ? (uint64_t)c->tune.pcg_check_every : (uint64_t)PCG_CHECK_EVERY;
+		return iterate(every, [&](uint64_t) { one(); }, [] {});
+	}
+
+	// The same with the batch given: between two reads of the state `every` iterations at the most, one(it) the it-th of its
+	// batch, and end() once behind them (a loop whose iterations come in groups: a restart cycle and its end).  The batch is
+	// sized from the k that was read: a loop whose every enqueued iteration counts while it is RUNNING (PCG, BiCGStab) has
+	// k == the iterations enqueued so far, and one whose group may end early and go on (GMRES) still never enqueues past
+	// max_iter and never waits on an empty batch.
+	template <class Body, class End> PcgState iterate(uint64_t every, Body one, End end)
+	{
+		SPS_HIP(hipEventRecord(c->ev[EV_SYMBOLIC], c->stream));
 		launches = 0;
-		for (uint64_t enqueued = 0;;) {
+		for (;;) {
 			const PcgState hs = read_back(c, st);
 			++readbacks;
 			if (hs.state != PCG_RUNNING) return hs;
-			const uint64_t batch = std::min<uint64_t>(every, max_iter - enqueued);   // (RUNNING: k < max_iter, and k <= enqueued)
-			for (uint64_t it = 0; it < batch; ++it) one();
-			enqueued += batch;
+			const uint64_t batch = std::min<uint64_t>(every, max_iter - hs.k);       // (RUNNING: k < max_iter)
+			for (uint64_t it = 0; it < batch; ++it) one(it);
+			end();
 		}
 	}
 

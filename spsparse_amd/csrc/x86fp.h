@@ -48,4 +48,12 @@ __device__ __forceinline__ double ref_div(double a, double b)
 	return r != r ? x86_nan(a, b) : r;
 }
 
+// sqrtsd: the correctly rounded square root (a NaN operand quieted; a < 0: the default NaN; sqrt(-0.0) = -0.0)
+__device__ __forceinline__ double ref_sqrt(double a)
+{
+	if (a != a) return quiet(a);
+	if (a < 0.0) return __longlong_as_double((long long)X86_DEFAULT_NAN);
+	return __dsqrt_rn(a);
+}
+
 } // namespace spsamd
