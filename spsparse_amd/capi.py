@@ -603,6 +603,41 @@ class Context:
         self._check(rc)
         return (res, st) if stats else res
 
+    def _graph_call(self, fn, stats_cls, names, A, order, seed, flags, transpose, out, stats, result):
+        """What color and aggregate share: fn into `out` (device tensors named `names`: per-vertex ids, ordered list, bounds)
+        or into host arrays of its own."""
+        n = int(A.shape1 if transpose == 'T' else A.shape0)
+        cnt, st = C.c_size_t(0), stats_cls()
+        rp = None if result is None else C.byref(result)
+
+        def call(pi, pl, pq, cap, mem):
+            return fn(self.h, C.byref(A), transpose.encode(), int(order), int(seed) & 0xFFFFFFFF, int(flags),
+                      pi, pl, pq, cap, mem, C.byref(cnt), C.byref(st), rp)
+
+        if out is not None:
+            oi, ol, oq = out
+            if oi is None:
+                raise ValueError("out %s is required" % names[0])
+            ptrs, sizes = [], []
+            for t, name in zip((oi, ol, oq), names):
+                if t is None:
+                    ptrs.append(None)
+                    sizes.append(0)
+                    continue
+                _p, nt, mt, _k = _index_list(t, "out " + name)
+                if mt != MEM_DEVICE and nt:
+                    raise ValueError("out %s must be a device tensor" % name)
+                ptrs.append(t.data_ptr())
+                sizes.append(nt)
+            if sizes[0] < n or (ol is not None and sizes[1] < n):
+                raise ValueError("out %s and out %s need %d entries" % (names[0], names[1], n))
+            self._check(call(ptrs[0], ptrs[1], ptrs[2], sizes[2], MEM_DEVICE))
+            return (int(cnt.value), st) if stats else int(cnt.value)
+        ids, lst, ptr = np.empty(max(n, 1), np.int32), np.empty(max(n, 1), np.int32), np.empty(n + 1, np.int32)
+        self._check(call(ids.ctypes.data, lst.ctypes.data, ptr.ctypes.data, n + 1, MEM_HOST))
+        got = (ids[:n].copy(), lst[:n].copy(), ptr[:cnt.value + 1].copy())
+        return got + (st,) if stats else got
+
     def color(self, A, order=COLOR_ORDER_HASH, seed=0, flags=0, transpose='.', out=None, stats=False, result=None):
         """spsamd_color: the greedy multi-colour ordering of op(A)'s graph, exactly the serial loop of the header.  A: a Coo
         struct whose op() is square (only its keys are read).  Without out: returns numpy int32 arrays (color, perm,
@@ -611,37 +646,7 @@ class Context:
         context's device, (color, perm, color_ptr) with perm and color_ptr possibly None, that receive the result; the
         colour count is returned, and a color_ptr that is too small raises SpsamdError with code -5.  stats=True appends
         a ColorStats to what is returned.  result: a capi.Result to fill (timings)."""
-        n = int(A.shape1 if transpose == 'T' else A.shape0)
-        cnt, st = C.c_size_t(0), ColorStats()
-        rp = None if result is None else C.byref(result)
-
-        def call(pc, pp, pq, cap, mem):
-            return self.L.spsamd_color(self.h, C.byref(A), transpose.encode(), int(order), int(seed) & 0xFFFFFFFF, int(flags),
-                                       pc, pp, pq, cap, mem, C.byref(cnt), C.byref(st), rp)
-
-        if out is not None:
-            oc, op, oq = out
-            ptrs, sizes = [], []
-            for t, name in ((oc, "out color"), (op, "out perm"), (oq, "out color_ptr")):
-                if t is None:
-                    if name == "out color":
-                        raise ValueError("out color is required")
-                    ptrs.append(None)
-                    sizes.append(0)
-                    continue
-                _p, nt, mt, _k = _index_list(t, name)
-                if mt != MEM_DEVICE and nt:
-                    raise ValueError("%s must be a device tensor" % name)
-                ptrs.append(t.data_ptr())
-                sizes.append(nt)
-            if sizes[0] < n or (op is not None and sizes[1] < n):
-                raise ValueError("out color and out perm need %d entries" % n)
-            self._check(call(ptrs[0], ptrs[1], ptrs[2], sizes[2], MEM_DEVICE))
-            return (int(cnt.value), st) if stats else int(cnt.value)
-        color, perm, ptr = np.empty(max(n, 1), np.int32), np.empty(max(n, 1), np.int32), np.empty(n + 1, np.int32)
-        self._check(call(color.ctypes.data, perm.ctypes.data, ptr.ctypes.data, n + 1, MEM_HOST))
-        got = (color[:n].copy(), perm[:n].copy(), ptr[:cnt.value + 1].copy())
-        return got + (st,) if stats else got
+        return self._graph_call(self.L.spsamd_color, ColorStats, ("color", "perm", "color_ptr"), A, order, seed, flags, transpose, out, stats, result)
 
     def aggregate(self, A, order=AGG_ORDER_HASH, seed=0, flags=0, transpose='.', out=None, stats=False, result=None):
         """spsamd_aggregate: the MIS(2) aggregates of op(A)'s graph, exactly the serial loop of the header.  A: a Coo struct
@@ -651,37 +656,7 @@ class Context:
         members and agg_ptr possibly None, that receive the result; the aggregate count is returned, and an agg_ptr that
         is too small raises SpsamdError with code -5.  stats=True appends an AggregateStats to what is returned.  result:
         a capi.Result to fill (timings).  prolongator(agg, naggregates) makes the tentative prolongator of the result."""
-        n = int(A.shape1 if transpose == 'T' else A.shape0)
-        cnt, st = C.c_size_t(0), AggregateStats()
-        rp = None if result is None else C.byref(result)
-
-        def call(pa, pm, pq, cap, mem):
-            return self.L.spsamd_aggregate(self.h, C.byref(A), transpose.encode(), int(order), int(seed) & 0xFFFFFFFF, int(flags),
-                                           pa, pm, pq, cap, mem, C.byref(cnt), C.byref(st), rp)
-
-        if out is not None:
-            oa, om, oq = out
-            ptrs, sizes = [], []
-            for t, name in ((oa, "out agg"), (om, "out members"), (oq, "out agg_ptr")):
-                if t is None:
-                    if name == "out agg":
-                        raise ValueError("out agg is required")
-                    ptrs.append(None)
-                    sizes.append(0)
-                    continue
-                _p, nt, mt, _k = _index_list(t, name)
-                if mt != MEM_DEVICE and nt:
-                    raise ValueError("%s must be a device tensor" % name)
-                ptrs.append(t.data_ptr())
-                sizes.append(nt)
-            if sizes[0] < n or (om is not None and sizes[1] < n):
-                raise ValueError("out agg and out members need %d entries" % n)
-            self._check(call(ptrs[0], ptrs[1], ptrs[2], sizes[2], MEM_DEVICE))
-            return (int(cnt.value), st) if stats else int(cnt.value)
-        agg, mem, ptr = np.empty(max(n, 1), np.int32), np.empty(max(n, 1), np.int32), np.empty(n + 1, np.int32)
-        self._check(call(agg.ctypes.data, mem.ctypes.data, ptr.ctypes.data, n + 1, MEM_HOST))
-        got = (agg[:n].copy(), mem[:n].copy(), ptr[:cnt.value + 1].copy())
-        return got + (st,) if stats else got
+        return self._graph_call(self.L.spsamd_aggregate, AggregateStats, ("agg", "members", "agg_ptr"), A, order, seed, flags, transpose, out, stats, result)
 
     def solve_pcg(self, A, b, x=None, precond=PRECOND_NONE, M=None, transpose='.', transpose_M='.', tol=1e-8, max_iter=1000,
                   hist_capacity=None, duplicate_policy=ADD, zero_nan=False, result=None):

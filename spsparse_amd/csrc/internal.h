@@ -713,6 +713,62 @@ void graph_classes(spsamd_ctx *c, const GraphRows &g, uint64_t N, uint32_t *deg,
 uint32_t *order_by_key(spsamd_ctx *c, PairSort &sort, uint64_t N, int key_bits, int shift, uint64_t nbuckets, bool bounds,
 	int32_t *list, int32_t *list_ptr, hipMemcpyKind kind);
 
+// The frame of a graph call: what spsamd_color and spsamd_aggregate do around their sweeps, once.
+// An operation names its messages, knobs and counters (GraphOp); its orders and its one flag have spsamd_color's values.
+static_assert(SPSAMD_AGG_ORDER_HASH == SPSAMD_COLOR_ORDER_HASH && SPSAMD_AGG_ORDER_DEGREE == SPSAMD_COLOR_ORDER_DEGREE &&
+	SPSAMD_AGG_SYMMETRIC == SPSAMD_COLOR_SYMMETRIC, "GraphCall::open checks one set of values");
+struct GraphOp {
+	const char *bad_order, *bad_flags, *not_square, *overlap, *too_small;      // the refusals' messages
+	int Tuning::*path, Tuning::*row, Tuning::*fuse_rows, Tuning::*wave_deg;    // its four knobs, and the defaults of the last two
+	uint32_t fuse_rows_default, wave_deg_default;
+	int acc_len, nlists;                       // its acc[] slots; its worklists per parity: 2, or 4 (two (thread, wave) pairs)
+};
+struct GraphTotals { uint64_t adjacency, max_degree, launches, fused_rounds, rows_wave; float ms_adjacency; };   // the stats both structs hold
+struct GraphCall {
+	spsamd_ctx *c;
+	const GraphOp *op;
+	int32_t *ids_out = nullptr, *list_out = nullptr, *ptr_out = nullptr;   // the caller's: per-vertex ids, the ordered list, its bounds
+	size_t ptr_capacity = 0, *out_count = nullptr;
+	spsamd_result *res = nullptr;
+	hipMemcpyKind kind = hipMemcpyDeviceToHost;                            // towards the caller's buffers
+	uint64_t N = 0;                                                        // from here on: what open() leaves
+	bool symmetric = false;
+	MaskKeys K; GraphRows g{};
+	int path = 0, rowk = 0;
+	uint32_t fuse_rows = 0, wave_deg = 0;
+	unsigned long long *acc = nullptr;         // op->acc_len counters, zeroed
+	uint32_t *ctr = nullptr, *deg = nullptr;   // ctr[nlists * parity + list]: the lengths of the worklists, zeroed
+	int32_t *ids = nullptr;
+	uint32_t *h = nullptr;                     // host staging of op->acc_len * 8 bytes
+	uint64_t launches = 0, rounds = 0;         // what sweep() counts
+	bool fused = false;
+	// Everything from the first argument check to the first workspace arrays: the refusals in their order, res and the
+	// `stats_bytes` of `stats` (may be null) zeroed, the keys taken, *out_count zeroed after that, the adjacency, the knobs,
+	// then acc, ctr, deg and ids out of the workspace in this order.  False: the call is over (no vertex) and returns *rc.
+	bool open(const spsamd_coo *A, char transpose, int order, int flags, int mem, void *stats, size_t stats_bytes, int *rc);
+	void read_counts(int par, uint32_t *cnt);  // cnt[nlists] = the lists' lengths at a parity: one copy, one synchronisation
+	// The host loop over the parities from the round-0 counts in cnt[nlists].  round(par, cnt) enqueues one round and returns its
+	// launches; fuse(par, cnt) enqueues the fused run of the rest: under path 2, or (path 0) once every (thread, wave) pair
+	// of lists holds at most fuse_rows.  Nothing is zeroed here: the operations' kernels do that.
+	template <class Round, class Fuse> void sweep(uint32_t *cnt, Round round, Fuse fuse)
+	{
+		for (int par = 0; cnt[0] || cnt[1]; par ^= 1) {
+			bool thin = path != 1;
+			for (int k = 0; k < op->nlists; k += 2) thin = thin && (path == 2 || (uint64_t)cnt[k] + cnt[k + 1] <= fuse_rows);
+			if (thin) { fuse(par, cnt); ++launches; fused = true; break; }
+			launches += round(par, cnt);
+			++rounds;
+			read_counts(par ^ 1, cnt);
+		}
+	}
+	// *out_count = count; false, with the context's last error set, where ptr_out cannot hold count + 1 bounds.  The caller
+	// returns SPSAMD_ECAPACITY then, without close(): nothing has been written.
+	bool fits(uint64_t count);
+	void deliver() { SPS_HIP(hipMemcpyAsync(ids_out, ids, N * sizeof(int32_t), kind, c->stream)); }
+	// finish_call and res's three times; `hacc`: acc as read back, whose slot `fused_slot` counts the fused run's rounds
+	GraphTotals close(const unsigned long long *hacc, int fused_slot);
+};
+
 // ---------------------------------------------------------------- MIS(2) aggregation (k_aggregate.hip)
 
 // the aggregates of op(A)'s graph into the caller's buffers: spsamd_aggregate after its null checks.  Returns SPSAMD_OK,

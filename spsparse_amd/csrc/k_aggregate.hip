@@ -413,81 +413,40 @@ __global__ void __launch_bounds__(256) k_agg_sizes(const uint32_t *__restrict__ 
 
 // ---------------------------------------------------------------- host
 
+// The call runs inside GraphCall (internal.h, k_color.hip); here are the lists, the two launch bodies and the assignment.
+// Four lists a parity: [4 * parity + list] of ctr is undecided thread, wave; spread thread, wave.
+static const GraphOp AGG_OP = {"unknown aggregation order", "unknown agg_flags", "op(A) must be square for an aggregation",
+	"agg, members and agg_ptr overlap", "agg_ptr is too small: it needs one entry per aggregate and one more; *out_naggregates holds the aggregates",
+	&Tuning::agg_path, &Tuning::agg_row, &Tuning::agg_fuse_rows, &Tuning::agg_wave_deg, AGG_FUSE_ROWS, AGG_WAVE_DEG, AGG_ACC, 4};
+
 int aggregate_graph(spsamd_ctx *c, const spsamd_coo *A, char transpose, int order, uint32_t seed, int agg_flags, int32_t *agg,
 	int32_t *members, int32_t *agg_ptr, size_t ptr_capacity, int mem, size_t *out_naggregates, spsamd_aggregate_stats *stats,
 	spsamd_result *res)
 {
-	if (order != SPSAMD_AGG_ORDER_HASH && order != SPSAMD_AGG_ORDER_DEGREE) throw Error{SPSAMD_EINVAL, "unknown aggregation order"};
-	if (agg_flags & ~SPSAMD_AGG_SYMMETRIC) throw Error{SPSAMD_EINVAL, "unknown agg_flags"};
-	if (mem != SPSAMD_MEM_HOST && mem != SPSAMD_MEM_DEVICE) throw Error{SPSAMD_EINVAL, "mem of the output must be SPSAMD_MEM_HOST or SPSAMD_MEM_DEVICE"};
-	const int lead = transpose == 'T' ? 1 : 0;
-	const uint64_t N = A->shape0;
-	if (A->shape0 != A->shape1) throw Error{SPSAMD_EDIM, "op(A) must be square for an aggregation"};
-	if (N >= (uint64_t(1) << 31)) throw Error{SPSAMD_EINVAL, "shape exceeds the int32 index range"};
-	const bool symmetric = (agg_flags & SPSAMD_AGG_SYMMETRIC) != 0;
-	{
-		const OperandView view = operand_view(c, A);
-		const uint64_t n = view.coo.nnz;
-		const void *buf[3] = {agg, members, agg_ptr};
-		const uint64_t bytes[3] = {N * 4, N * 4, (uint64_t)ptr_capacity * 4};
-		for (int p = 0; p < 3; ++p)
-			for (int q = p + 1; q < 3; ++q)
-				if (ranges_overlap(buf[p], bytes[p], buf[q], bytes[q])) throw Error{SPSAMD_EINVAL, "agg, members and agg_ptr overlap"};
-		const void *arr[3] = {view.coo.idx0, view.coo.idx1, view.coo.val};
-		for (int p = 0; p < 3; ++p)
-			for (int k = 0; k < 3; ++k)
-				if (ranges_overlap(buf[p], bytes[p], arr[k], n * (k == 2 ? 8 : 4))) throw Error{SPSAMD_EINVAL, "an output buffer overlaps A's arrays"};
-		if (mem == SPSAMD_MEM_DEVICE)
-			for (int p = 0; p < 3; ++p)
-				if (in_output_sets(c, buf[p], bytes[p])) throw Error{SPSAMD_EINVAL, "an output buffer lies in an output set of the context"};
-	}
-	std::memset(res, 0, sizeof(*res));
-	if (stats) std::memset(stats, 0, sizeof(*stats));
-	res->shape0 = res->shape1 = N;
-
-	SPS_HIP(hipSetDevice(c->device));
-	c->arena.reset();
+	GraphCall gc{c, &AGG_OP, agg, members, agg_ptr, ptr_capacity, out_naggregates, res};
+	int rc;
+	if (!gc.open(A, transpose, order, agg_flags, mem, stats, sizeof(*stats), &rc)) return rc;
 	hipStream_t st = c->stream;
-	SPS_HIP(hipEventRecord(c->ev[EV_BEGIN], st));
-	MaskKeys K;
-	mask_keys(c, A, lead, N, N, &K);
-	SPS_HIP(hipEventRecord(c->ev[EV_CONSOLIDATED], st));
-	res->nnz_a = K.n;
-	*out_naggregates = 0;
-	static const char *const too_small = "agg_ptr is too small: it needs one entry per aggregate and one more; *out_naggregates holds the aggregates";
-	if (N == 0) {                                                      // no vertex, no aggregate: agg_ptr is the one entry 0
-		if (agg_ptr && ptr_capacity < 1) { c->last_error = too_small; return SPSAMD_ECAPACITY; }
-		if (agg_ptr && mem == SPSAMD_MEM_HOST) agg_ptr[0] = 0;
-		else if (agg_ptr) { fill_zero(c, agg_ptr, sizeof(int32_t)); SPS_HIP(hipStreamSynchronize(st)); }
-		return SPSAMD_OK;
-	}
+	const uint64_t N = gc.N; const MaskKeys &K = gc.K; const GraphRows &g = gc.g;
+	unsigned long long *acc = gc.acc; uint32_t *ctr = gc.ctr, *deg = gc.deg;
+	int32_t *ids = gc.ids;                                              // the aggregate ids (until then: what graph_classes calls colours)
 
-	// ---- adjacency, and the promise checked
-	const GraphRows g = graph_adjacency(c, K, N, symmetric);
-	const int path = c->tune.agg_path == 1 || c->tune.agg_path == 2 ? c->tune.agg_path : 0;
-	const int rowk = c->tune.agg_row == 1 || c->tune.agg_row == 2 ? c->tune.agg_row : 0;
-	const uint32_t fuse_rows = c->tune.agg_fuse_rows > 0 ? (uint32_t)c->tune.agg_fuse_rows : AGG_FUSE_ROWS;
-	const uint32_t wave_deg = c->tune.agg_wave_deg > 0 ? (uint32_t)c->tune.agg_wave_deg : AGG_WAVE_DEG;
-	unsigned long long *acc = get_zeroed<unsigned long long>(c, AGG_ACC);
-	uint32_t *ctr = get_zeroed<uint32_t>(c, 8);                         // [4 * parity + list]: undecided thread, wave; spread thread, wave
-	uint32_t *deg = c->arena.get<uint32_t>(N);
-	int32_t *ids = c->arena.get<int32_t>(N);                            // the aggregate ids (until then: what graph_classes calls colours)
+	// ---- the lists, and the promise checked
 	uint64_t *word = c->arena.get<uint64_t>(N), *t1 = c->arena.get<uint64_t>(N);
 	uint32_t *ut[2] = {c->arena.get<uint32_t>(N), c->arena.get<uint32_t>(N)}, *uw[2] = {c->arena.get<uint32_t>(N), c->arena.get<uint32_t>(N)};
 	uint32_t *sl[2] = {c->arena.get<uint32_t>(N), c->arena.get<uint32_t>(N)}, *sw[2] = {c->arena.get<uint32_t>(N), c->arena.get<uint32_t>(N)};
-	graph_classes(c, g, N, deg, ids, ut[0], uw[0], ctr, acc, wave_deg, rowk, 1);
-	if (symmetric && K.n) { k_agg_asym<<<dim3(grid_for(K.n)), dim3(256), 0, st>>>(K.i, K.j, K.n, g.ptr, acc); SPS_LAUNCH_CHECK(); }
+	graph_classes(c, g, N, deg, ids, ut[0], uw[0], ctr, acc, gc.wave_deg, gc.rowk, 1);
+	if (gc.symmetric && K.n) { k_agg_asym<<<dim3(grid_for(K.n)), dim3(256), 0, st>>>(K.i, K.j, K.n, g.ptr, acc); SPS_LAUNCH_CHECK(); }
 	k_agg_words<<<dim3(grid_for(N)), dim3(256), 0, st>>>(deg, N, seed, order == SPSAMD_AGG_ORDER_DEGREE, word);
 	SPS_LAUNCH_CHECK();
-	uint32_t *h = (uint32_t *)c->host_staging(AGG_ACC * sizeof(unsigned long long));
-	uint32_t cnt[4] = {0, 0, 0, 0};
+	uint32_t cnt0[4];
 	{                                                                  // the round-0 lists' lengths and the asymmetric keys in one trip
 		WordList wl;
 		wl.add(ctr); wl.add(ctr + 1);
 		const int at = wl.add64(&acc[AGG_ASYM]);
 		uint32_t hw[4];
 		read_back_words(c, wl, hw);
-		cnt[0] = cnt[2] = hw[0]; cnt[1] = cnt[3] = hw[1];
+		cnt0[0] = cnt0[2] = hw[0]; cnt0[1] = cnt0[3] = hw[1];
 		const uint64_t asym = (uint64_t)hw[at + 1] << 32 | hw[at];
 		if (asym) {
 			if (stats) stats->asymmetric = asym;
@@ -495,37 +454,33 @@ int aggregate_graph(spsamd_ctx *c, const spsamd_coo *A, char transpose, int orde
 		}
 	}
 	// the spread lists of round 0 are the undecided ones: every vertex
-	if (cnt[0]) SPS_HIP(hipMemcpyAsync(sl[0], ut[0], (size_t)cnt[0] * sizeof(uint32_t), hipMemcpyDeviceToDevice, st));
-	if (cnt[1]) SPS_HIP(hipMemcpyAsync(sw[0], uw[0], (size_t)cnt[1] * sizeof(uint32_t), hipMemcpyDeviceToDevice, st));
+	if (cnt0[0]) SPS_HIP(hipMemcpyAsync(sl[0], ut[0], (size_t)cnt0[0] * sizeof(uint32_t), hipMemcpyDeviceToDevice, st));
+	if (cnt0[1]) SPS_HIP(hipMemcpyAsync(sw[0], uw[0], (size_t)cnt0[1] * sizeof(uint32_t), hipMemcpyDeviceToDevice, st));
 	SPS_HIP(hipEventRecord(c->ev[EV_SYMBOLIC], st));
 
 	// ---- sweep
 	AggArgs a;
 	a.ptr = g.ptr; a.adj = g.adj; a.word = word; a.t1 = t1; a.acc = acc;
-	uint64_t launches = 0, rounds = 0;
-	bool fused = false;
 	const uint32_t per_min = c->tune.agg_per_rows > 0 ? (uint32_t)c->tune.agg_per_rows : (uint32_t)std::max(c->num_cu, 1) * 256u * AGG_PER;
-	for (int par = 0; cnt[0] || cnt[1]; par ^= 1) {
-		const int nx = par ^ 1;
-		if (path != 1 && (path == 2 || ((uint64_t)cnt[0] + cnt[1] <= fuse_rows && (uint64_t)cnt[2] + cnt[3] <= fuse_rows))) {
+	gc.sweep(cnt0,
+		[&](int par, const uint32_t *cnt) {
+			const int nx = par ^ 1;
+			uint32_t *cn = ctr + 4 * nx, *cz = ctr + 4 * par;
+			uint64_t launches = 0;
+			if (cnt[2] >= per_min) { k_agg_spread_thread<AGG_PER><<<dim3(grid_for(cnt[2], 256 * AGG_PER)), dim3(256), 0, st>>>(a, sl[par], cnt[2], sl[nx], cn + 2); SPS_LAUNCH_CHECK(); ++launches; }
+			else if (cnt[2]) { k_agg_spread_thread<1><<<dim3(grid_for(cnt[2])), dim3(256), 0, st>>>(a, sl[par], cnt[2], sl[nx], cn + 2); SPS_LAUNCH_CHECK(); ++launches; }
+			if (cnt[3]) { k_agg_spread_wave<<<dim3(grid_for(cnt[3], 4)), dim3(256), 0, st>>>(a, sw[par], cnt[3], sw[nx], cn + 3); SPS_LAUNCH_CHECK(); ++launches; }
+			if (cnt[0] >= per_min) { k_agg_decide_thread<AGG_PER><<<dim3(grid_for(cnt[0], 256 * AGG_PER)), dim3(256), 0, st>>>(a, ut[par], cnt[0], ut[nx], cn, cz); SPS_LAUNCH_CHECK(); ++launches; }
+			else if (cnt[0]) { k_agg_decide_thread<1><<<dim3(grid_for(cnt[0])), dim3(256), 0, st>>>(a, ut[par], cnt[0], ut[nx], cn, cz); SPS_LAUNCH_CHECK(); ++launches; }
+			if (cnt[1]) { k_agg_decide_wave<<<dim3(grid_for(cnt[1], 4)), dim3(256), 0, st>>>(a, uw[par], cnt[1], uw[nx], cn + 1, cz); SPS_LAUNCH_CHECK(); ++launches; }
+			return launches;
+		},
+		[&](int par, const uint32_t *cnt) {
+			const int nx = par ^ 1;
 			k_agg_fused<<<dim3(1), dim3(AGG_NT), 0, st>>>(a, ut[par], ut[nx], cnt[0], uw[par], uw[nx], cnt[1], sl[par], sl[nx], cnt[2],
 				sw[par], sw[nx], cnt[3]);
 			SPS_LAUNCH_CHECK();
-			++launches; fused = true;
-			break;
-		}
-		uint32_t *cn = ctr + 4 * nx, *cz = ctr + 4 * par;
-		if (cnt[2] >= per_min) { k_agg_spread_thread<AGG_PER><<<dim3(grid_for(cnt[2], 256 * AGG_PER)), dim3(256), 0, st>>>(a, sl[par], cnt[2], sl[nx], cn + 2); SPS_LAUNCH_CHECK(); ++launches; }
-		else if (cnt[2]) { k_agg_spread_thread<1><<<dim3(grid_for(cnt[2])), dim3(256), 0, st>>>(a, sl[par], cnt[2], sl[nx], cn + 2); SPS_LAUNCH_CHECK(); ++launches; }
-		if (cnt[3]) { k_agg_spread_wave<<<dim3(grid_for(cnt[3], 4)), dim3(256), 0, st>>>(a, sw[par], cnt[3], sw[nx], cn + 3); SPS_LAUNCH_CHECK(); ++launches; }
-		if (cnt[0] >= per_min) { k_agg_decide_thread<AGG_PER><<<dim3(grid_for(cnt[0], 256 * AGG_PER)), dim3(256), 0, st>>>(a, ut[par], cnt[0], ut[nx], cn, cz); SPS_LAUNCH_CHECK(); ++launches; }
-		else if (cnt[0]) { k_agg_decide_thread<1><<<dim3(grid_for(cnt[0])), dim3(256), 0, st>>>(a, ut[par], cnt[0], ut[nx], cn, cz); SPS_LAUNCH_CHECK(); ++launches; }
-		if (cnt[1]) { k_agg_decide_wave<<<dim3(grid_for(cnt[1], 4)), dim3(256), 0, st>>>(a, uw[par], cnt[1], uw[nx], cn + 1, cz); SPS_LAUNCH_CHECK(); ++launches; }
-		++rounds;
-		SPS_HIP(hipMemcpyAsync(h, cn, 4 * sizeof(uint32_t), hipMemcpyDeviceToHost, st));
-		SPS_HIP(hipStreamSynchronize(st));
-		std::memcpy(cnt, h, sizeof cnt);
-	}
+		});
 	SPS_HIP(hipEventRecord(c->ev[EV_N0], st));
 
 	// ---- assignment
@@ -535,8 +490,7 @@ int aggregate_graph(spsamd_ctx *c, const spsamd_coo *A, char transpose, int orde
 	SPS_LAUNCH_CHECK();
 	scan_exclusive_u8_u32(c, root, rid, N);
 	const uint64_t nagg = read_back(c, rid + N);
-	*out_naggregates = nagg;
-	if (agg_ptr && ptr_capacity < nagg + 1) { c->last_error = too_small; return SPSAMD_ECAPACITY; }
+	if (!gc.fits(nagg)) return SPSAMD_ECAPACITY;
 	RingArgs ra;
 	ra.ptr = g.ptr; ra.adj = g.adj; ra.deg = deg; ra.root = root; ra.id = rid; ra.agg = ids; ra.ring = ring; ra.acc = acc; ra.n = N;
 	ra.seed = seed; ra.by_degree = order == SPSAMD_AGG_ORDER_DEGREE;
@@ -546,32 +500,26 @@ int aggregate_graph(spsamd_ctx *c, const spsamd_coo *A, char transpose, int orde
 	SPS_LAUNCH_CHECK();
 
 	// ---- members, agg_ptr, the sizes and delivery
-	const hipMemcpyKind kind = mem == SPSAMD_MEM_DEVICE ? hipMemcpyDeviceToDevice : hipMemcpyDeviceToHost;
 	if (members || agg_ptr || stats) {
 		PairSort sort(c, N);
 		k_agg_keys<<<dim3(grid_for(N)), dim3(256), 0, st>>>(ids, ring, N, sort.keys);
 		SPS_LAUNCH_CHECK();
-		const uint32_t *aptr = order_by_key(c, sort, N, bits_of(nagg) + 2, 2, nagg, true, members, agg_ptr, kind);   // stable: ascending index inside a ring
+		const uint32_t *aptr = order_by_key(c, sort, N, bits_of(nagg) + 2, 2, nagg, true, members, agg_ptr, gc.kind);   // stable: ascending index inside a ring
 		k_agg_sizes<<<dim3(grid_for(nagg)), dim3(256), 0, st>>>(aptr, nagg, acc);
 		SPS_LAUNCH_CHECK();
 	}
-	SPS_HIP(hipMemcpyAsync(agg, ids, N * sizeof(int32_t), kind, st));
-	unsigned long long hacc[AGG_ACC];
-	SPS_HIP(hipMemcpyAsync(h, acc, sizeof hacc, hipMemcpyDeviceToHost, st));
-	finish_call(c, res);
-	std::memcpy(hacc, h, sizeof hacc);
-	SPS_HIP(hipEventElapsedTime(&res->ms_consolidate, c->ev[EV_BEGIN], c->ev[EV_CONSOLIDATED]));
-	SPS_HIP(hipEventElapsedTime(&res->ms_symbolic, c->ev[EV_CONSOLIDATED], c->ev[EV_SYMBOLIC]));
-	SPS_HIP(hipEventElapsedTime(&res->ms_numeric, c->ev[EV_SYMBOLIC], c->ev[EV_END]));
+	gc.deliver();
+	const unsigned long long *hacc = (const unsigned long long *)gc.h;    // (there once close() has waited for the stream)
+	SPS_HIP(hipMemcpyAsync(gc.h, acc, AGG_ACC * sizeof(unsigned long long), hipMemcpyDeviceToHost, st));
+	const GraphTotals t = gc.close(hacc, AGG_FUSED);
 	if (stats) {
-		const uint64_t fused_rounds = fused ? hacc[AGG_FUSED] : 0;
-		stats->naggregates = nagg; stats->rounds = rounds + fused_rounds;
+		stats->naggregates = nagg; stats->rounds = gc.rounds + t.fused_rounds;
 		stats->ring1 = hacc[AGG_RING1]; stats->ring2 = hacc[AGG_RING2];
 		stats->max_size = hacc[AGG_MAXSZ]; stats->min_size = 0xFFFFFFFFull - hacc[AGG_MINSZ];
-		stats->adjacency = hacc[GRAPH_ADJ]; stats->max_degree = hacc[GRAPH_MAXDEG]; stats->asymmetric = 0;
-		stats->launches = launches; stats->fused_rounds = fused_rounds;
-		stats->rows_wave = hacc[GRAPH_ROWS_W]; stats->rows_thread = N - hacc[GRAPH_ROWS_W];
-		stats->ms_adjacency = res->ms_symbolic;
+		stats->adjacency = t.adjacency; stats->max_degree = t.max_degree; stats->asymmetric = 0;
+		stats->launches = t.launches; stats->fused_rounds = t.fused_rounds;
+		stats->rows_wave = t.rows_wave; stats->rows_thread = N - t.rows_wave;
+		stats->ms_adjacency = t.ms_adjacency;
 		SPS_HIP(hipEventElapsedTime(&stats->ms_sweep, c->ev[EV_SYMBOLIC], c->ev[EV_N0]));
 		SPS_HIP(hipEventElapsedTime(&stats->ms_assign, c->ev[EV_N0], c->ev[EV_END]));
 	}

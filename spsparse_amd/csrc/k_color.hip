@@ -426,26 +426,27 @@ uint32_t *order_by_key(spsamd_ctx *c, PairSort &sort, uint64_t N, int key_bits, 
 	return cptr;
 }
 
-int color_graph(spsamd_ctx *c, const spsamd_coo *A, char transpose, int order, uint32_t seed, int color_flags, int32_t *color,
-	int32_t *perm, int32_t *color_ptr, size_t ptr_capacity, int mem, size_t *out_ncolors, spsamd_color_stats *stats,
-	spsamd_result *res)
+// ---- the frame of a graph call (GraphCall, internal.h)
+
+bool GraphCall::open(const spsamd_coo *A, char transpose, int order, int flags, int mem, void *stats, size_t stats_bytes, int *rc)
 {
-	if (order != SPSAMD_COLOR_ORDER_HASH && order != SPSAMD_COLOR_ORDER_DEGREE) throw Error{SPSAMD_EINVAL, "unknown colouring order"};
-	if (color_flags & ~SPSAMD_COLOR_SYMMETRIC) throw Error{SPSAMD_EINVAL, "unknown color_flags"};
+	if (order != SPSAMD_COLOR_ORDER_HASH && order != SPSAMD_COLOR_ORDER_DEGREE) throw Error{SPSAMD_EINVAL, op->bad_order};
+	if (flags & ~SPSAMD_COLOR_SYMMETRIC) throw Error{SPSAMD_EINVAL, op->bad_flags};
 	if (mem != SPSAMD_MEM_HOST && mem != SPSAMD_MEM_DEVICE) throw Error{SPSAMD_EINVAL, "mem of the output must be SPSAMD_MEM_HOST or SPSAMD_MEM_DEVICE"};
 	const int lead = transpose == 'T' ? 1 : 0;
-	const uint64_t N = A->shape0;
-	if (A->shape0 != A->shape1) throw Error{SPSAMD_EDIM, "op(A) must be square for a colouring"};
+	N = A->shape0;
+	if (A->shape0 != A->shape1) throw Error{SPSAMD_EDIM, op->not_square};
 	if (N >= (uint64_t(1) << 31)) throw Error{SPSAMD_EINVAL, "shape exceeds the int32 index range"};
-	const bool symmetric = (color_flags & SPSAMD_COLOR_SYMMETRIC) != 0;
+	symmetric = (flags & SPSAMD_COLOR_SYMMETRIC) != 0;
+	kind = mem == SPSAMD_MEM_DEVICE ? hipMemcpyDeviceToDevice : hipMemcpyDeviceToHost;
 	{
 		const OperandView view = operand_view(c, A);
 		const uint64_t n = view.coo.nnz;
-		const void *buf[3] = {color, perm, color_ptr};
+		const void *buf[3] = {ids_out, list_out, ptr_out};
 		const uint64_t bytes[3] = {N * 4, N * 4, (uint64_t)ptr_capacity * 4};
 		for (int p = 0; p < 3; ++p)
 			for (int q = p + 1; q < 3; ++q)
-				if (ranges_overlap(buf[p], bytes[p], buf[q], bytes[q])) throw Error{SPSAMD_EINVAL, "color, perm and color_ptr overlap"};
+				if (ranges_overlap(buf[p], bytes[p], buf[q], bytes[q])) throw Error{SPSAMD_EINVAL, op->overlap};
 		const void *arr[3] = {view.coo.idx0, view.coo.idx1, view.coo.val};
 		for (int p = 0; p < 3; ++p)
 			for (int k = 0; k < 3; ++k)
@@ -455,108 +456,125 @@ int color_graph(spsamd_ctx *c, const spsamd_coo *A, char transpose, int order, u
 				if (in_output_sets(c, buf[p], bytes[p])) throw Error{SPSAMD_EINVAL, "an output buffer lies in an output set of the context"};
 	}
 	std::memset(res, 0, sizeof(*res));
-	if (stats) std::memset(stats, 0, sizeof(*stats));
+	if (stats) std::memset(stats, 0, stats_bytes);
 	res->shape0 = res->shape1 = N;
 
 	SPS_HIP(hipSetDevice(c->device));
 	c->arena.reset();
 	hipStream_t st = c->stream;
 	SPS_HIP(hipEventRecord(c->ev[EV_BEGIN], st));
-	MaskKeys K;
 	mask_keys(c, A, lead, N, N, &K);
 	SPS_HIP(hipEventRecord(c->ev[EV_CONSOLIDATED], st));
 	res->nnz_a = K.n;
-	*out_ncolors = 0;
-	if (N == 0) {                                                      // no vertex, no colour: color_ptr is the one entry 0
-		if (color_ptr && ptr_capacity < 1) {
-			c->last_error = "color_ptr is too small: it needs one entry per colour and one more; *out_ncolors holds the colours";
-			return SPSAMD_ECAPACITY;
-		}
-		if (color_ptr && mem == SPSAMD_MEM_HOST) color_ptr[0] = 0;
-		else if (color_ptr) { fill_zero(c, color_ptr, sizeof(int32_t)); SPS_HIP(hipStreamSynchronize(st)); }
-		return SPSAMD_OK;
+	*out_count = 0;
+	if (N == 0) {                                                      // no vertex, nothing to count: ptr_out is the one entry 0
+		*rc = fits(0) ? SPSAMD_OK : SPSAMD_ECAPACITY;
+		if (*rc != SPSAMD_OK || !ptr_out) return false;
+		if (mem == SPSAMD_MEM_HOST) ptr_out[0] = 0;
+		else { fill_zero(c, ptr_out, sizeof(int32_t)); SPS_HIP(hipStreamSynchronize(st)); }
+		return false;
 	}
+	g = graph_adjacency(c, K, N, symmetric);
+	const int kp = c->tune.*op->path, kr = c->tune.*op->row, kf = c->tune.*op->fuse_rows, kw = c->tune.*op->wave_deg;
+	path = kp == 1 || kp == 2 ? kp : 0;
+	rowk = kr == 1 || kr == 2 ? kr : 0;
+	fuse_rows = kf > 0 ? (uint32_t)kf : op->fuse_rows_default;
+	wave_deg = kw > 0 ? (uint32_t)kw : op->wave_deg_default;
+	acc = get_zeroed<unsigned long long>(c, op->acc_len);
+	ctr = get_zeroed<uint32_t>(c, 2 * op->nlists);
+	deg = c->arena.get<uint32_t>(N);
+	ids = c->arena.get<int32_t>(N);
+	h = (uint32_t *)c->host_staging(op->acc_len * sizeof(unsigned long long));
+	return true;
+}
 
-	// ---- adjacency
-	const GraphRows g = graph_adjacency(c, K, N, symmetric);
-	const uint32_t *ptr = g.ptr;
-	const int32_t *adj = g.adj;
-	const int path = c->tune.color_path == 1 || c->tune.color_path == 2 ? c->tune.color_path : 0;
-	const int rowk = c->tune.color_row == 1 || c->tune.color_row == 2 ? c->tune.color_row : 0;
-	const uint32_t fuse_rows = c->tune.color_fuse_rows > 0 ? (uint32_t)c->tune.color_fuse_rows : COL_FUSE_ROWS;
-	const uint32_t wave_deg = c->tune.color_wave_deg > 0 ? (uint32_t)c->tune.color_wave_deg : COL_WAVE_DEG;
-	unsigned long long *acc = get_zeroed<unsigned long long>(c, COL_ACC);
-	uint32_t *ctr = get_zeroed<uint32_t>(c, 4);                         // [2 * parity + class]: the lengths of the worklists
-	uint32_t *deg = c->arena.get<uint32_t>(N);
-	int32_t *col = c->arena.get<int32_t>(N), *pending = c->arena.get<int32_t>(N);
-	uint32_t *wait = get_zeroed<uint32_t>(c, N);
-	uint32_t *list_t[2] = {c->arena.get<uint32_t>(N), c->arena.get<uint32_t>(N)};
-	uint32_t *list_w[2] = {c->arena.get<uint32_t>(N), c->arena.get<uint32_t>(N)};
-	graph_classes(c, g, N, deg, col, list_t[0], list_w[0], ctr, acc, wave_deg, rowk, symmetric);
-	uint32_t *h = (uint32_t *)c->host_staging(COL_ACC * sizeof(unsigned long long));
-	auto read_counts = [&](int par, uint32_t *cnt_t, uint32_t *cnt_w) {
-		SPS_HIP(hipMemcpyAsync(h, ctr + 2 * par, 2 * sizeof(uint32_t), hipMemcpyDeviceToHost, st));
-		SPS_HIP(hipStreamSynchronize(st));
-		*cnt_t = h[0]; *cnt_w = h[1];
-	};
-	uint32_t cnt_t = 0, cnt_w = 0;
-	SPS_HIP(hipEventRecord(c->ev[EV_SYMBOLIC], st));
-	read_counts(0, &cnt_t, &cnt_w);
+void GraphCall::read_counts(int par, uint32_t *cnt)
+{
+	SPS_HIP(hipMemcpyAsync(h, ctr + op->nlists * par, op->nlists * sizeof(uint32_t), hipMemcpyDeviceToHost, c->stream));
+	SPS_HIP(hipStreamSynchronize(c->stream));
+	std::memcpy(cnt, h, op->nlists * sizeof(uint32_t));
+}
 
-	// ---- sweep
-	ColArgs a;
-	a.ptr = ptr; a.adj = adj; a.deg = deg; a.color = col; a.pending = pending; a.wait = wait; a.acc = acc; a.seed = seed;
-	a.by_degree = order == SPSAMD_COLOR_ORDER_DEGREE; a.directed = symmetric;
-	uint64_t launches = 0, rounds = 0;
-	bool fused = false;
-	for (int par = 0; cnt_t || cnt_w; par ^= 1) {
-		if (path != 1 && (path == 2 || (uint64_t)cnt_t + cnt_w <= fuse_rows)) {
-			k_col_fused<<<dim3(1), dim3(COL_NT), 0, st>>>(a, list_t[par], list_t[par ^ 1], cnt_t, list_w[par], list_w[par ^ 1], cnt_w);
-			SPS_LAUNCH_CHECK();
-			++launches; fused = true;
-			break;
-		}
-		if (cnt_t) { k_col_thread<<<dim3(grid_for(cnt_t)), dim3(256), 0, st>>>(a, list_t[par], cnt_t); SPS_LAUNCH_CHECK(); ++launches; }
-		if (cnt_w) { k_col_wave<<<dim3(grid_for(cnt_w, 4)), dim3(256), 0, st>>>(a, list_w[par], cnt_w); SPS_LAUNCH_CHECK(); ++launches; }
-		k_col_commit<<<dim3(grid_for((size_t)cnt_t + cnt_w)), dim3(256), 0, st>>>(a, list_t[par], cnt_t, list_w[par], cnt_w,
-			list_t[par ^ 1], list_w[par ^ 1], ctr + 2 * (par ^ 1), ctr + 2 * par);
-		SPS_LAUNCH_CHECK();
-		++rounds;
-		read_counts(par ^ 1, &cnt_t, &cnt_w);
-	}
-	if (K.n) { k_col_conflicts<<<dim3(grid_for(K.n)), dim3(256), 0, st>>>(K.i, K.j, K.n, col, acc); SPS_LAUNCH_CHECK(); }
-	unsigned long long hacc[COL_ACC];
-	SPS_HIP(hipMemcpyAsync(h, acc, sizeof hacc, hipMemcpyDeviceToHost, st));
-	SPS_HIP(hipStreamSynchronize(st));
-	std::memcpy(hacc, h, sizeof hacc);
-	const uint64_t fused_rounds = fused ? hacc[COL_FUSED] : 0;
-	rounds = std::max<uint64_t>(rounds + fused_rounds, 1);              // (the isolated vertices are round 0)
-	const uint64_t ncolors = std::max<uint64_t>(hacc[COL_NCOLORS], 1);  // (... and hold colour 0)
-	*out_ncolors = ncolors;
-	if (color_ptr && ptr_capacity < ncolors + 1) {
-		c->last_error = "color_ptr is too small: it needs one entry per colour and one more; *out_ncolors holds the colours";
-		return SPSAMD_ECAPACITY;
-	}
+bool GraphCall::fits(uint64_t count)
+{
+	*out_count = count;
+	if (!ptr_out || ptr_capacity >= count + 1) return true;
+	c->last_error = op->too_small;
+	return false;
+}
 
-	// ---- perm, color_ptr and delivery
-	const hipMemcpyKind kind = mem == SPSAMD_MEM_DEVICE ? hipMemcpyDeviceToDevice : hipMemcpyDeviceToHost;
-	if (perm || color_ptr) {
-		PairSort sort(c, N);
-		k_col_keys<<<dim3(grid_for(N)), dim3(256), 0, st>>>(col, N, sort.keys);
-		SPS_LAUNCH_CHECK();
-		order_by_key(c, sort, N, bits_of(ncolors), 0, ncolors, color_ptr != nullptr, perm, color_ptr, kind);   // stable: ascending index inside a colour
-	}
-	SPS_HIP(hipMemcpyAsync(color, col, N * sizeof(int32_t), kind, st));
+GraphTotals GraphCall::close(const unsigned long long *hacc, int fused_slot)
+{
 	finish_call(c, res);
 	SPS_HIP(hipEventElapsedTime(&res->ms_consolidate, c->ev[EV_BEGIN], c->ev[EV_CONSOLIDATED]));
 	SPS_HIP(hipEventElapsedTime(&res->ms_symbolic, c->ev[EV_CONSOLIDATED], c->ev[EV_SYMBOLIC]));
 	SPS_HIP(hipEventElapsedTime(&res->ms_numeric, c->ev[EV_SYMBOLIC], c->ev[EV_END]));
+	return GraphTotals{hacc[GRAPH_ADJ], hacc[GRAPH_MAXDEG], launches, fused ? hacc[fused_slot] : 0, hacc[GRAPH_ROWS_W], res->ms_symbolic};
+}
+
+static const GraphOp COL_OP = {"unknown colouring order", "unknown color_flags", "op(A) must be square for a colouring",
+	"color, perm and color_ptr overlap", "color_ptr is too small: it needs one entry per colour and one more; *out_ncolors holds the colours",
+	&Tuning::color_path, &Tuning::color_row, &Tuning::color_fuse_rows, &Tuning::color_wave_deg, COL_FUSE_ROWS, COL_WAVE_DEG, COL_ACC, 2};
+
+int color_graph(spsamd_ctx *c, const spsamd_coo *A, char transpose, int order, uint32_t seed, int color_flags, int32_t *color,
+	int32_t *perm, int32_t *color_ptr, size_t ptr_capacity, int mem, size_t *out_ncolors, spsamd_color_stats *stats,
+	spsamd_result *res)
+{
+	GraphCall gc{c, &COL_OP, color, perm, color_ptr, ptr_capacity, out_ncolors, res};
+	int rc;
+	if (!gc.open(A, transpose, order, color_flags, mem, stats, sizeof(*stats), &rc)) return rc;
+	hipStream_t st = c->stream;
+	const uint64_t N = gc.N; const MaskKeys &K = gc.K;
+	int32_t *col = gc.ids, *pending = c->arena.get<int32_t>(N);
+	uint32_t *wait = get_zeroed<uint32_t>(c, N);
+	uint32_t *list_t[2] = {c->arena.get<uint32_t>(N), c->arena.get<uint32_t>(N)};
+	uint32_t *list_w[2] = {c->arena.get<uint32_t>(N), c->arena.get<uint32_t>(N)};
+	graph_classes(c, gc.g, N, gc.deg, col, list_t[0], list_w[0], gc.ctr, gc.acc, gc.wave_deg, gc.rowk, gc.symmetric);
+	SPS_HIP(hipEventRecord(c->ev[EV_SYMBOLIC], st));
+	uint32_t cnt0[2];
+	gc.read_counts(0, cnt0);
+
+	// ---- sweep
+	ColArgs a;
+	a.ptr = gc.g.ptr; a.adj = gc.g.adj; a.deg = gc.deg; a.color = col; a.pending = pending; a.wait = wait; a.acc = gc.acc; a.seed = seed;
+	a.by_degree = order == SPSAMD_COLOR_ORDER_DEGREE; a.directed = gc.symmetric;
+	gc.sweep(cnt0,
+		[&](int par, const uint32_t *cnt) {
+			uint64_t launches = 0;                                     // (the commit is not counted: it is the round's bookkeeping)
+			if (cnt[0]) { k_col_thread<<<dim3(grid_for(cnt[0])), dim3(256), 0, st>>>(a, list_t[par], cnt[0]); SPS_LAUNCH_CHECK(); ++launches; }
+			if (cnt[1]) { k_col_wave<<<dim3(grid_for(cnt[1], 4)), dim3(256), 0, st>>>(a, list_w[par], cnt[1]); SPS_LAUNCH_CHECK(); ++launches; }
+			k_col_commit<<<dim3(grid_for((size_t)cnt[0] + cnt[1])), dim3(256), 0, st>>>(a, list_t[par], cnt[0], list_w[par], cnt[1],
+				list_t[par ^ 1], list_w[par ^ 1], gc.ctr + 2 * (par ^ 1), gc.ctr + 2 * par);
+			SPS_LAUNCH_CHECK();
+			return launches;
+		},
+		[&](int par, const uint32_t *cnt) {
+			k_col_fused<<<dim3(1), dim3(COL_NT), 0, st>>>(a, list_t[par], list_t[par ^ 1], cnt[0], list_w[par], list_w[par ^ 1], cnt[1]);
+			SPS_LAUNCH_CHECK();
+		});
+	if (K.n) { k_col_conflicts<<<dim3(grid_for(K.n)), dim3(256), 0, st>>>(K.i, K.j, K.n, col, gc.acc); SPS_LAUNCH_CHECK(); }
+	unsigned long long hacc[COL_ACC];
+	SPS_HIP(hipMemcpyAsync(gc.h, gc.acc, sizeof hacc, hipMemcpyDeviceToHost, st));
+	SPS_HIP(hipStreamSynchronize(st));
+	std::memcpy(hacc, gc.h, sizeof hacc);
+	const uint64_t ncolors = std::max<uint64_t>(hacc[COL_NCOLORS], 1);  // (the isolated vertices hold colour 0 ...)
+	if (!gc.fits(ncolors)) return SPSAMD_ECAPACITY;
+
+	// ---- perm, color_ptr and delivery
+	if (perm || color_ptr) {
+		PairSort sort(c, N);
+		k_col_keys<<<dim3(grid_for(N)), dim3(256), 0, st>>>(col, N, sort.keys);
+		SPS_LAUNCH_CHECK();
+		order_by_key(c, sort, N, bits_of(ncolors), 0, ncolors, color_ptr != nullptr, perm, color_ptr, gc.kind);   // stable: ascending index inside a colour
+	}
+	gc.deliver();
+	const GraphTotals t = gc.close(hacc, COL_FUSED);
 	if (stats) {
-		stats->ncolors = ncolors; stats->rounds = rounds;
-		stats->adjacency = hacc[GRAPH_ADJ]; stats->max_degree = hacc[GRAPH_MAXDEG]; stats->conflicts = hacc[COL_CONFLICTS];
-		stats->launches = launches; stats->fused_rounds = fused_rounds;
-		stats->rows_thread = hacc[GRAPH_ROWS_T]; stats->rows_wave = hacc[GRAPH_ROWS_W];
-		stats->ms_adjacency = res->ms_symbolic; stats->ms_color = res->ms_numeric;
+		stats->ncolors = ncolors; stats->rounds = std::max<uint64_t>(gc.rounds + t.fused_rounds, 1);   // (... and are round 0)
+		stats->adjacency = t.adjacency; stats->max_degree = t.max_degree; stats->conflicts = hacc[COL_CONFLICTS];
+		stats->launches = t.launches; stats->fused_rounds = t.fused_rounds;
+		stats->rows_thread = hacc[GRAPH_ROWS_T]; stats->rows_wave = t.rows_wave;
+		stats->ms_adjacency = t.ms_adjacency; stats->ms_color = res->ms_numeric;
 	}
 	return SPSAMD_OK;
 }
