@@ -51,6 +51,7 @@ __global__ __launch_bounds__(NT, 4) void k_dense(const Cell *cells, uint32_t nce
 	constexpr int SB = DENSE_SCAN_BATCH < GPW ? DENSE_SCAN_BATCH : GPW;     // groups of one scan-out batch
 	static_assert(GPW % SB == 0, "whole batches");
 	static_assert(!PLAIN || (!PAT && MODE != MODE_COUNT), "PLAIN: STORE and DIGEST without EXACT_PATTERN");
+	static_assert(NT * R <= DENSE_SLACK, "the masked lanes of a chunk's last step load inside the slack behind the B tuples");
 	__shared__ double acc[MODE == MODE_COUNT ? 1 : W + 64];      // + one dump slot per lane: tuples past the end of a segment's last item land there
 	__shared__ __attribute__((aligned(16))) uint8_t ctouch[MODE == MODE_COUNT ? W : 16];     // COUNT: the touched columns
 	__shared__ uint32_t s_cpref[NT + 1];     // compacted segments: exclusive ITEM prefix (+ total)

@@ -497,7 +497,7 @@ static BTup *ensure_btup(spsamd_ctx *c, MultiplyArgs &a, Prepared *p)
 {
 	if (p->btup) return p->btup;
 	wait_b_tuples(c, a);
-	p->btup = p->get<BTup>((size_t)p->m.nnz + DENSE_R);             // a dense-cell item reads R tuples: slack after the last one
+	p->btup = p->get<BTup>((size_t)p->m.nnz + DENSE_SLACK);
 	k_pack_b<<<dim3(grid_for(p->m.nnz)), dim3(256), 0, c->stream>>>(p->m.col, p->m.val, p->m.nnz, p->btup);
 	SPS_LAUNCH_CHECK();
 	return p->btup;

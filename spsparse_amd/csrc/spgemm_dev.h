@@ -398,6 +398,11 @@ __device__ __forceinline__ uint32_t expand_lookup(const Expand<NT, PB> &L, uint3
 #define DENSE_DEPTH 1
 #endif
 constexpr int DENSE_R = DENSE_R_V;
+// Tuples allocated behind the last one of an array of B tuples that k_dense reads.  The last step of a chunk's last batch
+// deals NT items whatever is left: every lane behind the last item -- up to NT - 1 of them, whole waves included -- takes the
+// chunk's last segment, computes a position past its end and loads R tuples there all the same (the result is masked).  The
+// farthest such load ends less than NT R tuples behind the segment's end; 1024 is the larger NT.
+constexpr int DENSE_SLACK = 1024 * DENSE_R;
 
 template <int NT, int PB>
 struct ExpandR {

@@ -51,7 +51,7 @@ struct Heavy {
 	uint32_t nnzb = 0;
 
 	// 32-bit byte offsets into B's tuples suffice (fetch_piece): always, short of 3.5e8 tuples
-	uint32_t narrow() const { return ((uint64_t)nnzb + DENSE_R) * 12u < (uint64_t(1) << 32) ? 1u : 0u; }
+	uint32_t narrow() const { return ((uint64_t)nnzb + DENSE_SLACK) * 12u < (uint64_t(1) << 32) ? 1u : 0u; }
 	// the claim counter of a tile launch (one zeroed counter per launch of a call; null: static walk)
 	template <int MODE> uint32_t *tile_claim() const { return tile_ctr ? tile_ctr + (MODE == MODE_STORE ? 1 : 0) : nullptr; }
 };

@@ -468,7 +468,7 @@ static void heavy_window_major(spsamd_ctx *c, Heavy &hv, const ConMat &B, uint32
 	SPS_LAUNCH_CHECK();
 	k_wm_ptr<<<dim3(ntile), dim3(WM_NT), 0, st>>>(wcnt, nrowb, hv.nwin, nwp, ntile, tilesum, wbase, hv.wptr);
 	SPS_LAUNCH_CHECK();
-	hv.btw = pb->get<BTup>((size_t)B.nnz + DENSE_R);
+	hv.btw = pb->get<BTup>((size_t)B.nnz + DENSE_SLACK);
 	k_wm_scatter<<<dim3(grid_for(B.nnz)), dim3(256), 0, st>>>(B.row, B.col, B.val, B.nnz, wshift, hv.bwin, hv.nwin1, hv.wptr, nrowb, hv.btw);
 	SPS_LAUNCH_CHECK();
 }
@@ -508,7 +508,7 @@ int heavy_b_index(spsamd_ctx *c, const ConMat &B, const uint32_t *bptr, uint32_t
 		throw TooWide{w2 << wshift};
 	}
 	const uint32_t nwin1 = nwin + 1, nwp = (nwin + 7u) & ~7u, nbw = (((nwin + 31u) >> 5) + 3u) & ~3u;
-	pb->reserve(nrowb * nwin1 * 4 + nrowb * nwp * 2 + nrowb * nbw * 4 + (nrowb * nwin + 1) * 4 + ((size_t)B.nnz + DENSE_R) * sizeof(BTup) + 4096);   // (a handle: one slab for all five)
+	pb->reserve(nrowb * nwin1 * 4 + nrowb * nwp * 2 + nrowb * nbw * 4 + (nrowb * nwin + 1) * 4 + ((size_t)B.nnz + DENSE_SLACK) * sizeof(BTup) + 4096);   // (a handle: one slab for all five)
 	pb->bwin = pb->get<uint32_t>(nrowb * nwin1);
 	pb->wcnt = pb->get<uint16_t>(nrowb * nwp);
 	pb->bocc = pb->get<uint32_t>(nrowb * nbw);

@@ -113,6 +113,31 @@ def check_digest(res, want, what):
     assert res.sum == vsum, "%s: digest sink: sum %r, want %r" % (what, res.sum, vsum)
 
 
+# ---- planned operands (tests/test_gpu_tile_shapes.py, tests/test_gpu_dense_cells.py)
+
+def sink_flags(flag):
+    from spsparse_amd import capi
+    return {"plain": 0, "exact": capi.SINK_EXACT_PATTERN, "ordered": capi.SINK_ORDERED}[flag]
+
+
+def operands(p, emit, keep):
+    """(a, b, C, scalei, scalek) as C structs over the host arrays of a plan of tests/tile_plan.py."""
+    from spsparse_amd import capi
+    from tests import tile_plan as tp
+
+    def vec(x):
+        if x is None:
+            return None
+        s, k = capi.host_vec(x.idx, x.val, x.shape0)
+        keep.append(k)
+        return s
+    a, ka = capi.host_coo(p.A.idx0, p.A.idx1, p.A.val, p.A.shape, p.A.sort0)
+    b, kb = capi.host_coo(p.B.idx0, p.B.idx1, p.B.val, p.B.shape, p.B.sort0)
+    keep += [ka, kb]
+    C_, scalei, scalek = tp.emit_args(p.A, p.B, emit)
+    return a, b, C_, vec(scalei), vec(scalek)
+
+
 # ---- spsamd_solve_tri (tests/test_gpu_solve.py, tests/test_gpu_solve_wide.py)
 
 SENT = -7.5          # what solve() fills X and the padding of B and X with

@@ -13,34 +13,12 @@ import re
 import pytest
 
 from tests import tile_plan as tp
-from tests.gpu_util import Knobs, check_digest, check_tuples, ctx  # noqa: F401  (ctx: fixture)
+from tests.gpu_util import Knobs, check_digest, check_tuples, ctx, operands, sink_flags  # noqa: F401  (ctx: fixture)
 from tests.tile_plan import BITMAP, HASH1, HASH2
 
 pytestmark = pytest.mark.gpu
 
 SCHEMES = {"bitmap": BITMAP, "hash2": HASH2, "hash1": HASH1}
-
-
-def sink_flags(flag):
-    from spsparse_amd import capi
-    return {"plain": 0, "exact": capi.SINK_EXACT_PATTERN, "ordered": capi.SINK_ORDERED}[flag]
-
-
-def operands(p, emit, keep):
-    """(a, b, C, scalei, scalek) as C structs over the plan's host arrays."""
-    from spsparse_amd import capi
-
-    def vec(x):
-        if x is None:
-            return None
-        s, k = capi.host_vec(x.idx, x.val, x.shape0)
-        keep.append(k)
-        return s
-    a, ka = capi.host_coo(p.A.idx0, p.A.idx1, p.A.val, p.A.shape, p.A.sort0)
-    b, kb = capi.host_coo(p.B.idx0, p.B.idx1, p.B.val, p.B.shape, p.B.sort0)
-    keep += [ka, kb]
-    C_, scalei, scalek = tp.emit_args(p.A, p.B, emit)
-    return a, b, C_, vec(scalei), vec(scalek)
 
 
 def run_plan(ctx, capfd, p, scheme, flag="plain", emit="plain", extra=None):

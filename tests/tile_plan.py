@@ -49,16 +49,18 @@ def item_cost(prods, L):
     return ((prods // R + L + 63) & ~63) + 64
 
 
-def cells_of_row(L, window_products, scheme, W, direct_min=None, coo=True, no_tiles=False, long_cap=0, long_dense_min=None):
+def cells_of_row(L, window_products, scheme, W, direct_min=None, coo=True, no_tiles=False, long_cap=0, long_dense_min=None, dense_min=None):
     """k_cells (csrc/symbolic_heavy.hip) for one row of L A tuples and its products per column window, under the limits
     heavy_prepare sets for a scheme.  direct_min: the knob (None: direct cells off, their default); coo: the COO sink
     (the first generation's tiles then hold fewer products); long_cap, long_dense_min: the knobs for rows too long for
-    tiles.  Returns (cells, tiles): cells in the row's order as (kind, wa, wb, products), kind one of "tile", "direct",
-    "dense", "hash1024" .. "hash8192"; tiles as (kind, [indices into cells])."""
+    tiles; dense_min: the knob (64 .. 4096, else the scheme's default).  Returns (cells, tiles): cells in the row's order as
+    (kind, wa, wb, products), kind one of "tile", "direct", "dense", "hash1024" .. "hash8192"; tiles as (kind, [indices
+    into cells])."""
     wshift = {8192: 13, 16384: 14}[W]
     tiles_on = not no_tiles
     tileable = tiles_on and L <= TILE_LMAX
-    dense_min = DENSE_MIN_BITMAP if scheme == BITMAP and tiles_on else DENSE_MIN_DEFAULT
+    user_dense_min = dense_min is not None and 64 <= dense_min <= 4096
+    dense_min = dense_min if user_dense_min else (DENSE_MIN_BITMAP if scheme == BITMAP and tiles_on else DENSE_MIN_DEFAULT)
     tile_cap = BM_MAXOUT if scheme == BITMAP else HASH_TILE_CAP
     span_cap = BM_WORDS >> (wshift - 6) if scheme == BITMAP else 0
     pb = {"tile": TILE_ITEMS if scheme != HASH1 else (TILE_PB_STORE if coo else TILE_PB), "direct": W}
